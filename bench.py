@@ -2,6 +2,7 @@
 """bench.py — voice-samples/sec of the batch render on N MI355X (one process per GPU).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg3_poly|cfg2|cfg4|cfg4_b1024|p3|p4] [--flags F]   (F: 1 exact, 64 keep the fast forms ...)
+                    [--full] [--dump-outputs DIR]
 
 Workloads (BASELINE.json `configs`; SURVEY 8(d) spells them out):
     cfg3 (default; = config 5 at 8 GPUs)  patch P1 saw VCO -> ladder VCF -> VCA, ADSR gated by an LFO square; 262 144 voices per GPU,
@@ -22,7 +23,8 @@ when WORLD_SIZE is not set — bench.py starts the N ranks itself (one per devic
 The control plane (barrier, max over ranks, handing the RCCL unique id around) is torch.distributed/gloo on CPU tensors;
 the data path never touches it.
 
-The default run (cfg3, 1 GPU, default sizes) ALSO times, after the headline steps, SIDE_STEPS steps each after one warm-up, same bracketing
+A plain run does only what the headline needs: set-up, the warm-up steps, the timed steps, the outputs if asked for, the line.
+`--full` (off by default) ALSO times, for cfg3 on 1 GPU at its default size, after the headline steps, SIDE_STEPS steps each after one warm-up, same bracketing
 (device sync both sides): the headline workload in the exact render mode (`cfg3_exact`: the reference's own arithmetic, bit for bit), the fully
 per-voice variant (`cfg3_poly`), config 2 (4 096 identical voices), config 4 (P2 FM pair, 65 536 voices) as the library renders it by default — the
 modulator inside its feedback loop exact as a whole (csrc/approx.cpp: a loop through a pitch has no error bound; profiles/r05_horizon.json) — and
@@ -31,13 +33,17 @@ buffer_size 1024 (`cfg4_b1024`, `cfg4_b1024_fast`), and the workloads of scope r
 the same line as four flat scalars each inside `roofline` (`<name>_ms_per_step` / `_frac_hbm` / `_frac_hbm_kernel` / `_kernel_ms`); each one's
 own full bench line (`configs`) and the long prose go to bench_detail.json beside this file and to stderr, NOT onto the line: the driver's record keeps
 the last 8 KB of stdout, the line is held under 6 KB (shape_line; tests/test_dist.py).  metric / value / config / roofline.frac stay the
-headline's.  `--no-side-configs` skips them.
+headline's.  `--no-side-configs` skips them; `--full` also adds `cpu_baseline` (`--no-cpu` skips it).
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step computed, as DIR/<name>.npy: `mix` ([2][T] f32, after the
+reduce for N > 1), `frames` ([planes][T][k] f32: every sample of k voices of this rank's frames, a fixed seeded draw that fits DUMP_BYTES in all)
+and `frames_voices` (those voices' indices, f64).  The same arguments give the same inputs, so two builds can be compared output for output.
 
 Prints ONE JSON line (rank 0): metric/value/unit per the driver's contract, plus
   roofline     — achieved = algorithmic bytes of a step / step time (4 B x planes x V x T / t_render, per GPU),
                  peak 8 TB/s HBM; `frac_kernel` is the same for the dominant kernel alone (HIP events on the kernel's own
                  stream, read back through srack_render_kernel_ms — the figure rocprofv3's per-kernel average reproduces)
-  cpu_baseline — the C oracle in the reference's structure (block-major execute, one object graph per voice, all
+  cpu_baseline — (--full) the C oracle in the reference's structure (block-major execute, one object graph per voice, all
                  oscillator ports computed) on the host cores, bounded sample (N = 1 only).
 """
 import argparse
@@ -88,6 +94,11 @@ FM_PAIR_F64_OPS = {"render_fm_pair": 48, "render_fm_pair_ring": 48,
 F64_LANE_OPS_MEASURED = 33.3e12
 
 WORKLOADS = ("cfg3", "cfg3_poly", "cfg2", "cfg4", "cfg4_b1024", "p3", "p4")
+
+# --dump-outputs: at most this many bytes in all; the frames are sampled by voice (a fixed seed: the same voices from run to run)
+DUMP_BYTES = 64_000_000
+DUMP_VOICES = 128
+DUMP_SEED = 20240607
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -283,6 +294,28 @@ class HipBackend:
                  pci_bus_id=bus, ranks_seen=self.ranks_seen, voices=idx, frames=frames[:, :, torch.from_numpy(idx).to(self.dev)].cpu().numpy(),
                  frames_sum_f64=frames.double().sum(dim=2).cpu().numpy(), frames_abs_sum_f64=frames.double().abs().sum(dim=2).cpu().numpy(),
                  partial_mix=partial, reduced_mix=reduced if reduced is not None else partial, planes=np.array(p.planes()[1]), info=p.info())
+
+    def outputs(self):
+        """--dump-outputs: what the last timed step left for its caller, as host arrays — the [2][T] mix and every sample of a fixed, seeded
+        draw of this rank's voices out of the frames [planes][T][V] (as many voices as fit DUMP_BYTES beside the mix, at most DUMP_VOICES)."""
+        torch, a = self.torch, self.args
+        V, T = a.voices, a.samples
+        out = {}
+        if not a.no_mix:
+            mix = self.mix.cpu().numpy()
+            if a.block:  # one call per block: that call's mix is [2][n] at 2 * t
+                flat = mix.reshape(-1)
+                mix = np.concatenate([flat[2 * t:2 * t + 2 * min(a.block, T - t)].reshape(2, -1) for t in range(0, T, a.block)], axis=1)
+            out["mix"] = mix
+        if self.frames is not None:
+            room = DUMP_BYTES - sum(x.nbytes for x in out.values()) - 8 * DUMP_VOICES
+            k = min(V, DUMP_VOICES, room // (4 * self.n_planes * T))
+            if k < 1:
+                raise SystemExit(f"--dump-outputs: one voice's frames ({self.n_planes} x {T} samples) do not fit in {DUMP_BYTES} bytes")
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(V, k, replace=False))
+            out["frames"] = self.frames[:, :, torch.from_numpy(idx).to(self.dev)].cpu().numpy()
+            out["frames_voices"] = idx.astype(np.float64)
+        return out
 
     def step(self):
         a = self.args
@@ -546,6 +579,18 @@ def write_detail(detail):
     print("[bench] detail:\n" + text, file=sys.stderr, flush=True)
 
 
+def write_outputs(directory, arrays):
+    """--dump-outputs: each array as `directory`/<name>.npy, f32 or f64, DUMP_BYTES in all at most."""
+    total = sum(x.nbytes for x in arrays.values())
+    assert total <= DUMP_BYTES, total
+    os.makedirs(directory, exist_ok=True)
+    for name, x in arrays.items():
+        assert x.dtype in (np.float32, np.float64), (name, x.dtype)
+        np.save(os.path.join(directory, name + ".npy"), x)
+    print(f"[bench] outputs of the last timed step in {directory}: " + ", ".join(f"{n} {list(x.shape)} {x.dtype}" for n, x in arrays.items()),
+          file=sys.stderr, flush=True)
+
+
 def arithmetic_short(flags, info=""):
     """arithmetic_note in one sentence (the line carries this; the paragraph is in bench_detail.json and DESIGN.md section 2)"""
     if "; exact osc " in info and not flags & 1:
@@ -589,6 +634,8 @@ def run_rank(args, backend_cls=HipBackend):
     elapsed = cp.max(mine)
     per_rank_ms = [x / args.steps * 1e3 for x in cp.gather(mine)]
     kernel_ms, n_launch = be.kernel_ms()
+    if args.dump_outputs and rank == 0:  # before anything else renders into the step's buffers
+        write_outputs(args.dump_outputs, be.outputs())
     if os.environ.get("SRACK_BENCH_DUMP") and hasattr(be, "dump"):
         be.dump(os.environ["SRACK_BENCH_DUMP"])
 
@@ -659,7 +706,7 @@ def run_rank(args, backend_cls=HipBackend):
                                                      note="rocprofv3 PMC passes of this command (profiles/run_profile.sh); a profiler cannot run inside the timed region")
         if world > 1:  # a straggler shows here (the value is paced by the slowest rank)
             print("[bench] ms per step by rank: " + " ".join(f"{r}:{m:.3f}" for r, m in enumerate(per_rank_ms)), file=sys.stderr, flush=True)
-        if (world == 1 and be.name == "hip" and args.workload == "cfg3" and not args.no_side_configs and args.flags == 0 and not args.block and not args.no_frames
+        if (args.full and world == 1 and be.name == "hip" and args.workload == "cfg3" and not args.no_side_configs and args.flags == 0 and not args.block and not args.no_frames
                 and not args.no_mix and (V, T) == (default_voices("cfg3"), 48000)):
             # the same workload driven the way the reference's audio callback drives `execute` — one call per buffer_size samples
             # (main.rs:59-63) — instead of one call per second of audio: what a host that ticks pays (tick sessions)
@@ -690,7 +737,7 @@ def run_rank(args, backend_cls=HipBackend):
                     rf[w + "_frac_valu_f64"] = c["frac_valu_f64"]
                     rf[w + "_f64_ops_per_voice_sample"] = c["f64_ops_per_voice_sample"]
                     rf[w + "_frac_of_measured_f64_rate"] = c["frac_of_measured_f64_rate"]
-        if world == 1 and not args.no_cpu and args.workload not in ("p3", "p4") and be.name == "hip":
+        if args.full and world == 1 and not args.no_cpu and args.workload not in ("p3", "p4") and be.name == "hip":
             out["cpu_baseline"] = cpu_baseline(be.S, args.workload)
     be.close()
     cp.close()
@@ -708,8 +755,12 @@ def parse_args(argv=None):
     ap.add_argument("--flags", type=int, default=0, help="SRACK_RENDER_* flags (1 exact osc, 2 no fusion, 4 no uniform hoist, 8 no control stages)")
     ap.add_argument("--no-frames", action="store_true", help="mix only (diagnostic; not the metric)")
     ap.add_argument("--no-mix", action="store_true", help="frames only (diagnostic; not the metric)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-side-configs", action="store_true", help="skip configs 2 and 4 after the headline steps of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the side configurations and the ticked run (cfg3, 1 GPU, default sizes) and cpu_baseline (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the mix, a seeded sample of voices' frames) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg of --full")
+    ap.add_argument("--no-side-configs", action="store_true", help="skip configs 2 and 4 after the headline steps of --full")
     ap.add_argument("--block", type=int, default=0,
                     help="diagnostic: render each step in calls of this many samples (the app's tick loop: one call per buffer_size), not in one call")
     ap.add_argument("--force-dist", action="store_true",

@@ -25,7 +25,7 @@ rm -f profiles/${TAG}_bench.json
 python profiles/summarize.py $TAG --no-assert > $OUT/summary.log 2>&1
 # the un-profiled bench line of the same configuration on the same box (cpu_baseline only when asked for: third argument " ") — AFTER the
 # summary exists: bench.py looks the per-launch HBM traffic up in it (roofline.traffic, measured_in_this_run: false)
-python bench.py --steps 20 --warmup 5 --no-side-configs ${3:---no-cpu} ${2:-} > profiles/${TAG}_bench.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 5 --no-side-configs ${3:---no-cpu} ${2:-} > profiles/${TAG}_bench.json 2> $OUT/bench.err
 # ... and once more, now with the un-profiled line beside the traced one (the profiler's inflation of the step) and the checks enforced
 python profiles/summarize.py $TAG > $OUT/summary.log 2>&1
 echo "summarize rc=$?"

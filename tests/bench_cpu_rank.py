@@ -54,6 +54,9 @@ class OracleBackend:
     def kernel_ms(self):
         return 0.0, 0
 
+    def outputs(self):
+        return {"mix": self.mix}
+
     def info(self):
         return "oracle"
 

@@ -198,6 +198,24 @@ def test_bench_under_torch_distributed_run(tmp_path):
     assert sorted(os.listdir(tmp_path)) == ["steps.0", "steps.1"] and open(str(tmp_path / "steps") + ".1").read() == "3"
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR`: after the timed steps rank 0 leaves what the last step computed as DIR/<name>.npy (f32 / f64), and the same
+    arguments give the same arrays from run to run."""
+    got = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        d.mkdir()
+        out = _run_bench_cpu(d, 2, extra=("--dump-outputs", str(d / "out")))
+        assert out["steps"] == 2 and open(str(d / "steps") + ".0").read() == "3"
+        assert sorted(os.listdir(d / "out")) == ["mix.npy"]
+        mix = np.load(d / "out" / "mix.npy")
+        assert mix.dtype == np.float32 and mix.shape == (2, 1200)
+        np.testing.assert_array_equal(mix, np.load(d / "mix.npy"))  # the reduced mix the last step left on rank 0
+        got.append(mix)
+    np.testing.assert_array_equal(got[0], got[1])
+    assert np.abs(got[0]).max() > 0.5
+
+
 def test_bench_single_rank_needs_no_rendezvous(tmp_path):
     out = _run_bench_cpu(tmp_path, 1)
     assert out["n_gpus"] == 1 and out["ranks_seen"] == 1

@@ -1,11 +1,12 @@
 #!/bin/bash
-# the default bench line exactly as the driver runs it (python bench.py), with its wall time and a digest
-mkdir -p gpurun_out/r4
-( time python bench.py ) > gpurun_out/r4/default_line.json 2> gpurun_out/r4/default_line.err
-grep -E "^real" gpurun_out/r4/default_line.err
+# the full bench line (python bench.py --full), with its wall time and a digest: bash tools/default_line.sh [output directory]
+OUT=${1:-${TMPDIR:-/tmp}/default_line}
+mkdir -p $OUT
+( time python bench.py --full ) > $OUT/default_line.json 2> $OUT/default_line.err
+grep -E "^real" $OUT/default_line.err
 python - <<'PY'
 import json
-d = json.loads(open("gpurun_out/r4/default_line.json").read().strip().splitlines()[-1])
+d = json.load(open("bench_detail.json"))  # everything the run measured; the line itself is shaped to fit 6 KB
 r = d["roofline"]
 print("ms/step", round(d["ms_per_step"], 3), "frac", round(r["frac"], 4), "frac_kernel", round(r["frac_kernel"], 4))
 for k in sorted(r):

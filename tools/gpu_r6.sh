@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6's GPU passes, one parameterised script (run ON THE GPU BOX from the repo root):
 #   tests [pytest args]          the -m gpu suite with its wall time
-#   line                         the default bench line exactly as the driver runs it (python bench.py --steps 20 --warmup 5), its size and digest
+#   line                         the full bench line (python bench.py --full --steps 20 --warmup 5), its size and digest
 #   bench <name> <bench args>    one bench line (5 steps, no CPU leg, no side configs)
 #   ab "<bench args>" A.so B.so  alternate prebuilt libraries on this box, three rounds
 #   prof <tag> "<bench args>"    rocprofv3 evidence for one workload (profiles/run_profile.sh)
@@ -30,7 +30,7 @@ PY
 while [ $# -gt 0 ]; do
   case $1 in
     tests) shift; ( time timeout 1500 python -m pytest tests -m gpu -q -x ${1:-} ) > $OUT/pytest.log 2>&1; grep -E "passed|failed|error|^real" $OUT/pytest.log | tail -4; shift ;;
-    line) shift; ( time python bench.py --steps 20 --warmup 5 ) > $OUT/default_line.json 2> $OUT/default_line.err; grep -E "^real" $OUT/default_line.err; digest $OUT/default_line.json; cp bench_detail.json $OUT/default_detail.json 2>/dev/null ;;
+    line) shift; ( time python bench.py --full --steps 20 --warmup 5 ) > $OUT/default_line.json 2> $OUT/default_line.err; grep -E "^real" $OUT/default_line.err; digest $OUT/default_line.json; cp bench_detail.json $OUT/default_detail.json 2>/dev/null ;;
     bench) name=$2; args=$3; shift 3; timeout 600 python bench.py --steps 5 --warmup 2 --no-cpu --no-side-configs $args > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc=$?"; digest $OUT/$name.json ;;
     ab) args=$2; shift 2; libs=""
         while [ $# -gt 0 ] && [[ "$1" == *.so ]]; do libs="$libs $1"; shift; done

@@ -12,6 +12,14 @@
 
 #include "interp.hip.h"
 
+// render_voice_chain_track's priority ramp: a voice wave drops to priority 1 at SRK_PRIO_AT1 / 64 of its launch, to 0 at SRK_PRIO_AT0 / 64
+#ifndef SRK_PRIO_AT1
+#define SRK_PRIO_AT1 32
+#endif
+#ifndef SRK_PRIO_AT0
+#define SRK_PRIO_AT0 56
+#endif
+
 #ifndef SRK_FM_UNROLL
 #define SRK_FM_UNROLL 8
 #endif
@@ -278,6 +286,34 @@ __global__ __launch_bounds__(64) void render_voice_chain(KernelArgs a, ChainRole
     }
 }
 
+#ifdef SRK_WAVE_CENSUS
+// Tools-only build (tools/wave_census.py): lane 0 of every wave of render_voice_chain_track records when it started and ended on the
+// 100 MHz constant clock (comparable across XCDs) and where it ran.  Eight words per wave slot: [0..1] start, [2..3] end, [4] HW_ID,
+// [5] XCC_ID, [6] 1 = recorded | 2 = the control block, [7] the wave's index.  Plain global stores; null: this launch is not recorded.
+__device__ uint32_t* srk_census_rec;
+SRK_DEV uint32_t* census_begin(uint32_t slot, uint32_t wave, bool ctl, int lane)
+{
+    uint32_t* rec = srk_census_rec;
+    if (!rec || lane != 0) return nullptr;
+    rec += (size_t)slot * 8;
+    const uint64_t t = __builtin_amdgcn_s_memrealtime();
+    rec[0] = (uint32_t)t;
+    rec[1] = (uint32_t)(t >> 32);
+    rec[4] = (uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_REG_HW_ID: wave / SIMD / CU / SH / SE
+    rec[5] = (uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 20);  // HW_REG_XCC_ID
+    rec[6] = ctl ? 3u : 1u;
+    rec[7] = wave;
+    return rec;
+}
+SRK_DEV void census_end(uint32_t* rec)
+{
+    if (!rec) return;
+    const uint64_t t = __builtin_amdgcn_s_memrealtime();
+    rec[2] = (uint32_t)t;
+    rec[3] = (uint32_t)(t >> 32);
+}
+#endif
+
 // ---- fused voice chain, envelope from a control track (P1 after uniform hoisting) ---------------------
 // OSC_A.<port> -> VCF.<port> -> VCA <- track[t]; the track sample is wave-uniform (scalar load, SGPR operand).
 // The loop body is one basic block: the filter chain of sample t interleaves with the oscillator of t+1.
@@ -292,10 +328,19 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
         // a latency chain sharing its SIMD with four throughput-bound voice waves: without priority it gets a
         // fifth of the issue slots and can outlast the voice blocks (measured: 1.9 -> 2.6 ms per launch)
         __builtin_amdgcn_s_setprio(3);
+#ifdef SRK_WAVE_CENSUS
+        uint32_t* crec = census_begin(a.n_waves, 0xffffffffu, true, threadIdx.x);
+#endif
         ctl_gate_env<kExact>(co);
+#ifdef SRK_WAVE_CENSUS
+        census_end(crec);
+#endif
         return;
     }
     const int lane = threadIdx.x;
+#ifdef SRK_WAVE_CENSUS
+    uint32_t* crec = census_begin(blockIdx.x - a.block0, blockIdx.x - a.block0, false, lane);
+#endif
     const WaveMap wm = wave_map(a, lane);
     const uint32_t voice = wm.voice, vc = wm.vc, V = a.V;
     const bool active = wm.active;
@@ -363,8 +408,16 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
     XSaw xo;
     const bool xs = kExact && kOscAPort == OSC_OUT_SAW && xsaw_usable(sa.pos, ka.delta) && vcf_nan_free(sv);
     if (xs) xsaw_init(xo, sa.pos, ka.delta);
+    // Waves in step (notes/r07.md): the four voice waves of a SIMD run the same code for the same samples, yet under age-ordered
+    // arbitration the oldest runs ahead and the youngest finishes up to ~30 % of the launch later, alone on its SIMD for the tail.  A wave's
+    // priority falls 2 -> 1 -> 0 as it passes fixed points of the launch, so the waves behind win the issue slots until they catch up.
+    // (The control block keeps 3.)  Scalar work once per 32-sample tile.
+    const uint32_t prio1_at = (uint32_t)(((uint64_t)a.T * SRK_PRIO_AT1) >> 6), prio0_at = (uint32_t)(((uint64_t)a.T * SRK_PRIO_AT0) >> 6);
+    __builtin_amdgcn_s_setprio(2);
     for (uint32_t t0 = 0; t0 < a.T; t0 += kMixRows) {
         const int n = (int)min((uint32_t)kMixRows, a.T - t0);
+        if (t0 >= prio1_at && t0 < prio1_at + kMixRows) __builtin_amdgcn_s_setprio(1);
+        if (t0 >= prio0_at && t0 < prio0_at + kMixRows) __builtin_amdgcn_s_setprio(0);
         if (xs) {
             xsaw_tile(xo, mix_tile + lane, kMixPitch, n);
             auto sample_x = [&](int i, float xin) {
@@ -447,6 +500,9 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
         put(s0 + VCF_S_FREQ, __float_as_uint(sv.freq));
         put(s0 + VCF_S_RES, __float_as_uint(sv.res));
     }
+#ifdef SRK_WAVE_CENSUS
+    census_end(crec);
+#endif
 }
 
 // ---- fused sequencer-driven voice chain (patch P3's shape after hoisting) ------------------------------------------

@@ -760,6 +760,63 @@ static void launch_ctl(const FlatProgram& Cp, const KernelArgs& kc, hipStream_t 
     }
 }
 
+#ifdef SRK_WAVE_CENSUS
+// Tools-only build (make EXTRA=-DSRK_WAVE_CENSUS ...; tools/wave_census.py): while armed, every launch of render_voice_chain_track records
+// its waves (fused.hip.h) into the next n_waves + 1 slots of one device buffer (slot n_waves: the control block).  Not in the library's ABI.
+static struct {
+    uint32_t* d_rec = nullptr;
+    uint32_t cap = 0, used = 0;
+    std::vector<uint32_t> slots;      // wave slots of each recorded launch
+    std::vector<uint32_t*> where;     // the pointer each launch was given (host copies stay alive until the next srack_census_begin)
+} g_census;
+
+static int census_arm(uint32_t n_slots, hipStream_t st)
+{
+    uint32_t* p = nullptr;
+    if (g_census.d_rec && g_census.used + n_slots <= g_census.cap && g_census.where.size() < g_census.where.capacity()) {
+        p = g_census.d_rec + (size_t)g_census.used * 8;
+        g_census.used += n_slots;
+        g_census.slots.push_back(n_slots);
+    }
+    if (g_census.where.size() == g_census.where.capacity()) return SRACK_OK;  // not armed (or out of launch slots): the symbol stays null
+    g_census.where.push_back(p);
+    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(srk_census_rec), &g_census.where.back(), sizeof(p), 0, hipMemcpyHostToDevice, st));
+    return SRACK_OK;
+}
+
+extern "C" int srack_census_begin(uint32_t max_slots, uint32_t max_launches)
+{
+    HIP_TRY(hipDeviceSynchronize());
+    (void)hipFree(g_census.d_rec);
+    g_census = {};
+    HIP_TRY(hipMalloc(&g_census.d_rec, sizeof(uint32_t) * 8 * (size_t)max_slots));
+    HIP_TRY(hipMemset(g_census.d_rec, 0, sizeof(uint32_t) * 8 * (size_t)max_slots));
+    g_census.cap = max_slots;
+    g_census.where.reserve(max_launches);
+    HIP_TRY(hipDeviceSynchronize());
+    return SRACK_OK;
+}
+
+// Copies the records out (8 words per slot, launch after launch) and the slots of each launch; disarms.  Returns the number of launches.
+extern "C" int srack_census_read(uint32_t* out, uint32_t max_slots, uint32_t* slots_per_launch, uint32_t max_launches)
+{
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t* null_rec = nullptr;
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(srk_census_rec), &null_rec, sizeof(null_rec), 0, hipMemcpyHostToDevice));
+    const uint32_t n = std::min<uint32_t>((uint32_t)g_census.slots.size(), max_launches);
+    uint32_t words = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (words / 8 + g_census.slots[i] > max_slots) return (int)i;
+        slots_per_launch[i] = g_census.slots[i];
+        words += 8 * g_census.slots[i];
+    }
+    if (words) HIP_TRY(hipMemcpy(out, g_census.d_rec, sizeof(uint32_t) * words, hipMemcpyDeviceToHost));
+    g_census.where.clear();
+    g_census.where.shrink_to_fit();  // capacity 0: nothing more is recorded until srack_census_begin
+    return (int)n;
+}
+#endif
+
 // How a render is scheduled.  Without a control program: one launch of the voice kernel.  With one: the
 // render is cut into chunks; control chunk k (one wave, a latency chain) runs on its own stream and voice
 // chunk k waits only for it, so all but the first control chunk hide behind voice kernels of earlier chunks.
@@ -1277,6 +1334,9 @@ struct Segment {
                 if ((rc = jit_launch(*special, ka, n_waves + ka.block0, st)) != SRACK_OK) return rc;
             } else if (fused) {
                 const int out_mode = (ka.frames ? 1 : 0) | (ka.mixpart ? 2 : 0);
+#ifdef SRK_WAVE_CENSUS
+                if (track && (rc = census_arm(n_waves + 1, st)) != SRACK_OK) return rc;
+#endif
                 launch_fused(osc_port, vcf_port, (flags & SRACK_RENDER_EXACT_OSC) != 0, out_mode, track, ka, roles, co, dim3(n_waves + ka.block0), st);
             } else if (seq_chain) {
                 const int out_mode = (ka.frames ? 1 : 0) | (ka.mixpart ? 2 : 0);

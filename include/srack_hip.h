@@ -333,6 +333,25 @@ int srack_render_planes(srack_patch* p, int* channel_plane, int cap);
 int srack_render(srack_patch* p, uint32_t n_samples, float* d_frames, float* d_mix,
                  uint32_t flags, void* stream);
 
+/* srack_render plus per-voice statistics of the output, folded into d_stats (device, f64 [planes][SRACK_STAT_COUNT][n_voices], 8-byte
+ * aligned) — for a host that wants one number per voice without writing and re-reading the frames.  For every sample x of plane p and
+ * voice v (the f32 value the call writes, or would write, to d_frames): NaN / +-inf adds 1 to NONFINITE and nothing else; otherwise
+ * SUM += (double)x, SUM_SQ += (double)x * x, PEAK_POS = max(PEAK_POS, x), PEAK_NEG = max(PEAK_NEG, -x), and |x| > 1 adds 1 to CLIPPED (a peak moves
+ * only to a value strictly above it: from the zero fill, a peak of nothing is +0.0).
+ * The call adds to what the buffer holds: zero-fill it once and the statistics cover every call since (tick sessions, segments, edits,
+ * srack_patch_keep_state).  The sums are taken in sample order: bit for bit the sequential f64 loop, however the render is cut.
+ * d_frames and d_mix may be NULL independently of d_stats (statistics only: no frames are written); d_stats NULL is srack_render.
+ * Every voice kernel: the fused voice chains accumulate them in registers (no frames written when none are asked for); any other kernel's
+ * frames — the host's, or one launch's worth of library scratch — are folded after each launch, in sample order as well.  Asking for
+ * statistics changes neither the kernel, the chunks nor any bit of frames, mix or voice state.  A patch with no plane returns SRACK_OK
+ * and leaves d_stats untouched. */
+enum {
+    SRACK_STAT_SUM = 0, SRACK_STAT_SUM_SQ = 1, SRACK_STAT_PEAK_POS = 2, SRACK_STAT_PEAK_NEG = 3,
+    SRACK_STAT_NONFINITE = 4, SRACK_STAT_CLIPPED = 5, SRACK_STAT_COUNT = 6
+};
+int srack_render_stats(srack_patch* p, uint32_t n_samples, float* d_frames, float* d_mix,
+                       double* d_stats, uint32_t flags, void* stream);
+
 /* Optional: do everything a later srack_render(p, <= n_samples, ..., flags) would do on first use — flatten the graph,
  * upload the programs and the voice table, size the scratch buffers (mix partials when want_mix, control tracks) — so
  * that the first render costs what every render costs.  Renders nothing and leaves the voice state untouched. */
@@ -390,6 +409,8 @@ int srack_device_free(void* d_ptr);
 /* Waits for `stream`, then copies through pinned buffers of the library's own (the caller's memory may be pageable; per device, double-buffered,
  * large copies on several helper threads: 51 GB/s for 50 GB on the GPU box); returns when h_dst holds the bytes. */
 int srack_device_to_host(void* h_dst, const void* d_src, size_t bytes, void* stream);
+/* The other way (e.g. a statistics buffer to start from): enqueued on `stream`, returns once h_src may be reused. */
+int srack_device_from_host(void* d_dst, const void* h_src, size_t bytes, void* stream);
 int srack_device_sync(void* stream);
 
 /* ---- multi-GPU mix-down --------------------------------------------------------------------- */

@@ -55,9 +55,11 @@ mod ffi {
         pub fn srack_voices_set_field_f32(p: *mut SrackPatch, module: c_int, field: c_int, values: *const f32) -> c_int;
         pub fn srack_render_planes(p: *mut SrackPatch, channel_plane: *mut c_int, cap: c_int) -> c_int;
         pub fn srack_render(p: *mut SrackPatch, n_samples: u32, d_frames: *mut f32, d_mix: *mut f32, flags: u32, stream: *mut c_void) -> c_int;
+        pub fn srack_render_stats(p: *mut SrackPatch, n_samples: u32, d_frames: *mut f32, d_mix: *mut f32, d_stats: *mut f64, flags: u32, stream: *mut c_void) -> c_int;
         pub fn srack_device_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
         pub fn srack_device_free(d_ptr: *mut c_void) -> c_int;
         pub fn srack_device_to_host(h_dst: *mut c_void, d_src: *const c_void, bytes: usize, stream: *mut c_void) -> c_int;
+        pub fn srack_device_from_host(d_dst: *mut c_void, h_src: *const c_void, bytes: usize, stream: *mut c_void) -> c_int;
         pub fn srack_device_set(device: c_int) -> c_int;
         pub fn srack_device_get(device: *mut c_int, pci_bus_id: *mut c_char, cap: usize) -> c_int;
         pub fn srack_kernel_cache_set_dir(dir: *const c_char) -> c_int;
@@ -69,6 +71,17 @@ mod ffi {
         pub fn srack_dist_reduce_mix(comm: *mut c_void, d_mix: *mut f32, count: usize, root: c_int, stream: *mut c_void) -> c_int;
         pub fn srack_dist_destroy(comm: *mut c_void) -> c_int;
     }
+}
+
+/// Fields of a statistics buffer (values of `SRACK_STAT_*`): `[planes][STAT_COUNT][n_voices]` f64.
+pub mod stat {
+    pub const SUM: usize = 0;
+    pub const SUM_SQ: usize = 1;
+    pub const PEAK_POS: usize = 2;
+    pub const PEAK_NEG: usize = 3;
+    pub const NONFINITE: usize = 4;
+    pub const CLIPPED: usize = 5;
+    pub const COUNT: usize = 6;
 }
 
 /// Render flags (values of `SRACK_RENDER_*`).
@@ -139,6 +152,17 @@ impl DeviceBuffer {
     pub fn to_host(&self, dst: &mut [f32]) -> Result<(), Error> {
         assert!(dst.len() * 4 <= self.bytes);
         check(unsafe { ffi::srack_device_to_host(dst.as_mut_ptr() as *mut c_void, self.ptr, dst.len() * 4, std::ptr::null_mut()) }).map(|_| ())
+    }
+    pub fn as_f64(&self) -> *mut f64 {
+        self.ptr as *mut f64
+    }
+    pub fn to_host_f64(&self, dst: &mut [f64]) -> Result<(), Error> {
+        assert!(dst.len() * 8 <= self.bytes);
+        check(unsafe { ffi::srack_device_to_host(dst.as_mut_ptr() as *mut c_void, self.ptr, dst.len() * 8, std::ptr::null_mut()) }).map(|_| ())
+    }
+    pub fn from_host_f64(&mut self, src: &[f64]) -> Result<(), Error> {
+        assert!(src.len() * 8 <= self.bytes);
+        check(unsafe { ffi::srack_device_from_host(self.ptr, src.as_ptr() as *const c_void, src.len() * 8, std::ptr::null_mut()) }).map(|_| ())
     }
 }
 
@@ -237,6 +261,13 @@ impl Patch {
         let f = frames.map_or(std::ptr::null_mut(), |b| b.as_f32());
         let m = mix.map_or(std::ptr::null_mut(), |b| b.as_f32());
         check(unsafe { ffi::srack_render(self.raw, n_samples, f, m, flags, std::ptr::null_mut()) }).map(|_| ())
+    }
+    /// `execute_batch` plus per-voice statistics folded into `stats`: `[planes][STAT_COUNT][n_voices]` f64, zero-filled once by the
+    /// host (`from_host_f64`) and added to by every call (`srack_render_stats`).
+    pub fn execute_batch_stats(&mut self, n_samples: u32, frames: Option<&DeviceBuffer>, mix: Option<&DeviceBuffer>, stats: &DeviceBuffer, flags: u32) -> Result<(), Error> {
+        let f = frames.map_or(std::ptr::null_mut(), |b| b.as_f32());
+        let m = mix.map_or(std::ptr::null_mut(), |b| b.as_f32());
+        check(unsafe { ffi::srack_render_stats(self.raw, n_samples, f, m, stats.as_f64(), flags, std::ptr::null_mut()) }).map(|_| ())
     }
 }
 

@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsrack_hip.so")
 
 OK, ERR_INVALID, ERR_PORT, ERR_NO_OUTPUT, ERR_SELF_LOOP, ERR_STATE, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8
+STAT_SUM, STAT_SUM_SQ, STAT_PEAK_POS, STAT_PEAK_NEG, STAT_NONFINITE, STAT_CLIPPED, STAT_COUNT = 0, 1, 2, 3, 4, 5, 6
 RENDER_DEFAULT, RENDER_EXACT_OSC, RENDER_NO_FUSION, RENDER_NO_UNIFORM_HOIST, RENDER_NO_CTL_STAGES, RENDER_NO_SPECIALIZE, RENDER_SPECIALIZE, RENDER_KEEP_DEFAULT = 0, 1, 2, 4, 8, 16, 32, 64
 
 # every symbol include/srack_hip.h declares (tests check the library exports exactly these)
@@ -26,9 +27,9 @@ ABI_SYMBOLS = [
     "srack_patch_set_field", "srack_patch_get_field", "srack_patch_keep_state", "srack_patch_set_step", "srack_patch_get_step", "srack_patch_set_wave", "srack_patch_get_wave", "srack_patch_load_srk", "srack_patch_save_srk", "srack_patch_module_id",
     "srack_patch_set_module_position", "srack_patch_get_module_position", "srack_patch_set_output_buffer", "srack_patch_get_output_buffer", "srack_patch_set_noise_seed", "srack_patch_connect", "srack_patch_disconnect", "srack_patch_get_input",
     "srack_patch_plan", "srack_patch_plan_list", "srack_patch_removed_edges", "srack_patch_delayed_edges",
-    "srack_voices_configure", "srack_voices_set_field_f32", "srack_voices_set_field_f64", "srack_render_planes", "srack_render", "srack_render_reserve",
+    "srack_voices_configure", "srack_voices_set_field_f32", "srack_voices_set_field_f64", "srack_render_planes", "srack_render", "srack_render_stats", "srack_render_reserve",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
-    "srack_device_alloc", "srack_device_free", "srack_device_to_host", "srack_device_sync",
+    "srack_device_alloc", "srack_device_free", "srack_device_to_host", "srack_device_from_host", "srack_device_sync",
     "srack_dist_unique_id", "srack_dist_init", "srack_dist_comm_count", "srack_dist_destroy", "srack_dist_reduce_mix",
 ]
 
@@ -90,6 +91,7 @@ def _load():
     L.srack_voices_set_field_f64.argtypes = [vp, i32, i32, dp]
     L.srack_render_planes.argtypes = [vp, ip, i32]
     L.srack_render.argtypes = [vp, u32, vp, vp, u32, vp]
+    L.srack_render_stats.argtypes = [vp, u32, vp, vp, vp, u32, vp]
     L.srack_render_reserve.argtypes = [vp, u32, i32, u32]
     L.srack_render_info.argtypes = [vp, C.c_char_p, sz]
     L.srack_render_kernel_ms.argtypes = [vp, dp, ip, i32]
@@ -104,6 +106,7 @@ def _load():
     L.srack_device_alloc.argtypes = [C.POINTER(vp), sz]
     L.srack_device_free.argtypes = [vp]
     L.srack_device_to_host.argtypes = [vp, vp, sz, vp]
+    L.srack_device_from_host.argtypes = [vp, vp, sz, vp]
     L.srack_device_sync.argtypes = [vp]
     L.srack_dist_unique_id.argtypes = [C.c_char_p]
     L.srack_dist_init.argtypes = [C.c_char_p, i32, i32, C.POINTER(vp)]
@@ -360,9 +363,13 @@ class Patch:
         """First-use set-up (flatten, upload, scratch buffers) ahead of the first render."""
         _check(lib.srack_render_reserve(self.h, n_samples, 1 if want_mix else 0, flags))
 
-    def render_raw(self, n_samples, d_frames=None, d_mix=None, flags=0, stream=None):
-        """Device pointers (ints) in; asynchronous on `stream`."""
-        _check(lib.srack_render(self.h, n_samples, d_frames, d_mix, flags, stream))
+    def render_raw(self, n_samples, d_frames=None, d_mix=None, flags=0, stream=None, d_stats=None):
+        """Device pointers (ints) in; asynchronous on `stream`.  d_stats: per-voice statistics, f64 [planes][STAT_COUNT][V],
+        folded into what the buffer holds (srack_render_stats)."""
+        if d_stats is None:
+            _check(lib.srack_render(self.h, n_samples, d_frames, d_mix, flags, stream))
+        else:
+            _check(lib.srack_render_stats(self.h, n_samples, d_frames, d_mix, d_stats, flags, stream))
 
     def info(self):
         n = _check(lib.srack_render_info(self.h, None, 0))   # (the length: a description names every control unit and may pass any fixed size)
@@ -415,6 +422,41 @@ class Patch:
                 lib.srack_device_free(d_fr)
             if d_mx.value:
                 lib.srack_device_free(d_mx)
+
+    def render_stats(self, n_samples, frames=False, mix=False, flags=0, stats=None):
+        """render() plus per-voice statistics of every plane -> (frames or None, mix or None, stats f64 [planes][STAT_COUNT][V]).
+        `stats`: an earlier call's result to continue from (None: zeros).  Fields: STAT_SUM, STAT_SUM_SQ, STAT_PEAK_POS, STAT_PEAK_NEG,
+        STAT_NONFINITE, STAT_CLIPPED (include/srack_hip.h)."""
+        if self.n_voices == 0:
+            self.configure_voices(1)
+        n_planes, _ = self.planes()
+        V, T, Cn = self.n_voices, n_samples, self.channels
+        st = np.zeros((n_planes, STAT_COUNT, V)) if stats is None else np.array(stats, dtype=np.float64, order="C", copy=True)
+        assert st.shape == (n_planes, STAT_COUNT, V), st.shape
+        d_fr, d_mx, d_st = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        try:
+            if frames and n_planes > 0:
+                _check(lib.srack_device_alloc(C.byref(d_fr), max(1, n_planes * T * V * 4)))
+            if mix:
+                _check(lib.srack_device_alloc(C.byref(d_mx), max(1, Cn * T * 4)))
+            _check(lib.srack_device_alloc(C.byref(d_st), max(8, st.nbytes)))
+            _check(lib.srack_device_from_host(d_st, st.ctypes.data_as(C.c_void_p), st.nbytes, None))
+            self.render_raw(T, d_fr if d_fr.value else None, d_mx if d_mx.value else None, flags, None, d_st)
+            fr = mx = None
+            if frames:
+                fr = np.zeros((n_planes, T, V), dtype=np.float32)
+                if d_fr.value:
+                    _check(lib.srack_device_to_host(fr.ctypes.data_as(C.c_void_p), d_fr, fr.nbytes, None))
+            if mix:
+                mx = np.empty((Cn, T), dtype=np.float32)
+                _check(lib.srack_device_to_host(mx.ctypes.data_as(C.c_void_p), d_mx, mx.nbytes, None))
+            _check(lib.srack_device_to_host(st.ctypes.data_as(C.c_void_p), d_st, st.nbytes, None))
+            _check(lib.srack_device_sync(None))
+            return fr, mx, st
+        finally:
+            for d in (d_fr, d_mx, d_st):
+                if d.value:
+                    lib.srack_device_free(d)
 
     def render_channels(self, n_samples, flags=0):
         """-> [channels][T][V] f32 (planes expanded to channels, silence for unconnected ones)."""

@@ -548,7 +548,23 @@ int srack_render(srack_patch* p, uint32_t n_samples, float* d_frames, float* d_m
             set_error("render: call srack_voices_configure first");
             return SRACK_ERR_STATE;
         }
-        return device_render(p->h, n_samples, d_frames, d_mix, flags, stream);
+        return device_render(p->h, n_samples, d_frames, d_mix, nullptr, flags, stream);
+    });
+}
+
+int srack_render_stats(srack_patch* p, uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, uint32_t flags, void* stream)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        if (((uintptr_t)d_stats & 7u) != 0) {  // (before anything touches the device)
+            set_error("render_stats: d_stats must be 8-byte aligned");
+            return SRACK_ERR_INVALID;
+        }
+        if (p->h.n_voices == 0) {
+            set_error("render_stats: call srack_voices_configure first");
+            return SRACK_ERR_STATE;
+        }
+        return device_render(p->h, n_samples, d_frames, d_mix, d_stats, flags, stream);
     });
 }
 
@@ -903,6 +919,17 @@ int bounce_copy(int device, char* dst, const char* src, size_t bytes)
     return rc;
 }
 }  // namespace
+int srack_device_from_host(void* d_dst, const void* h_src, size_t bytes, void* stream)
+{
+    return guarded([&]() -> int {
+        if (bytes == 0) return SRACK_OK;
+        if (!d_dst || !h_src) return SRACK_ERR_INVALID;
+        HIP_TRY_C(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+        HIP_TRY_C(hipStreamSynchronize((hipStream_t)stream));  // the host's memory may be pageable and reused as soon as this returns
+        return SRACK_OK;
+    });
+}
+
 int srack_device_to_host(void* h_dst, const void* d_src, size_t bytes, void* stream)
 {
     return guarded([&]() -> int {

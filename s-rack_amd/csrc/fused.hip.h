@@ -184,7 +184,7 @@ __global__ __launch_bounds__(64) void render_voice_chain(KernelArgs a, ChainRole
     const AdsrConst kd = adsr_consts(parv(od, ADSR_P_A), parv(od, ADSR_P_D), parv(od, ADSR_P_S), parv(od, ADSR_P_R), parv(od, ADSR_P_SR));
     const bool negative = parv(oc, VCA_P_NEG) != 0.0f;
 
-    Emit em = make_emit(a, plane, lane);
+    EmitOf<kOut> em = make_emit_of<kOut>(a, plane, lane);
 
     COsc ca, cl;
     FOsc fa_osc;
@@ -258,6 +258,7 @@ __global__ __launch_bounds__(64) void render_voice_chain(KernelArgs a, ChainRole
         sa.sync_last = sl.sync_last = false;  // sync unconnected: `last` follows the constant 0.0 input
         adsr_seg_flush(sd, seg);
     }
+    emit_stats_end(em);
 
     if (active) {
         auto put = [&](int rr, uint32_t v) { a.table[(size_t)rr * V + voice] = v; };
@@ -379,7 +380,7 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
     bool sv_fin = !kExact || vcf_nan_free(sv);  // (exact mode: v_med3 clamps while nothing can turn into a NaN, modules.hip.h vcf_run)
     const bool negative = parv(oc, VCA_P_NEG) != 0.0f;
 
-    Emit em = make_emit(a, plane, lane);
+    EmitOf<kOut> em = make_emit_of<kOut>(a, plane, lane);
 
     // default mode, saw: the phase lives in 64-bit fixed point (modules.hip.h, FOsc); the host stores state and increment so
     constexpr bool kFixed = !kExact && kOscAPort == OSC_OUT_SAW;
@@ -484,6 +485,7 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
         sa.pos = xo.pos;
         sa.sync_last = false;  // sync unconnected: `last` follows the constant 0.0 input
     }
+    emit_stats_end(em);
     if (active) {
         auto put = [&](int rr, uint32_t v) { a.table[(size_t)rr * V + voice] = v; };
         put(oa.state_row + OSC_S_POS_LO, kFixed ? fpos_lo : f64_lo(sa.pos));
@@ -2188,6 +2190,22 @@ __global__ __launch_bounds__(256) void mix_reduce_final(MixArgs m)
             for (uint32_t y = 0; y < kMixSplit; y++) s += m.mixgroup[((size_t)plane * kMixSplit + y) * m.T + i];
         m.mix[(size_t)c * m.mix_stride + i] = s;
     }
+}
+
+// Per-voice statistics of a launch's frames, for the kernels that do not carry the accumulators themselves (everything but
+// render_voice_chain / render_voice_chain_track): one thread per (voice, plane) walks the launch's T rows in sample order — the
+// sequential loop, so its sums are bit for bit what the in-kernel accumulators give, time-parallel kernels included.  A wave reads 256
+// contiguous bytes of a row per sample.  frames: the launch's first row; plane_stride as in KernelArgs.
+__global__ __launch_bounds__(256) void stats_fold(const float* __restrict__ frames, uint64_t plane_stride, uint32_t V, uint32_t T, double* stats)
+{
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x, plane = blockIdx.y;
+    if (v >= V) return;
+    double* s = stats + (size_t)plane * kStatCount * V + v;
+    const float* f = frames + (size_t)plane * plane_stride + v;
+    VoiceStats st;
+    stats_load(st, s, V);
+    for (uint32_t t = 0; t < T; t++) stats_add(st, f[(size_t)t * V]);
+    stats_store(st, s, V);
 }
 
 __global__ void fill_zero(float* p, size_t n)

@@ -29,10 +29,16 @@ struct KernelArgs {
     // Kernels specialised at run time only (jit.cpp): blocks [0, block0) of a launch are the control program's units, block b
     // running unit b on the chunk ctl_slots[b] describes (T == 0: nothing to do in this launch).
     const KernelArgs* ctl_slots;
-    // A control unit inside a tick session (render.hip, TickSession): the state this chunk leaves behind goes to another copy of the
-    // table than the one it was read from, so that a chunk computed ahead of the host's next call never overwrites what the patch
-    // holds as of the last rendered sample.  Null: in place.
-    uint32_t* table_out;
+    union {
+        // A control unit inside a tick session (render.hip, TickSession): the state this chunk leaves behind goes to another copy of the
+        // table than the one it was read from, so that a chunk computed ahead of the host's next call never overwrites what the patch
+        // holds as of the last rendered sample.  Null: in place.
+        uint32_t* table_out;
+        // A voice launch (which has no table_out): per-voice output statistics (srack_render_stats), f64 [planes][SRACK_STAT_COUNT][V],
+        // NOT offset by time — a launch folds its samples into what the buffer holds.  Read only by kernels instantiated with the
+        // statistics output mode (wave.hip.h, kOutStats).  (Sharing the slot keeps the block's layout, and with it every other kernel's code.)
+        double* stats;
+    };
 };
 
 struct ChainRoles {  // op indices of the fused voice chain (osc_l / adsr unused in the track variant)

@@ -167,6 +167,8 @@ struct DeviceState {
     size_t mixgroup_bytes = 0;
     float* d_tracks = nullptr;
     size_t tracks_bytes = 0;
+    float* d_stat_frames = nullptr;  // frames of one launch for stats_fold when the host asked for statistics without frames
+    size_t stat_frames_bytes = 0;
     std::shared_ptr<const JitKernel> jit[5];  // the specialised voice kernel per output mode (1 frames, 2 mix, 3 both, 4 neither), co-owned with the cache
     bool jit_failed = false;  // specialisation was tried by default and is not available: the interpreter renders
     std::string jit_note;     // for srack_render_info: how the kernel was come by (compiled in N ms / disk cache / memory), or why there is none
@@ -189,6 +191,7 @@ void device_release(DeviceState* d)
     (void)hipFree(d->d_mixpart);
     (void)hipFree(d->d_mixgroup);
     (void)hipFree(d->d_tracks);
+    (void)hipFree(d->d_stat_frames);
     if (d->tick.done) (void)hipEventDestroy(d->tick.done);
     for (hipEvent_t e : d->ev_mix) (void)hipEventDestroy(e);
     if (d->ev_mix_done) (void)hipEventDestroy(d->ev_mix_done);
@@ -493,7 +496,11 @@ static void launch_fused4(bool track, const KernelArgs& ka, const ChainRoles& ro
 template <uint32_t A, uint32_t F>
 static void launch_fused3(bool exact, int out_mode, bool track, const KernelArgs& ka, const ChainRoles& roles, const CtlWork& co, dim3 grid, hipStream_t st)
 {
-    if (exact && out_mode == 3 && track)  // frames + mix, the usual request, also gets the compile-time output mode in exact mode
+    if ((out_mode & kOutStats) && exact)  // per-voice statistics (wave.hip.h): one instantiation per flavour, frames and mix decided at run time
+        launch_fused4<A, F, true, kOutStats>(track, ka, roles, co, grid, st);
+    else if (out_mode & kOutStats)
+        launch_fused4<A, F, false, kOutStats>(track, ka, roles, co, grid, st);
+    else if (exact && out_mode == 3 && track)  // frames + mix, the usual request, also gets the compile-time output mode in exact mode
         hipLaunchKernelGGL((render_voice_chain_track<A, F, true, 3>), grid, dim3(64), 0, st, ka, roles, co);
     else if (exact)  // otherwise one instantiation, output mode decided at run time
         launch_fused4<A, F, true, 0>(track, ka, roles, co, grid, st);
@@ -740,6 +747,14 @@ static int resolve_specialized(PatchHandle& h, uint32_t flags, uint32_t n_sample
     return SRACK_OK;
 }
 
+// Per-voice statistics (srack_render_stats): the fused voice chains, render_voice_chain and the flagship render_voice_chain_track,
+// accumulate them in registers as they emit (wave.hip.h, EmitStats: no frames need to exist); every other kernel's frames are folded
+// after each launch (stats_fold).  Neither changes which kernel renders, the chunks, or any bit of frames, mix or state.
+static bool stats_in_kernel(const FlatProgram& P, const JitKernel* special)
+{
+    return !special && (P.fused == FUSED_VOICE_CHAIN || P.fused == FUSED_VOICE_CHAIN_TRACK);
+}
+
 static void launch_ctl(const FlatProgram& Cp, const KernelArgs& kc, hipStream_t st)
 {
     if (Cp.fused == FUSED_CTL_GATE_ENV) {
@@ -839,6 +854,11 @@ struct Segment {
     TickSession& tk;
     const uint32_t V, C, T_total, t_seg, T, flags;
     float *d_frames, *d_mix;
+    double* d_stats;  // per-voice statistics [planes][kStatCount][V] (not offset by time: every launch folds into it), or null
+    // The statistics of a kernel that does not carry them itself: stats_fold over each launch's frames — the host's, or (no frames
+    // asked for) one launch's worth in d_stat_frames, which the kernel then writes instead.  Same kernel, same chunks, same bits.
+    bool fold = false;
+    uint32_t fold_rows = 0;  // rows of d_stat_frames per plane (0: the host's frames)
     const hipStream_t st;
     int rc = SRACK_OK;
     // Voices per wave.  A full wave (64) is right whenever there are enough voices to give every SIMD work.
@@ -864,10 +884,10 @@ struct Segment {
     MixArgs m{};
     bool mix_aside = false;
 
-    Segment(PatchHandle& h_, uint32_t T_total_, uint32_t t_seg_, uint32_t T_, float* d_frames_, float* d_mix_, uint32_t flags_, hipStream_t st_)
+    Segment(PatchHandle& h_, uint32_t T_total_, uint32_t t_seg_, uint32_t T_, float* d_frames_, float* d_mix_, double* d_stats_, uint32_t flags_, hipStream_t st_)
         : h(h_), P(h_.prog.voice), d(h_.dev), tk(h_.dev->tick), V(h_.prog.voice.n_voices), C((uint32_t)h_.prog.voice.hdr.n_channels), T_total(T_total_),
           t_seg(t_seg_), T(T_), flags(flags_), d_frames(d_frames_ ? d_frames_ + (size_t)t_seg_ * h_.prog.voice.n_voices : nullptr),
-          d_mix(d_mix_ ? d_mix_ + t_seg_ : nullptr), st(st_), fm_block(fm_block_shape(h_.prog.voice, flags_, T_)), fm_block_x(fm_block_x_shape(h_.prog.voice, flags_, T_)), fm_x_z1(fm_x_z1_shape(h_.prog.voice, flags_)),
+          d_mix(d_mix_ ? d_mix_ + t_seg_ : nullptr), d_stats(d_stats_), st(st_), fm_block(fm_block_shape(h_.prog.voice, flags_, T_)), fm_block_x(fm_block_x_shape(h_.prog.voice, flags_, T_)), fm_x_z1(fm_x_z1_shape(h_.prog.voice, flags_)),
           lanes((fm_block || fm_block_x) ? (uint32_t)kBlkVoices : lanes_per_wave(h_.prog.voice.n_voices)), n_waves((h_.prog.voice.n_voices + lanes - 1) / lanes)
     {
     }
@@ -1022,6 +1042,7 @@ struct Segment {
             d_frames = nullptr;
             d_mix = nullptr;
         }
+        if (P.hdr.n_planes == 0) d_stats = nullptr;  // (no plane: nothing to fold, the buffer stays as it is)
 
         return SRACK_OK;
     }
@@ -1039,8 +1060,10 @@ struct Segment {
         n_stages = (uint32_t)h.prog.ctl.size();
         co_ctl = has_ctl && P.fused == FUSED_VOICE_CHAIN_TRACK && n_stages == 1 && h.prog.ctl[0].fused == FUSED_CTL_GATE_ENV && h.prog.n_tracks == 1;
         {
-            const int om = (d_frames ? 1 : 0) | (d_mix ? 2 : 0);
+            // (a specialised kernel never carries the statistics: asked for them, it writes frames — the host's or scratch — to fold)
+            const int om = (d_frames || d_stats ? 1 : 0) | (d_mix ? 2 : 0);
             if ((rc = resolve_specialized(h, flags, T, om ? om : 4, &special, &special_ctl)) != SRACK_OK) return rc;
+            fold = d_stats && !stats_in_kernel(P, special);
         }
         // chunk schedule: short first chunks (only control chunk 0 is exposed), doubling up to kChunkMax
         // With a control pipeline of depth L the first voice chunk waits for L + 1 control launches: those stay short.
@@ -1092,6 +1115,10 @@ struct Segment {
         if (d_mix && (rc = grow(d->d_mixpart, d->mixpart_bytes, sizeof(float) * (size_t)P.hdr.n_planes * n_waves * stride)) != SRACK_OK) return rc;
         if (d_mix && (rc = grow(d->d_mixgroup, d->mixgroup_bytes, sizeof(float) * (size_t)P.hdr.n_planes * kMixSplit * stride)) != SRACK_OK) return rc;
         if (has_ctl && (rc = grow(d->d_tracks, d->tracks_bytes, sizeof(float) * (size_t)h.prog.n_tracks * T)) != SRACK_OK) return rc;
+        if (fold && !d_frames) {
+            for (const auto& c : chunks) fold_rows = std::max(fold_rows, c.second);
+            if ((rc = grow(d->d_stat_frames, d->stat_frames_bytes, sizeof(float) * (size_t)P.hdr.n_planes * fold_rows * V)) != SRACK_OK) return rc;
+        }
         // One argument block per (launch, control unit): launch j runs unit s on chunk j - lag[s]; chunk c is complete after launch
         // c + max_lag.  (A control program that was not cut into units is one unit with lag 0.)
         return SRACK_OK;
@@ -1308,6 +1335,11 @@ struct Segment {
             ka.n_waves = n_waves;
             ka.lanes = lanes;
             ka.n0 = h.samples_rendered + t_off;
+            ka.stats = fold ? nullptr : d_stats;  // (in-kernel statistics: the fused voice chains)
+            if (fold_rows) {
+                ka.frames = d->d_stat_frames;
+                ka.plane_stride = (uint64_t)fold_rows * V;
+            }
             CtlWork co{};
             if (tick && co_ctl) {  // block 0: the track of the next chunk — this call's, or the first of the call the session expects next
                 co = tick_work(tk.c + k + 1);
@@ -1333,7 +1365,7 @@ struct Segment {
             if (special) {
                 if ((rc = jit_launch(*special, ka, n_waves + ka.block0, st)) != SRACK_OK) return rc;
             } else if (fused) {
-                const int out_mode = (ka.frames ? 1 : 0) | (ka.mixpart ? 2 : 0);
+                const int out_mode = (ka.frames ? 1 : 0) | (ka.mixpart ? 2 : 0) | (ka.stats ? kOutStats : 0);
 #ifdef SRK_WAVE_CENSUS
                 if (track && (rc = census_arm(n_waves + 1, st)) != SRACK_OK) return rc;
 #endif
@@ -1354,6 +1386,10 @@ struct Segment {
                 launch_interp(P, ka, st);
             }
             HIP_TRY(hipGetLastError());
+            if (fold) {  // behind the launch on its stream; the next launch's writes to d_stat_frames wait for it
+                hipLaunchKernelGGL(stats_fold, dim3((V + 255) / 256, (uint32_t)P.hdr.n_planes), dim3(256), 0, st, ka.frames, ka.plane_stride, V, len, d_stats);
+                HIP_TRY(hipGetLastError());
+            }
             if (mix_aside && k + 1 < n_chunks) {
                 HIP_TRY(hipEventRecord(d->ev_mix[k], st));
                 HIP_TRY(hipStreamWaitEvent(d->mix_stream, d->ev_mix[k], 0));
@@ -1435,7 +1471,7 @@ struct Segment {
     }
 };
 
-static int render_segment(PatchHandle& h, uint32_t T_total, uint32_t t_seg, uint32_t T, float* d_frames, float* d_mix, uint32_t flags, hipStream_t st)
+static int render_segment(PatchHandle& h, uint32_t T_total, uint32_t t_seg, uint32_t T, float* d_frames, float* d_mix, double* d_stats, uint32_t flags, hipStream_t st)
 {
     if (!h.dev) {
         const int rc = upload_program(h);
@@ -1445,13 +1481,13 @@ static int render_segment(PatchHandle& h, uint32_t T_total, uint32_t t_seg, uint
         HIP_TRY(hipStreamWaitEvent(st, h.dev->ev_ready, 0));
         h.dev->ready_pending = false;
     }
-    return Segment(h, T_total, t_seg, T, d_frames, d_mix, flags, st).run();
+    return Segment(h, T_total, t_seg, T, d_frames, d_mix, d_stats, flags, st).run();
 }
 
 // A render is cut into segments of at most kSegment samples so that the scratch it needs (per-wave mix partials
 // [planes][V/64][T], control tracks [n_tracks][T]) stays bounded however long the render is: 16 MB of partials per
 // 1000 samples at 262 144 voices.  Voice and control state carry over between segments exactly as between calls.
-int device_render(PatchHandle& h, uint32_t n_samples, float* d_frames, float* d_mix, uint32_t flags, void* stream)
+int device_render(PatchHandle& h, uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, uint32_t flags, void* stream)
 {
     int rc = ensure_program(h, flags);
     if (rc != SRACK_OK) return rc;
@@ -1464,7 +1500,7 @@ int device_render(PatchHandle& h, uint32_t n_samples, float* d_frames, float* d_
     flags = h.prog.effective_flags | (flags & kLaunchPolicyFlags);
     constexpr uint32_t kSegment = 65536;
     for (uint32_t t = 0; t < n_samples && rc == SRACK_OK; t += kSegment)
-        rc = render_segment(h, n_samples, t, std::min(kSegment, n_samples - t), d_frames, d_mix, flags, (hipStream_t)stream);
+        rc = render_segment(h, n_samples, t, std::min(kSegment, n_samples - t), d_frames, d_mix, d_stats, flags, (hipStream_t)stream);
     return rc;
 }
 

@@ -67,8 +67,57 @@ static_assert(kMixRows == dev::kTileRows, "the tile-wise module forms (modules.h
 constexpr int kMixPitch = 68;  // floats per LDS row of the mix tile: 64 lanes + 4 of padding (see emit_flush)
 constexpr int kMixTile = kMixRows * kMixPitch;
 
+// ---- per-voice output statistics (srack_render_stats) -------------------------------------------------------
+// Fields of d_stats, f64 [planes][kStatCount][V] (include/srack_hip.h, SRACK_STAT_*).  A lane is one voice for the whole launch, so
+// the statistics are registers of that lane: the sums continue from the buffer in sample order (bit for bit the sequential f64
+// loop, whatever the chunking), peaks and counts merge at the end.  A non-finite sample only counts: it enters the sums and peaks
+// as -0.0, which leaves every accumulator's bits as they are (s + -0.0 == s for every s, the sum of squares is never -0.0, and
+// a peak only moves to a value strictly above it, so a peak of nothing stays the +0.0 it starts from).  Kernels that do not carry the
+// accumulators themselves have their frames folded by stats_fold (fused.hip.h) after each launch, through the same stats_add.
+constexpr int kStatCount = 6;
+enum { kStatSum = 0, kStatSumSq = 1, kStatPeakPos = 2, kStatPeakNeg = 3, kStatNonfinite = 4, kStatClipped = 5 };
+
+struct VoiceStats {
+    double sum, sum_sq;
+    float peak_pos, peak_neg;
+    uint32_t nonfinite, clipped;  // this launch's counts (added to the buffer's at the end)
+};
+
+SRK_DEV void stats_add(VoiceStats& s, float x)
+{
+    const bool fin = __builtin_isfinite(x);
+    const float xs = fin ? x : -0.0f;
+    const double xd = (double)xs;
+    s.sum += xd;
+    s.sum_sq = __builtin_fma(xd, xd, s.sum_sq);  // (the product is exact: fma and add agree)
+    s.peak_pos = xs > s.peak_pos ? xs : s.peak_pos;
+    s.peak_neg = -xs > s.peak_neg ? -xs : s.peak_neg;
+    s.nonfinite += fin ? 0u : 1u;
+    s.clipped += fabsf(xs) > 1.0f ? 1u : 0u;
+}
+
+SRK_DEV void stats_load(VoiceStats& s, const double* p, size_t V)  // p: field 0 of one voice; fields V apart
+{
+    s.sum = p[(size_t)kStatSum * V];
+    s.sum_sq = p[(size_t)kStatSumSq * V];
+    s.peak_pos = (float)p[(size_t)kStatPeakPos * V];
+    s.peak_neg = (float)p[(size_t)kStatPeakNeg * V];
+    s.nonfinite = s.clipped = 0u;
+}
+SRK_DEV void stats_store(const VoiceStats& s, double* p, size_t V)
+{
+    p[kStatSum * V] = s.sum;
+    p[kStatSumSq * V] = s.sum_sq;
+    p[kStatPeakPos * V] = (double)s.peak_pos;
+    p[kStatPeakNeg * V] = (double)s.peak_neg;
+    p[kStatNonfinite * V] += (double)s.nonfinite;
+    p[kStatClipped * V] += (double)s.clipped;
+}
+
 // ---- per-sample output of the fused kernels ---------------------------------------------------------------
-// kOut: 0 = decide at run time (exact-mode kernels), 1 = frames only, 2 = mix only, 3 = frames + mix.
+// kOut: 0 = decide at run time (exact-mode kernels), 1 = frames only, 2 = mix only, 3 = frames + mix;
+// kOutStats (8) = frames and mix decided at run time, plus the per-voice statistics.  (4 = neither frames nor mix: the kernels specialised
+// at run time for a render that only advances the voice state, jit.cpp)
 // Frames: SGPR row base advanced by V per sample + a constant per-lane offset; lanes past V (only in the
 // last wave) shadow voice V-1, compute the identical sample and store it to the identical address, so the
 // store needs no exec mask.  Mix: the sample goes into a 32-row LDS tile; every 32 samples (and at the end)
@@ -86,16 +135,32 @@ struct Emit {
     uint32_t n_active;  // lanes of this wave that are real voices
 };
 
+// kOutStats: the output stage with the statistics of the lane's voice beside it (a type of its own, so that the other output modes'
+// code stays exactly what it was)
+constexpr int kOutStats = 8;
+struct EmitStats : Emit {
+    double* stats;  // field 0 of this lane's voice (clamped to a real one) in d_stats; fields stats_stride (= V) apart
+    uint32_t stats_stride;
+    VoiceStats st;
+};
+template <bool kStats>
+struct EmitSel { typedef Emit type; };
+template <>
+struct EmitSel<true> { typedef EmitStats type; };
 template <int kOut>
-SRK_DEV void emit_put(Emit& e, float* mix_tile, float o, int i, uint32_t V)  // i = row of the current 32-sample tile
+using EmitOf = typename EmitSel<(kOut & kOutStats) != 0>::type;
+
+template <int kOut, class E>
+SRK_DEV void emit_put(E& e, float* mix_tile, float o, int i, uint32_t V)  // i = row of the current 32-sample tile
 {
-    const bool frames = kOut == 0 ? e.has_frames : (kOut & 1) != 0;
-    const bool mix = kOut == 0 ? e.has_mix : (kOut & 2) != 0;
+    const bool frames = (kOut & ~kOutStats) == 0 ? e.has_frames : (kOut & 1) != 0;
+    const bool mix = (kOut & ~kOutStats) == 0 ? e.has_mix : (kOut & 2) != 0;
     if (frames) {
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), e.rsrc, e.lane_c * 4, (int)e.soff, SRK_FRAME_AUX);
         e.soff += V * 4u;
     }
     if (mix) mix_tile[i * kMixPitch + e.lane] = o;  // (ds_write_addtid_b32 — no address VGPR — measured: no gain)
+    if constexpr ((kOut & kOutStats) != 0) stats_add(e.st, o);
 }
 
 SRK_DEV void emit_rebase(Emit& e)  // point the descriptor at frame_row; a tile spans at most 32 rows = 32 * V * 4 bytes
@@ -109,12 +174,12 @@ SRK_DEV void emit_rebase(Emit& e)  // point the descriptor at frame_row; a tile 
 template <int kOut, bool kBarrier = true>
 SRK_DEV void emit_flush(Emit& e, float* mix_tile, uint32_t t0, int n, uint32_t V)  // the tile holds samples t0 .. t0+n-1
 {
-    const bool frames = kOut == 0 ? e.has_frames : (kOut & 1) != 0;
+    const bool frames = (kOut & ~kOutStats) == 0 ? e.has_frames : (kOut & 1) != 0;
     if (frames) {
         e.frame_row += (size_t)n * V;
         emit_rebase(e);
     }
-    const bool mix = kOut == 0 ? e.has_mix : (kOut & 2) != 0;
+    const bool mix = (kOut & ~kOutStats) == 0 ? e.has_mix : (kOut & 2) != 0;
     if (!mix) return;
     if (!e.full_wave && (uint32_t)e.lane >= e.n_active)  // shadow lanes contribute nothing to the mix
         for (int r = 0; r < kMixRows; r++) mix_tile[r * kMixPitch + e.lane] = 0.0f;
@@ -196,6 +261,22 @@ SRK_DEV void emit_track_flush(Emit& e, const float* track_t0, uint32_t t0, int n
     if (mix && e.lane < n) e.mp[t0 + e.lane] = (float)e.n_active * track_t0[e.lane];
 }
 
+// kOutStats: the statistics of the lane's voice in `plane` — loaded where a launch starts (shadow lanes load the voice they shadow) ...
+SRK_DEV void emit_stats_begin(EmitStats& e, const KernelArgs& a, int plane)
+{
+    const uint32_t V = a.V;
+    e.stats = a.stats + (size_t)plane * kStatCount * V + (size_t)(dev::wave_index(a) * a.lanes + (uint32_t)e.lane_c);
+    e.stats_stride = V;
+    stats_load(e.st, e.stats, V);
+}
+// ... and stored where it ends, by the real voices only
+SRK_DEV void emit_stats_end(const Emit&) {}
+SRK_DEV void emit_stats_end(const EmitStats& e)
+{
+    if ((uint32_t)e.lane >= e.n_active) return;
+    stats_store(e.st, e.stats, e.stats_stride);
+}
+
 SRK_DEV Emit make_emit(const KernelArgs& a, int plane, int lane)
 {
     using dev::WaveMap;
@@ -213,6 +294,20 @@ SRK_DEV Emit make_emit(const KernelArgs& a, int plane, int lane)
     e.has_mix = e.mp != nullptr;
     emit_rebase(e);
     return e;
+}
+
+// The output stage of output mode kOut for `plane` (make_emit; with kOutStats, the statistics loaded beside it)
+template <int kOut>
+SRK_DEV EmitOf<kOut> make_emit_of(const KernelArgs& a, int plane, int lane)
+{
+    if constexpr ((kOut & kOutStats) != 0) {
+        EmitStats e;
+        static_cast<Emit&>(e) = make_emit(a, plane, lane);
+        emit_stats_begin(e, a, plane);
+        return e;
+    } else {
+        return make_emit(a, plane, lane);
+    }
 }
 
 }  // namespace srack

@@ -151,6 +151,15 @@ public:
     {
         check(srack_render(p_, n_samples, d_frames, d_mix, flags, stream));
     }
+    // MonoMixerModule's `*dst += src * gain` over voices: a gain and a bus per voice (n_voices entries each, nullptr: bus 0 / gain 1),
+    // one mix per bus.  The table is not part of the program: changing it between execute_batch calls restarts nothing.
+    void set_buses(uint32_t n_buses, const int* bus = nullptr, const float* gain = nullptr) { check(srack_voices_set_buses(p_, n_buses, bus, gain)); }
+    uint32_t get_buses(int* bus = nullptr, float* gain = nullptr, uint32_t cap = 0) const { return (uint32_t)check(srack_voices_get_buses(p_, bus, gain, cap)); }
+    // execute_batch plus d_bus_mix, f32 [n_buses][channels][n_samples] (written); d_frames, d_mix, d_stats may each be null
+    void execute_batch_buses(uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags = 0, void* stream = nullptr)
+    {
+        check(srack_render_buses(p_, n_samples, d_frames, d_mix, d_stats, d_bus_mix, flags, stream));
+    }
 
     srack_patch* handle() { return p_; }
     const AudioConfig& config() const { return cfg_; }

@@ -352,6 +352,49 @@ enum {
 int srack_render_stats(srack_patch* p, uint32_t n_samples, float* d_frames, float* d_mix,
                        double* d_stats, uint32_t flags, void* stream);
 
+/* ---- mix buses: a gain and a bus per voice, one mix per bus ---------------------------------------------------
+ * MonoMixerModule is `*dst += src * gain` with a gain per input (mixer.rs:110-117); d_mix above is its gain-1 sum over all voices.
+ * The faithful N-voice generalisation has a gain per voice, and hosts group voices (chords, sweep values, left / right, data-set
+ * items): every voice gets a gain and a bus, and a render fills one mix per bus — without the host writing, re-reading and reducing
+ * the frames itself. */
+#define SRACK_MAX_BUSES 65536
+#define SRACK_BUS_NONE  (-1)
+
+/* The mix table of the handle's voices.  Host memory, n_voices entries each, copied.
+ *   bus  : bus[v] in [0, n_buses) or SRACK_BUS_NONE (the voice is in no bus); NULL = every voice in bus 0
+ *   gain : any f32 (0, negative, non-finite included);                        NULL = 1.0f for every voice
+ * 1 <= n_buses <= SRACK_MAX_BUSES; a bus may be empty.  SRACK_ERR_STATE before srack_voices_configure, SRACK_ERR_INVALID for a
+ * bus index outside the range (the table set before stays).  srack_voices_configure drops the table.
+ * The table is NOT part of the patch's program: setting or changing it between renders does not re-flatten, does not restart
+ * the voices and changes no bit of frames, mix, statistics or voice state. */
+int srack_voices_set_buses(srack_patch* p, uint32_t n_buses, const int* bus, const float* gain);
+/* returns n_buses (0: no table set); copies up to cap entries of each (either pointer may be NULL) */
+int srack_voices_get_buses(const srack_patch* p, int* bus, float* gain, uint32_t cap);
+/* Diagnostics (tests, tools): how the table was laid out for the bus fold.  Voices are taken in tiles of 64; a SEGMENT is the voices of
+ * one tile that share a bus.  Returns the number of segments and writes, for the first segment_cap of them in ascending (tile, bus)
+ * order, four ints — tile, bus, the segment's row of the fold's scratch (-1: the bus's only segment, which needs none), voices — and
+ * to `order` (up to order_cap entries) the voices segment after segment, each segment's in the order they are added.  Within a bus
+ * the scratch rows ascend with the tile: that is the order the bus's segments are added in.  Either pointer may be NULL. */
+int srack_voices_bus_plan(const srack_patch* p, int* segments, uint32_t segment_cap, int* order, uint32_t order_cap);
+
+/* srack_render_stats plus the bus mixes:
+ *   d_bus_mix : device, f32 [n_buses][channels][n_samples]
+ *   d_bus_mix[b][c][t] = sum over the voices v with bus[v] == b of  fl32(gain[v] * x[plane(c)][t][v])
+ * x is the f32 sample the call writes (or would write) to d_frames; channels map to planes as for d_mix (an unconnected
+ * channel is 0); product and sum are IEEE f32 (a NaN or inf sample, or 0 * inf, makes that bus's sample non-finite and touches
+ * no other bus); an empty bus is 0.  The call WRITES d_bus_mix (it does not add to it).
+ * d_frames, d_mix, d_stats may each be NULL independently.  d_bus_mix NULL is srack_render_stats exactly.
+ * SRACK_ERR_STATE if d_bus_mix is given and no table is set.
+ * The order of the f32 additions is fixed by the table and the voice count (no floating-point atomics): within a tile of 64 voices a
+ * bus's voices in ascending order, then the bus's tiles in ascending order.  So sample t of every bus has the same bits from run to
+ * run, however the render is cut into calls, and whatever else the call is asked for.  Every voice kernel: each launch's frames —
+ * the host's, or one launch's worth of library scratch — are folded right behind it.  Asking for bus mixes changes neither the
+ * kernel, the chunks nor any bit of frames, mix, statistics or voice state.
+ * Sharded: each rank sets the table of its own voices with GLOBAL bus numbers and the same n_buses, and the per-rank bus mixes are
+ * summed by srack_dist_reduce_mix with count = n_buses * channels * n_samples. */
+int srack_render_buses(srack_patch* p, uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats,
+                       float* d_bus_mix, uint32_t flags, void* stream);
+
 /* Optional: do everything a later srack_render(p, <= n_samples, ..., flags) would do on first use — flatten the graph,
  * upload the programs and the voice table, size the scratch buffers (mix partials when want_mix, control tracks) — so
  * that the first render costs what every render costs.  Renders nothing and leaves the voice state untouched. */
@@ -365,8 +408,8 @@ int srack_render_kernel_compile(srack_patch* p, uint32_t flags);
 
 /* Scratch the render needs for the mix-down partials etc. is owned by the handle; this reports it. */
 /* Human-readable: the programs (ops, rows, units), "approx[...]" — the default mode's error bound or why the flavour is exact —, any
- * SRACK_* tuning variable the process carries ("knobs=[...]": such a process does not render what was tested), where the kernel came from,
- * and last "kernel=<name>".  Returns the length; copies at most cap - 1 characters (buf may be NULL to ask for the length). */
+ * SRACK_* tuning variable the process carries ("knobs=[...]": such a process does not render what was tested), "buses=<n>[fold]" when the
+ * last render filled the mixes of n buses (by a fold over each launch's frames), where the kernel came from, and last "kernel=<name>".  Returns the length; copies at most cap - 1 characters (buf may be NULL to ask for the length). */
 int srack_render_info(srack_patch* p, char* buf, size_t cap);
 
 /* Average duration in ms of the dominant render kernel over the renders since the last call with

@@ -56,6 +56,9 @@ mod ffi {
         pub fn srack_render_planes(p: *mut SrackPatch, channel_plane: *mut c_int, cap: c_int) -> c_int;
         pub fn srack_render(p: *mut SrackPatch, n_samples: u32, d_frames: *mut f32, d_mix: *mut f32, flags: u32, stream: *mut c_void) -> c_int;
         pub fn srack_render_stats(p: *mut SrackPatch, n_samples: u32, d_frames: *mut f32, d_mix: *mut f32, d_stats: *mut f64, flags: u32, stream: *mut c_void) -> c_int;
+        pub fn srack_voices_set_buses(p: *mut SrackPatch, n_buses: u32, bus: *const c_int, gain: *const f32) -> c_int;
+        pub fn srack_voices_get_buses(p: *const SrackPatch, bus: *mut c_int, gain: *mut f32, cap: u32) -> c_int;
+        pub fn srack_render_buses(p: *mut SrackPatch, n_samples: u32, d_frames: *mut f32, d_mix: *mut f32, d_stats: *mut f64, d_bus_mix: *mut f32, flags: u32, stream: *mut c_void) -> c_int;
         pub fn srack_device_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
         pub fn srack_device_free(d_ptr: *mut c_void) -> c_int;
         pub fn srack_device_to_host(h_dst: *mut c_void, d_src: *const c_void, bytes: usize, stream: *mut c_void) -> c_int;
@@ -83,6 +86,10 @@ pub mod stat {
     pub const CLIPPED: usize = 5;
     pub const COUNT: usize = 6;
 }
+
+/// Mix buses (`SRACK_MAX_BUSES`, `SRACK_BUS_NONE`).
+pub const MAX_BUSES: u32 = 65536;
+pub const BUS_NONE: i32 = -1;
 
 /// Render flags (values of `SRACK_RENDER_*`).
 pub mod render_flags {
@@ -268,6 +275,28 @@ impl Patch {
         let f = frames.map_or(std::ptr::null_mut(), |b| b.as_f32());
         let m = mix.map_or(std::ptr::null_mut(), |b| b.as_f32());
         check(unsafe { ffi::srack_render_stats(self.raw, n_samples, f, m, stats.as_f64(), flags, std::ptr::null_mut()) }).map(|_| ())
+    }
+    /// The mix table of the voices: `bus[v]` in `0 .. n_buses` or `BUS_NONE` (None: every voice in bus 0), `gain[v]` any f32 (None: 1.0).
+    /// Not part of the program: changing it between renders restarts nothing (`srack_voices_set_buses`).
+    pub fn set_buses(&mut self, n_buses: u32, bus: Option<&[i32]>, gain: Option<&[f32]>) -> Result<(), Error> {
+        let b = bus.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        let g = gain.map_or(std::ptr::null(), |x| x.as_ptr());
+        check(unsafe { ffi::srack_voices_set_buses(self.raw, n_buses, b, g) }).map(|_| ())
+    }
+    /// `(n_buses, bus, gain)` of the table set, `n_voices` entries each; `n_buses` 0: none set.
+    pub fn get_buses(&self, n_voices: usize) -> Result<(u32, Vec<i32>, Vec<f32>), Error> {
+        let (mut b, mut g) = (vec![0 as c_int; n_voices], vec![0f32; n_voices]);
+        let n = check(unsafe { ffi::srack_voices_get_buses(self.raw, b.as_mut_ptr(), g.as_mut_ptr(), n_voices as u32) })?;
+        Ok((n as u32, b, g))
+    }
+    /// `execute_batch` plus one weighted mix per bus: `bus_mix` is `[n_buses][channels][n_samples]` f32, written by the call
+    /// (`srack_render_buses`); frames, mix and statistics may each be None.
+    pub fn execute_batch_buses(&mut self, n_samples: u32, frames: Option<&DeviceBuffer>, mix: Option<&DeviceBuffer>, stats: Option<&DeviceBuffer>,
+                               bus_mix: &DeviceBuffer, flags: u32) -> Result<(), Error> {
+        let f = frames.map_or(std::ptr::null_mut(), |b| b.as_f32());
+        let m = mix.map_or(std::ptr::null_mut(), |b| b.as_f32());
+        let s = stats.map_or(std::ptr::null_mut(), |b| b.as_f64());
+        check(unsafe { ffi::srack_render_buses(self.raw, n_samples, f, m, s, bus_mix.as_f32(), flags, std::ptr::null_mut()) }).map(|_| ())
     }
 }
 

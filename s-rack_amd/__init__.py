@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsrack_hip.so")
 
 OK, ERR_INVALID, ERR_PORT, ERR_NO_OUTPUT, ERR_SELF_LOOP, ERR_STATE, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8
+MAX_BUSES, BUS_NONE = 65536, -1
 STAT_SUM, STAT_SUM_SQ, STAT_PEAK_POS, STAT_PEAK_NEG, STAT_NONFINITE, STAT_CLIPPED, STAT_COUNT = 0, 1, 2, 3, 4, 5, 6
 RENDER_DEFAULT, RENDER_EXACT_OSC, RENDER_NO_FUSION, RENDER_NO_UNIFORM_HOIST, RENDER_NO_CTL_STAGES, RENDER_NO_SPECIALIZE, RENDER_SPECIALIZE, RENDER_KEEP_DEFAULT = 0, 1, 2, 4, 8, 16, 32, 64
 
@@ -28,6 +29,7 @@ ABI_SYMBOLS = [
     "srack_patch_set_module_position", "srack_patch_get_module_position", "srack_patch_set_output_buffer", "srack_patch_get_output_buffer", "srack_patch_set_noise_seed", "srack_patch_connect", "srack_patch_disconnect", "srack_patch_get_input",
     "srack_patch_plan", "srack_patch_plan_list", "srack_patch_removed_edges", "srack_patch_delayed_edges",
     "srack_voices_configure", "srack_voices_set_field_f32", "srack_voices_set_field_f64", "srack_render_planes", "srack_render", "srack_render_stats", "srack_render_reserve",
+    "srack_voices_set_buses", "srack_voices_get_buses", "srack_voices_bus_plan", "srack_render_buses",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
     "srack_device_alloc", "srack_device_free", "srack_device_to_host", "srack_device_from_host", "srack_device_sync",
     "srack_dist_unique_id", "srack_dist_init", "srack_dist_comm_count", "srack_dist_destroy", "srack_dist_reduce_mix",
@@ -92,6 +94,11 @@ def _load():
     L.srack_render_planes.argtypes = [vp, ip, i32]
     L.srack_render.argtypes = [vp, u32, vp, vp, u32, vp]
     L.srack_render_stats.argtypes = [vp, u32, vp, vp, vp, u32, vp]
+    if hasattr(L, "srack_render_buses"):  # (tools/ alternate older builds of the library under this binding)
+        L.srack_voices_set_buses.argtypes = [vp, u32, ip, fp]
+        L.srack_voices_get_buses.argtypes = [vp, ip, fp, u32]
+        L.srack_voices_bus_plan.argtypes = [vp, ip, u32, ip, u32]
+        L.srack_render_buses.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp]
     L.srack_render_reserve.argtypes = [vp, u32, i32, u32]
     L.srack_render_info.argtypes = [vp, C.c_char_p, sz]
     L.srack_render_kernel_ms.argtypes = [vp, dp, ip, i32]
@@ -348,6 +355,36 @@ class Patch:
             a = np.ascontiguousarray(values, dtype=np.float32)
             _check(lib.srack_voices_set_field_f32(self.h, module, field, a.ctypes.data_as(C.POINTER(C.c_float))))
 
+    def set_buses(self, n_buses, bus=None, gain=None):
+        """The mix table (srack_voices_set_buses): bus[v] in [0, n_buses) or BUS_NONE (None: every voice in bus 0), gain[v] any f32
+        (None: 1.0).  Not part of the program: changing it between renders restarts nothing."""
+        b = g = None
+        if bus is not None:
+            b = np.ascontiguousarray(bus, dtype=np.intc)
+            assert b.shape == (self.n_voices,), b.shape
+        if gain is not None:
+            g = np.ascontiguousarray(gain, dtype=np.float32)
+            assert g.shape == (self.n_voices,), g.shape
+        _check(lib.srack_voices_set_buses(self.h, n_buses, None if b is None else b.ctypes.data_as(C.POINTER(C.c_int)),
+                                          None if g is None else g.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def get_buses(self):
+        """-> (n_buses, bus int32 [V], gain f32 [V]); (0, None, None) when no table is set"""
+        n = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        if n == 0:
+            return 0, None, None
+        b, g = np.empty(self.n_voices, dtype=np.intc), np.empty(self.n_voices, dtype=np.float32)
+        _check(lib.srack_voices_get_buses(self.h, b.ctypes.data_as(C.POINTER(C.c_int)), g.ctypes.data_as(C.POINTER(C.c_float)), self.n_voices))
+        return n, b, g
+
+    def bus_plan(self):
+        """How the table is laid out for the bus fold (srack_voices_bus_plan) -> (segments int [S][4]: tile, bus, scratch row or -1, voices;
+        order: the voices segment after segment)"""
+        n = _check(lib.srack_voices_bus_plan(self.h, None, 0, None, 0))
+        seg, order = np.zeros((n, 4), dtype=np.intc), np.zeros(max(1, self.n_voices), dtype=np.intc)
+        _check(lib.srack_voices_bus_plan(self.h, seg.ctypes.data_as(C.POINTER(C.c_int)), n, order.ctypes.data_as(C.POINTER(C.c_int)), self.n_voices))
+        return seg, order[:int(seg[:, 3].sum())]
+
     def get_voice_field(self, module, field):
         out = np.empty(self.n_voices, dtype=np.float64)
         _check(lib.srack_voices_get_field(self.h, module, field, out.ctypes.data_as(C.POINTER(C.c_double))))
@@ -362,6 +399,10 @@ class Patch:
     def reserve(self, n_samples, want_mix=True, flags=0):
         """First-use set-up (flatten, upload, scratch buffers) ahead of the first render."""
         _check(lib.srack_render_reserve(self.h, n_samples, 1 if want_mix else 0, flags))
+
+    def render_buses_raw(self, n_samples, d_bus_mix, d_frames=None, d_mix=None, d_stats=None, flags=0, stream=None):
+        """render_raw plus d_bus_mix: device, f32 [n_buses][channels][n_samples], written (srack_render_buses)."""
+        _check(lib.srack_render_buses(self.h, n_samples, d_frames, d_mix, d_stats, d_bus_mix, flags, stream))
 
     def render_raw(self, n_samples, d_frames=None, d_mix=None, flags=0, stream=None, d_stats=None):
         """Device pointers (ints) in; asynchronous on `stream`.  d_stats: per-voice statistics, f64 [planes][STAT_COUNT][V],
@@ -455,6 +496,46 @@ class Patch:
             return fr, mx, st
         finally:
             for d in (d_fr, d_mx, d_st):
+                if d.value:
+                    lib.srack_device_free(d)
+
+    def render_buses(self, n_samples, frames=False, mix=False, stats=False, flags=0):
+        """render_stats() plus the bus mixes of the table set with set_buses -> (frames or None, mix or None, stats or None — from zeros —,
+        bus_mix f32 [n_buses][channels][T])."""
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        if n_buses == 0:
+            raise SrackError(ERR_STATE, "render_buses: no mix table set (set_buses)")
+        n_planes, _ = self.planes()
+        V, T, Cn = self.n_voices, n_samples, self.channels
+        bm = np.empty((n_buses, Cn, T), dtype=np.float32)
+        st = np.zeros((n_planes, STAT_COUNT, V)) if stats else None
+        d_fr, d_mx, d_st, d_bm = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        try:
+            if frames and n_planes > 0:
+                _check(lib.srack_device_alloc(C.byref(d_fr), max(1, n_planes * T * V * 4)))
+            if mix:
+                _check(lib.srack_device_alloc(C.byref(d_mx), max(1, Cn * T * 4)))
+            if stats:
+                _check(lib.srack_device_alloc(C.byref(d_st), max(8, st.nbytes)))
+                _check(lib.srack_device_from_host(d_st, st.ctypes.data_as(C.c_void_p), st.nbytes, None))
+            _check(lib.srack_device_alloc(C.byref(d_bm), max(4, bm.nbytes)))
+            self.render_buses_raw(T, d_bm, d_fr if d_fr.value else None, d_mx if d_mx.value else None, d_st if d_st.value else None, flags, None)
+            fr = mx = None
+            if frames:
+                fr = np.zeros((n_planes, T, V), dtype=np.float32)
+                if d_fr.value:
+                    _check(lib.srack_device_to_host(fr.ctypes.data_as(C.c_void_p), d_fr, fr.nbytes, None))
+            if mix:
+                mx = np.empty((Cn, T), dtype=np.float32)
+                _check(lib.srack_device_to_host(mx.ctypes.data_as(C.c_void_p), d_mx, mx.nbytes, None))
+            if stats:
+                _check(lib.srack_device_to_host(st.ctypes.data_as(C.c_void_p), d_st, st.nbytes, None))
+            if bm.nbytes:
+                _check(lib.srack_device_to_host(bm.ctypes.data_as(C.c_void_p), d_bm, bm.nbytes, None))
+            _check(lib.srack_device_sync(None))
+            return fr, mx, st, bm
+        finally:
+            for d in (d_fr, d_mx, d_st, d_bm):
                 if d.value:
                     lib.srack_device_free(d)
 

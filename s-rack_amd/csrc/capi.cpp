@@ -521,6 +521,11 @@ int srack_voices_configure(srack_patch* p, uint32_t n_voices)
         p->h.overrides.clear();
         p->h.voices_revision++;
         p->h.voices_fresh = true;
+        p->h.n_buses = 0;  // the mix table belonged to the voices that were
+        p->h.bus.clear();
+        p->h.bus_gain.clear();
+        p->h.bus_plan = BusPlan();
+        p->h.bus_revision++;
         return SRACK_OK;
     });
 }
@@ -548,7 +553,7 @@ int srack_render(srack_patch* p, uint32_t n_samples, float* d_frames, float* d_m
             set_error("render: call srack_voices_configure first");
             return SRACK_ERR_STATE;
         }
-        return device_render(p->h, n_samples, d_frames, d_mix, nullptr, flags, stream);
+        return device_render(p->h, n_samples, d_frames, d_mix, nullptr, nullptr, flags, stream);
     });
 }
 
@@ -564,7 +569,94 @@ int srack_render_stats(srack_patch* p, uint32_t n_samples, float* d_frames, floa
             set_error("render_stats: call srack_voices_configure first");
             return SRACK_ERR_STATE;
         }
-        return device_render(p->h, n_samples, d_frames, d_mix, d_stats, flags, stream);
+        return device_render(p->h, n_samples, d_frames, d_mix, d_stats, nullptr, flags, stream);
+    });
+}
+
+int srack_voices_set_buses(srack_patch* p, uint32_t n_buses, const int* bus, const float* gain)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        PatchHandle& h = p->h;
+        if (h.n_voices == 0) {
+            set_error("voices_set_buses: call srack_voices_configure first");
+            return SRACK_ERR_STATE;
+        }
+        if (n_buses == 0 || n_buses > SRACK_MAX_BUSES) {
+            set_error("voices_set_buses: n_buses must be 1 .. 65536");
+            return SRACK_ERR_INVALID;
+        }
+        for (uint32_t v = 0; bus && v < h.n_voices; v++)
+            if (bus[v] < SRACK_BUS_NONE || (bus[v] >= 0 && (uint32_t)bus[v] >= n_buses)) {
+                set_error("voices_set_buses: voice " + std::to_string(v) + " names bus " + std::to_string(bus[v]) + " of " + std::to_string(n_buses));
+                return SRACK_ERR_INVALID;
+            }
+        // (built aside and committed at the end: a failure above or an allocation failure here leaves the old table in place)
+        std::vector<int32_t> b(h.n_voices, 0);
+        std::vector<float> g(h.n_voices, 1.0f);
+        if (bus) std::copy(bus, bus + h.n_voices, b.begin());
+        if (gain) std::copy(gain, gain + h.n_voices, g.begin());
+        BusPlan plan = bus_plan_make(h.n_voices, n_buses, b.data());
+        h.n_buses = n_buses;
+        h.bus = std::move(b);
+        h.bus_gain = std::move(g);
+        h.bus_plan = std::move(plan);
+        h.bus_revision++;
+        return SRACK_OK;
+    });
+}
+
+int srack_voices_get_buses(const srack_patch* p, int* bus, float* gain, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        const PatchHandle& h = p->h;
+        const uint32_t n = h.n_buses ? std::min(cap, h.n_voices) : 0u;
+        if (bus) std::copy(h.bus.begin(), h.bus.begin() + n, bus);
+        if (gain) std::copy(h.bus_gain.begin(), h.bus_gain.begin() + n, gain);
+        return (int)h.n_buses;
+    });
+}
+
+int srack_voices_bus_plan(const srack_patch* p, int* segments, uint32_t segment_cap, int* order, uint32_t order_cap)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        const BusPlan& B = p->h.bus_plan;
+        uint32_t n_order = 0;
+        for (uint32_t i = 0; i < B.n_tiles; i++)
+            for (uint32_t s = B.tile_seg[i]; s < B.tile_seg[i + 1]; s++) {
+                const uint32_t j0 = s == B.tile_seg[i] ? 0u : B.seg_end[s - 1], j1 = B.seg_end[s];
+                if (segments && s < segment_cap) {
+                    segments[4 * s + 0] = (int)i;
+                    segments[4 * s + 1] = B.seg_bus[s];
+                    segments[4 * s + 2] = B.seg_dst[s] >= 0 ? B.seg_dst[s] : -1;
+                    segments[4 * s + 3] = (int)(j1 - j0);
+                }
+                for (uint32_t j = j0; j < j1; j++, n_order++)
+                    if (order && n_order < order_cap) order[n_order] = (int)(i * kBusTile + B.order[(size_t)i * kBusTile + j]);
+            }
+        return (int)B.seg_end.size();
+    });
+}
+
+int srack_render_buses(srack_patch* p, uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags, void* stream)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        if (((uintptr_t)d_stats & 7u) != 0) {
+            set_error("render_buses: d_stats must be 8-byte aligned");
+            return SRACK_ERR_INVALID;
+        }
+        if (p->h.n_voices == 0) {
+            set_error("render_buses: call srack_voices_configure first");
+            return SRACK_ERR_STATE;
+        }
+        if (d_bus_mix && p->h.n_buses == 0) {
+            set_error("render_buses: d_bus_mix given and no mix table set: call srack_voices_set_buses first");
+            return SRACK_ERR_STATE;
+        }
+        return device_render(p->h, n_samples, d_frames, d_mix, d_stats, d_bus_mix, flags, stream);
     });
 }
 
@@ -607,6 +699,7 @@ int srack_render_info(srack_patch* p, char* buf, size_t cap)
         s += tuning_knobs_note();
         const char* k = device_kernel_name(p->h);
         // (the kernel's name stays LAST: hosts and tests read it with split("kernel="))
+        s += device_bus_note(p->h);
         s += device_jit_note(p->h);
         if (k && *k) s += std::string(" kernel=") + k;
         if (buf && cap) {
@@ -676,6 +769,13 @@ int srack_voices_get_field(srack_patch* p, int module, int field, double* values
         }
         int rc = ensure_program(h, h.prog_valid ? h.prog_flags : 0u);
         if (rc != SRACK_OK) return rc;
+        {  // (before anything looks the field up in the device tables: a field the module does not have has no row there)
+            const int nf = h.graph.num_fields(module);
+            if (nf < 0 || field < 0 || field >= nf) {
+                set_error("voices_get_field: no such module/field");
+                return SRACK_ERR_INVALID;
+            }
+        }
         std::vector<double> got;
         if (read_device_state(h, module, field, got)) {
             for (uint32_t v = 0; v < h.n_voices; v++) values[v] = got[v];

@@ -167,8 +167,15 @@ struct DeviceState {
     size_t mixgroup_bytes = 0;
     float* d_tracks = nullptr;
     size_t tracks_bytes = 0;
-    float* d_stat_frames = nullptr;  // frames of one launch for stats_fold when the host asked for statistics without frames
+    float* d_stat_frames = nullptr;  // frames of one launch for stats_fold / the bus fold when the host asked for statistics or bus mixes without frames
     size_t stat_frames_bytes = 0;
+    // mix buses: the handle's bus plan (buses.hpp) as one block of words on the device — gain, order, tile_seg, seg_end, seg_dst, bus_first,
+    // bus_count — uploaded when the table changed (bus_revision), and the fold's partials
+    uint32_t* d_bus_tab = nullptr;
+    uint64_t bus_revision = 0;
+    float* d_bus_part = nullptr;
+    size_t bus_part_bytes = 0;
+    uint32_t last_buses = 0;  // bus mixes the last render filled (srack_render_info)
     std::shared_ptr<const JitKernel> jit[5];  // the specialised voice kernel per output mode (1 frames, 2 mix, 3 both, 4 neither), co-owned with the cache
     bool jit_failed = false;  // specialisation was tried by default and is not available: the interpreter renders
     std::string jit_note;     // for srack_render_info: how the kernel was come by (compiled in N ms / disk cache / memory), or why there is none
@@ -192,6 +199,8 @@ void device_release(DeviceState* d)
     (void)hipFree(d->d_mixgroup);
     (void)hipFree(d->d_tracks);
     (void)hipFree(d->d_stat_frames);
+    (void)hipFree(d->d_bus_tab);
+    (void)hipFree(d->d_bus_part);
     if (d->tick.done) (void)hipEventDestroy(d->tick.done);
     for (hipEvent_t e : d->ev_mix) (void)hipEventDestroy(e);
     if (d->ev_mix_done) (void)hipEventDestroy(d->ev_mix_done);
@@ -859,6 +868,10 @@ struct Segment {
     // asked for) one launch's worth in d_stat_frames, which the kernel then writes instead.  Same kernel, same chunks, same bits.
     bool fold = false;
     uint32_t fold_rows = 0;  // rows of d_stat_frames per plane (0: the host's frames)
+    // Bus mixes (srack_render_buses): f32 [n_buses][channels][T_total] of the WHOLE render, or null.  Always a fold over each launch's frames
+    // (bus_fold_tiles / bus_fold_sum), the host's or d_stat_frames: same kernel, same chunks, same bits of everything else.
+    float* d_bus;
+    uint32_t bus_slab = 0;  // rows the fold takes at a time (the pitch of its partials)
     const hipStream_t st;
     int rc = SRACK_OK;
     // Voices per wave.  A full wave (64) is right whenever there are enough voices to give every SIMD work.
@@ -884,10 +897,10 @@ struct Segment {
     MixArgs m{};
     bool mix_aside = false;
 
-    Segment(PatchHandle& h_, uint32_t T_total_, uint32_t t_seg_, uint32_t T_, float* d_frames_, float* d_mix_, double* d_stats_, uint32_t flags_, hipStream_t st_)
+    Segment(PatchHandle& h_, uint32_t T_total_, uint32_t t_seg_, uint32_t T_, float* d_frames_, float* d_mix_, double* d_stats_, float* d_bus_, uint32_t flags_, hipStream_t st_)
         : h(h_), P(h_.prog.voice), d(h_.dev), tk(h_.dev->tick), V(h_.prog.voice.n_voices), C((uint32_t)h_.prog.voice.hdr.n_channels), T_total(T_total_),
           t_seg(t_seg_), T(T_), flags(flags_), d_frames(d_frames_ ? d_frames_ + (size_t)t_seg_ * h_.prog.voice.n_voices : nullptr),
-          d_mix(d_mix_ ? d_mix_ + t_seg_ : nullptr), d_stats(d_stats_), st(st_), fm_block(fm_block_shape(h_.prog.voice, flags_, T_)), fm_block_x(fm_block_x_shape(h_.prog.voice, flags_, T_)), fm_x_z1(fm_x_z1_shape(h_.prog.voice, flags_)),
+          d_mix(d_mix_ ? d_mix_ + t_seg_ : nullptr), d_stats(d_stats_), d_bus(d_bus_ ? d_bus_ + t_seg_ : nullptr), st(st_), fm_block(fm_block_shape(h_.prog.voice, flags_, T_)), fm_block_x(fm_block_x_shape(h_.prog.voice, flags_, T_)), fm_x_z1(fm_x_z1_shape(h_.prog.voice, flags_)),
           lanes((fm_block || fm_block_x) ? (uint32_t)kBlkVoices : lanes_per_wave(h_.prog.voice.n_voices)), n_waves((h_.prog.voice.n_voices + lanes - 1) / lanes)
     {
     }
@@ -1023,11 +1036,67 @@ struct Segment {
         tk.slots_n = batch;
         return SRACK_OK;
     }
+    // ---- mix buses: the table on the device; the argument block of one slab's fold ----------------------------------------------------------
+    int bus_upload()
+    {
+        const BusPlan& B = h.bus_plan;
+        if (d->d_bus_tab && d->bus_revision == h.bus_revision) return SRACK_OK;
+        std::vector<uint32_t> w;
+        auto put = [&w](const void* p, size_t n) { w.insert(w.end(), (const uint32_t*)p, (const uint32_t*)p + n); };
+        put(h.bus_gain.data(), h.bus_gain.size());
+        put(B.order.data(), B.order.size());
+        put(B.tile_seg.data(), B.tile_seg.size());
+        put(B.seg_end.data(), B.seg_end.size());
+        put(B.seg_dst.data(), B.seg_dst.size());
+        put(B.bus_first.data(), B.bus_first.size());
+        put(B.bus_count.data(), B.bus_count.size());
+        // a fresh block: an earlier render may still be reading the old one (hipFree waits for it)
+        (void)hipFree(d->d_bus_tab);
+        d->d_bus_tab = nullptr;
+        HIP_TRY(hipMalloc(&d->d_bus_tab, sizeof(uint32_t) * w.size()));
+        HIP_TRY(hipMemcpy(d->d_bus_tab, w.data(), sizeof(uint32_t) * w.size(), hipMemcpyHostToDevice));
+        d->bus_revision = h.bus_revision;
+        return SRACK_OK;
+    }
+    // frames: the slab's first row (plane 0); t_at: the slab's first sample within this segment
+    BusFoldArgs bus_args(const float* frames, uint64_t plane_stride, uint32_t t_at, uint32_t rows)
+    {
+        const BusPlan& B = h.bus_plan;
+        BusFoldArgs b{};
+        b.frames = frames;
+        b.plane_stride = plane_stride;
+        b.V = V;
+        b.T = rows;
+        const uint32_t* w = d->d_bus_tab;
+        b.gain = (const float*)w;
+        b.order = (w += h.bus_gain.size());
+        b.tile_seg = (w += B.order.size());
+        b.seg_end = (w += B.tile_seg.size());
+        b.seg_dst = (const int32_t*)(w += B.seg_end.size());
+        b.bus_first = (w += B.seg_dst.size());
+        b.bus_count = (const int32_t*)(w += B.bus_first.size());
+        b.part = d->d_bus_part;
+        b.n_partials = B.n_partials;
+        b.part_pitch = bus_slab;
+        b.n_buses = h.n_buses;
+        b.n_planes = (uint32_t)P.hdr.n_planes;
+        b.n_channels = C;
+        b.out = d_bus + t_at;
+        b.out_stride = T_total;
+        for (int c = 0; c < 8; c++) b.channel_plane[c] = (uint32_t)c < C ? P.hdr.channel_plane[c] : -1;
+        return b;
+    }
     // ---- prepare: a program nothing of which reaches the output; the mix scratch -----------------------------------------------------------
     int prepare(bool& done)
     {
         done = false;
+        if (d_bus && (rc = bus_upload()) != SRACK_OK) return rc;
         if (P.hdr.n_planes == 0) {  // nothing reaches the output: silence (output.rs:55)
+            if (d_bus) {  // no channel is connected: bus_fold_sum zeroes them all
+                const BusFoldArgs b = bus_args(nullptr, 0, 0, T);
+                hipLaunchKernelGGL(bus_fold_sum, dim3(h.n_buses * ((T + 255) / 256)), dim3(256), 0, st, b);
+                HIP_TRY(hipGetLastError());
+            }
             if (d_mix)
                 for (uint32_t c = 0; c < C; c++)
                     hipLaunchKernelGGL(fill_zero, dim3((T + 255) / 256), dim3(256), 0, st, d_mix + (size_t)c * T_total, (size_t)T);
@@ -1043,6 +1112,7 @@ struct Segment {
             d_mix = nullptr;
         }
         if (P.hdr.n_planes == 0) d_stats = nullptr;  // (no plane: nothing to fold, the buffer stays as it is)
+        if (P.hdr.n_planes == 0) d_bus = nullptr;    // (every channel of every bus has been zeroed above)
 
         return SRACK_OK;
     }
@@ -1061,7 +1131,7 @@ struct Segment {
         co_ctl = has_ctl && P.fused == FUSED_VOICE_CHAIN_TRACK && n_stages == 1 && h.prog.ctl[0].fused == FUSED_CTL_GATE_ENV && h.prog.n_tracks == 1;
         {
             // (a specialised kernel never carries the statistics: asked for them, it writes frames — the host's or scratch — to fold)
-            const int om = (d_frames || d_stats ? 1 : 0) | (d_mix ? 2 : 0);
+            const int om = (d_frames || d_stats || d_bus ? 1 : 0) | (d_mix ? 2 : 0);
             if ((rc = resolve_specialized(h, flags, T, om ? om : 4, &special, &special_ctl)) != SRACK_OK) return rc;
             fold = d_stats && !stats_in_kernel(P, special);
         }
@@ -1115,9 +1185,19 @@ struct Segment {
         if (d_mix && (rc = grow(d->d_mixpart, d->mixpart_bytes, sizeof(float) * (size_t)P.hdr.n_planes * n_waves * stride)) != SRACK_OK) return rc;
         if (d_mix && (rc = grow(d->d_mixgroup, d->mixgroup_bytes, sizeof(float) * (size_t)P.hdr.n_planes * kMixSplit * stride)) != SRACK_OK) return rc;
         if (has_ctl && (rc = grow(d->d_tracks, d->tracks_bytes, sizeof(float) * (size_t)h.prog.n_tracks * T)) != SRACK_OK) return rc;
-        if (fold && !d_frames) {
+        if ((fold || d_bus) && !d_frames) {
             for (const auto& c : chunks) fold_rows = std::max(fold_rows, c.second);
             if ((rc = grow(d->d_stat_frames, d->stat_frames_bytes, sizeof(float) * (size_t)P.hdr.n_planes * fold_rows * V)) != SRACK_OK) return rc;
+        }
+        if (d_bus) {
+            // The partials of one slab: [planes][n_partials][bus_slab].  A launch is folded in slabs short enough to keep them within
+            // kBusPartBytes (a table that scatters every bus over every tile has as many partials as voices), but never under one 64-row tile.
+            constexpr size_t kBusPartBytes = (size_t)256 << 20;
+            uint32_t longest = 0;
+            for (const auto& c : chunks) longest = std::max(longest, c.second);
+            const size_t per_row = sizeof(float) * (size_t)P.hdr.n_planes * std::max(1u, h.bus_plan.n_partials);
+            bus_slab = (uint32_t)std::min<size_t>((longest + 63u) / 64u * 64u, std::max<size_t>(64, kBusPartBytes / per_row / 64 * 64));
+            if (h.bus_plan.n_partials > 0 && (rc = grow(d->d_bus_part, d->bus_part_bytes, per_row * bus_slab)) != SRACK_OK) return rc;
         }
         // One argument block per (launch, control unit): launch j runs unit s on chunk j - lag[s]; chunk c is complete after launch
         // c + max_lag.  (A control program that was not cut into units is one unit with lag 0.)
@@ -1390,6 +1470,16 @@ struct Segment {
                 hipLaunchKernelGGL(stats_fold, dim3((V + 255) / 256, (uint32_t)P.hdr.n_planes), dim3(256), 0, st, ka.frames, ka.plane_stride, V, len, d_stats);
                 HIP_TRY(hipGetLastError());
             }
+            if (d_bus) {  // likewise; slab after slab through the one block of partials (in stream order)
+                const uint32_t n_seg = (uint32_t)h.bus_plan.seg_end.size();
+                for (uint32_t r0 = 0; r0 < len; r0 += bus_slab) {
+                    const uint32_t rows = std::min(bus_slab, len - r0);
+                    const BusFoldArgs b = bus_args(ka.frames + (size_t)r0 * V, ka.plane_stride, t_off + r0, rows);
+                    if (n_seg > 0) hipLaunchKernelGGL(bus_fold_tiles, dim3(h.bus_plan.n_tiles, (rows + kBusRows - 1) / kBusRows, (uint32_t)P.hdr.n_planes), dim3(64), 0, st, b);
+                    hipLaunchKernelGGL(bus_fold_sum, dim3(h.n_buses * ((rows + 255) / 256)), dim3(256), 0, st, b);
+                    HIP_TRY(hipGetLastError());
+                }
+            }
             if (mix_aside && k + 1 < n_chunks) {
                 HIP_TRY(hipEventRecord(d->ev_mix[k], st));
                 HIP_TRY(hipStreamWaitEvent(d->mix_stream, d->ev_mix[k], 0));
@@ -1471,7 +1561,7 @@ struct Segment {
     }
 };
 
-static int render_segment(PatchHandle& h, uint32_t T_total, uint32_t t_seg, uint32_t T, float* d_frames, float* d_mix, double* d_stats, uint32_t flags, hipStream_t st)
+static int render_segment(PatchHandle& h, uint32_t T_total, uint32_t t_seg, uint32_t T, float* d_frames, float* d_mix, double* d_stats, float* d_bus, uint32_t flags, hipStream_t st)
 {
     if (!h.dev) {
         const int rc = upload_program(h);
@@ -1481,13 +1571,13 @@ static int render_segment(PatchHandle& h, uint32_t T_total, uint32_t t_seg, uint
         HIP_TRY(hipStreamWaitEvent(st, h.dev->ev_ready, 0));
         h.dev->ready_pending = false;
     }
-    return Segment(h, T_total, t_seg, T, d_frames, d_mix, d_stats, flags, st).run();
+    return Segment(h, T_total, t_seg, T, d_frames, d_mix, d_stats, d_bus, flags, st).run();
 }
 
 // A render is cut into segments of at most kSegment samples so that the scratch it needs (per-wave mix partials
 // [planes][V/64][T], control tracks [n_tracks][T]) stays bounded however long the render is: 16 MB of partials per
 // 1000 samples at 262 144 voices.  Voice and control state carry over between segments exactly as between calls.
-int device_render(PatchHandle& h, uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, uint32_t flags, void* stream)
+int device_render(PatchHandle& h, uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus, uint32_t flags, void* stream)
 {
     int rc = ensure_program(h, flags);
     if (rc != SRACK_OK) return rc;
@@ -1500,7 +1590,8 @@ int device_render(PatchHandle& h, uint32_t n_samples, float* d_frames, float* d_
     flags = h.prog.effective_flags | (flags & kLaunchPolicyFlags);
     constexpr uint32_t kSegment = 65536;
     for (uint32_t t = 0; t < n_samples && rc == SRACK_OK; t += kSegment)
-        rc = render_segment(h, n_samples, t, std::min(kSegment, n_samples - t), d_frames, d_mix, d_stats, flags, (hipStream_t)stream);
+        rc = render_segment(h, n_samples, t, std::min(kSegment, n_samples - t), d_frames, d_mix, d_stats, d_bus, flags, (hipStream_t)stream);
+    if (h.dev) h.dev->last_buses = d_bus ? h.n_buses : 0u;
     return rc;
 }
 
@@ -1575,6 +1666,7 @@ int device_read_rows(PatchHandle& h, int ctl_stage, int first_row, int n_rows, u
 }
 
 const char* device_kernel_name(const PatchHandle& h) { return h.dev ? h.dev->kernel_name : ""; }
+std::string device_bus_note(const PatchHandle& h) { return h.dev && h.dev->last_buses ? " buses=" + std::to_string(h.dev->last_buses) + "[fold]" : std::string(); }
 std::string device_jit_note(const PatchHandle& h) { return h.dev ? h.dev->jit_note : std::string(); }
 
 }  // namespace srack

@@ -6,6 +6,7 @@
 #include <utility>
 #include <vector>
 
+#include "buses.hpp"
 #include "flatten.hpp"
 #include "graph.hpp"
 
@@ -40,6 +41,13 @@ struct PatchHandle {
     // keep_state: (module, field) pairs of STATE fields the host wrote since the last flatten — the carry leaves those alone
     // (an explicit srack_patch_set_field / srack_voices_set_field_* on a state field wins over the running value)
     std::set<std::pair<int, int>> state_writes;
+    // The mix table of the voices (srack_voices_set_buses): NOT part of the program — setting it re-flattens nothing and restarts nothing.
+    // n_buses 0: no table.  The plan is what the bus fold reads (buses.hpp), made when the table is set; the device copy follows bus_revision.
+    uint32_t n_buses = 0;
+    std::vector<int32_t> bus;
+    std::vector<float> bus_gain;
+    BusPlan bus_plan;
+    uint64_t bus_revision = 0;
     bool timing_armed = false;      // srack_render_kernel_ms has been called: renders bracket the dominant kernel with HIP events
 
     ~PatchHandle();
@@ -51,7 +59,7 @@ int ensure_program(PatchHandle& h, uint32_t flags);
 // The program `flags` would render, without touching the handle (its own if current, else flattened from a copy into `scratch`).
 int peek_program(PatchHandle& h, uint32_t flags, FlatPair& scratch, const FlatPair** out);
 
-int device_render(PatchHandle& h, uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, uint32_t flags, void* stream);
+int device_render(PatchHandle& h, uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags, void* stream);
 int device_reserve(PatchHandle& h, uint32_t n_samples, bool want_mix, uint32_t flags);
 int device_kernel_ms(PatchHandle& h, double* avg_ms, int* n_launches, int reset);
 int device_read_rows(PatchHandle& h, int ctl_stage /* -1: the voice program */, int first_row, int n_rows, uint32_t* host_dst);
@@ -59,6 +67,7 @@ int device_read_rows(PatchHandle& h, int ctl_stage /* -1: the voice program */, 
 bool read_device_state(PatchHandle& h, int module, int field, std::vector<double>& values);
 void device_release(DeviceState* d);
 const char* device_kernel_name(const PatchHandle& h);
+std::string device_bus_note(const PatchHandle& h);  // " buses=4096[fold]" when the last render filled bus mixes, else ""
 std::string device_jit_note(const PatchHandle& h);  // " jit=compiled(1834 ms)" / " jit=disk-cache" / " jit=memory-cache" / " jit=unavailable(why)" / ""
 
 }  // namespace srack

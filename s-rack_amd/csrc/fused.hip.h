@@ -315,6 +315,13 @@ SRK_DEV void census_end(uint32_t* rec)
     rec[2] = (uint32_t)t;
     rec[3] = (uint32_t)(t >> 32);
 }
+// ... and a paced voice wave (wave.hip.h) adds to word [6]: 4 = paced, bits 3 .. 15 its pace key, bits 16 .. 23 the largest lead (either
+// way, in steps summed over the group's other waves, at most 255) it saw, bits 24 .. 31 the steps it took (at most 255)
+SRK_DEV void census_end(uint32_t* rec, const dev::Pace& p)
+{
+    if (rec && p.word) rec[6] = 1u | 4u | (p.key << 3) | ((p.max_lead < 255u ? p.max_lead : 255u) << 16) | ((p.mine < 255u ? p.mine : 255u) << 24);
+    census_end(rec);
+}
 #endif
 
 // ---- fused voice chain, envelope from a control track (P1 after uniform hoisting) ---------------------
@@ -411,16 +418,20 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
     XSaw xo;
     const bool xs = kExact && kOscAPort == OSC_OUT_SAW && xsaw_usable(sa.pos, ka.delta) && vcf_nan_free(sv);
     if (xs) xsaw_init(xo, sa.pos, ka.delta);
-    // Waves in step (notes/r07.md): the four voice waves of a SIMD run the same code for the same samples, yet under age-ordered
-    // arbitration the oldest runs ahead and the youngest finishes up to ~30 % of the launch later, alone on its SIMD for the tail.  A wave's
-    // priority falls 2 -> 1 -> 0 as it passes fixed points of the launch, so the waves behind win the issue slots until they catch up.
-    // (The control block keeps 3.)  Scalar work once per 32-sample tile.
+    // Waves in step (notes/r07.md, notes/r10.md): the four voice waves of a SIMD run the same code for the same samples, yet under age-ordered
+    // arbitration the oldest runs ahead and the youngest finishes up to ~30 % of the launch later, alone on its SIMD for the tail.  Paced
+    // (a.pace, wave.hip.h): a wave's priority follows its lead over its SIMD's other waves, measured every SRK_PACE_TILES tiles.  Not paced:
+    // the open-loop ramp, priority 2 -> 1 -> 0 as the wave passes fixed points of the launch.  (The control block keeps 3.)  Scalar work
+    // once per 32-sample tile either way; priority changes no bit of the output.
     const uint32_t prio1_at = (uint32_t)(((uint64_t)a.T * SRK_PRIO_AT1) >> 6), prio0_at = (uint32_t)(((uint64_t)a.T * SRK_PRIO_AT0) >> 6);
+    Pace pace = pace_join(a.pace, lane);
     __builtin_amdgcn_s_setprio(2);
     for (uint32_t t0 = 0; t0 < a.T; t0 += kMixRows) {
         const int n = (int)min((uint32_t)kMixRows, a.T - t0);
-        if (t0 >= prio1_at && t0 < prio1_at + kMixRows) __builtin_amdgcn_s_setprio(1);
-        if (t0 >= prio0_at && t0 < prio0_at + kMixRows) __builtin_amdgcn_s_setprio(0);
+        if (!pace.word) {
+            if (t0 >= prio1_at && t0 < prio1_at + kMixRows) __builtin_amdgcn_s_setprio(1);
+            if (t0 >= prio0_at && t0 < prio0_at + kMixRows) __builtin_amdgcn_s_setprio(0);
+        }
         if (xs) {
             xsaw_tile(xo, mix_tile + lane, kMixPitch, n);
             auto sample_x = [&](int i, float xin) {
@@ -433,6 +444,8 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
                 emit_put<kOut>(em, mix_tile, o, i, V);
             };
             if (n == kMixRows) {  // eight rows of the tile in flight per LDS round trip; a row is read before its output overwrites it
+                uint32_t pace_seen;
+                const bool pace_now = pace_step(pace, t0 / kMixRows, lane, pace_seen);
 #pragma unroll
                 for (int i0 = 0; i0 < kMixRows; i0 += 8) {
                     float xin[8];
@@ -441,6 +454,7 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
 #pragma unroll
                     for (int u = 0; u < 8; u++) sample_x(i0 + u, xin[u]);
                 }
+                if (pace_now) pace_apply(pace, pace_seen);
             } else {
                 for (int i = 0; i < n; i++) sample_x(i, mix_tile[i * kMixPitch + lane]);
             }
@@ -472,8 +486,13 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
             emit_put<kOut>(em, mix_tile, o, i, V);
         };
         if (n == kMixRows) {  // constant trip count: unrollable (readlane is convergent, so a runtime count is not)
+            // pacing: the step's atomic before the tile's samples, its value looked at after them — in this block alone, so that the value
+            // is neither waited for behind the frame stores in flight nor alive anywhere else in the loop
+            uint32_t pace_seen;
+            const bool pace_now = pace_step(pace, t0 / kMixRows, lane, pace_seen);
 #pragma unroll 32
             for (int i = 0; i < kMixRows; i++) sample(i);
+            if (pace_now) pace_apply(pace, pace_seen);
         } else {
             for (int i = 0; i < n; i++) sample(i);
         }
@@ -505,7 +524,7 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
         put(s0 + VCF_S_RES, __float_as_uint(sv.res));
     }
 #ifdef SRK_WAVE_CENSUS
-    census_end(crec);
+    census_end(crec, pace);
 #endif
 }
 

@@ -39,6 +39,9 @@ struct KernelArgs {
         // statistics output mode (wave.hip.h, kOutStats).  (Sharing the slot keeps the block's layout, and with it every other kernel's code.)
         double* stats;
     };
+    // render_voice_chain_track: this launch's slice of the pacing table (wave.hip.h, kPaceKeys words, cleared by the host), or null: the
+    // voice waves keep the open-loop priority ramp
+    uint32_t* pace;
 };
 
 struct ChainRoles {  // op indices of the fused voice chain (osc_l / adsr unused in the track variant)

@@ -47,7 +47,9 @@ namespace srack {
 // Tuning knobs of tools/ (not part of the interface): read once per process and clamped to values the schedule can run with.
 struct Knobs {
     uint32_t want_waves = 1024;  // waves to aim for when there are few voices (one per SIMD)
-    uint32_t chunk_max = 4096;   // samples per launch; measured on the headline workload: 4096 -> 13.98, 8192 -> 14.14, 16384 -> 14.8 ms per step
+    uint32_t chunk_max = 4096;   // samples per launch; re-measured on the headline workload with the voice waves paced (notes/r10.md, three rounds, one box):
+                                 // 4096 -> 10.08 / 10.08 / 10.11, 8192 -> 10.07 / 10.07 / 10.05, 16384 -> 10.13 / 10.12 / 10.12 ms per step: flat within the
+                                 // rounds' own spread up to 8192, 16384 still 0.4 % behind (before the waves were kept in step: 13.98 / 14.14 / 14.8)
     uint32_t chunk_first = 1024; // samples of the first chunks of a render with a control program (the control work for them is exposed)
     bool debug_occ = false;
     int high_prio_ctl = 1;       // the control stream is created with the highest priority (its own pool of hardware queues)
@@ -61,6 +63,7 @@ struct Knobs {
     int mix_aside = 0;                // 1: the mix partials of chunk k are summed on a side stream while chunk k + 1 renders.  Measured (round 4, one box,
                                       // three alternating rounds): config 3 11.52 / 11.54 / 11.57 ms per step all at once at the end, 11.62 / 11.67 / 11.69 aside;
                                       // cfg3_poly 16.40 against 16.43 — at the power cap a kernel that runs beside the voices is paid for in clock
+    int pace = 1;                     // the flagship's voice waves pace themselves against their SIMD's other waves (wave.hip.h, notes/r10.md); 0: the open-loop priority ramp
     int tick = 2;                     // calls keep the control program running ahead across calls (TickSession below); 1: calls of one chunk only (round 3); 0: every call starts it afresh
 };
 static const Knobs& knobs()
@@ -87,6 +90,7 @@ static const Knobs& knobs()
         v.fm_block_min = (uint32_t)num("SRACK_FM_BLOCK_MIN", 1, 65536, 4096);
         v.tick = (int)num("SRACK_TICK", 0, 2, 2);
         v.mix_aside = (int)num("SRACK_MIX_ASIDE", 0, 1, 0);
+        v.pace = (int)num("SRACK_PACE", 0, 1, 1);
         return v;
     }();
     return k;
@@ -147,6 +151,7 @@ struct TickSession {
     uint64_t slots_base = 0;           // argument blocks of the carried launches of calls [slots_base, slots_base + slots_n) are on the device
     uint32_t slots_n = 0;
 };
+constexpr uint32_t kPaceSlices = 16;
 constexpr uint32_t kTickBatch = 256, kTickFirstBatch = 8;  // (a session that the very next call ends should not have uploaded much)
 
 struct DeviceState {
@@ -167,6 +172,9 @@ struct DeviceState {
     size_t mixgroup_bytes = 0;
     float* d_tracks = nullptr;
     size_t tracks_bytes = 0;
+    // pacing table of render_voice_chain_track (wave.hip.h): kPaceSlices slices of kPaceKeys words, launch k of a call uses slice
+    // k % kPaceSlices; one memset per call clears the slices the call will use (a call of more launches clears again each time round)
+    uint32_t* d_pace = nullptr;
     float* d_stat_frames = nullptr;  // frames of one launch for stats_fold / the bus fold when the host asked for statistics or bus mixes without frames
     size_t stat_frames_bytes = 0;
     // mix buses: the handle's bus plan (buses.hpp) as one block of words on the device — gain, order, tile_seg, seg_end, seg_dst, bus_first,
@@ -198,6 +206,7 @@ void device_release(DeviceState* d)
     (void)hipFree(d->d_mixpart);
     (void)hipFree(d->d_mixgroup);
     (void)hipFree(d->d_tracks);
+    (void)hipFree(d->d_pace);
     (void)hipFree(d->d_stat_frames);
     (void)hipFree(d->d_bus_tab);
     (void)hipFree(d->d_bus_part);
@@ -1396,9 +1405,16 @@ struct Segment {
                 d->ev_mix.push_back(e);
             }
         }
+        const bool paced = fused && track && !special && knobs().pace;
+        if (paced && !d->d_pace) HIP_TRY(hipMalloc(&d->d_pace, sizeof(uint32_t) * dev::kPaceKeys * kPaceSlices));
         for (uint32_t k = 0; k < n_chunks; k++) {
             const uint32_t t_off = chunks[k].first, len = chunks[k].second;
             KernelArgs ka{};
+            if (paced) {
+                if (k % kPaceSlices == 0)
+                    HIP_TRY(hipMemsetAsync(d->d_pace, 0, sizeof(uint32_t) * dev::kPaceKeys * std::min(kPaceSlices, n_chunks - k), st));
+                ka.pace = d->d_pace + (size_t)(k % kPaceSlices) * dev::kPaceKeys;
+            }
             ka.ops = d->voice.d_ops;
             ka.prog = P.hdr;
             ka.table = d->voice.d_table;

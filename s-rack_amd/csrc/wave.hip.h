@@ -60,6 +60,83 @@ SRK_DEV WaveMap wave_map(const Args& a, int lane)
     return m;
 }
 
+// ---- pacing: the voice waves of one SIMD kept in step (notes/r10.md) -------------------------------------------------
+// A SIMD's voice waves run the same code for the same samples, yet the oldest wins arbitration and the youngest runs its tail alone.
+// Every SRK_PACE_TILES tiles a wave adds 1 to its SIMD's word of KernelArgs::pace — one returning atomic from one lane, which publishes
+// its step and reads the group's total — and, a tile's samples later, sets its issue priority by its lead over the group's other waves:
+// ahead 0, behind 2, else 1.
+// Nothing ever waits: no loop on the table, no sleep, no barrier; a wrong key or a stale total only paces worse.  The word packs the
+// members that joined (bits 24 .. 31) and the sum of their steps (bits 0 .. 23); the host clears the launch's slice (render.hip).
+#ifndef SRK_PACE_TILES
+#define SRK_PACE_TILES 4  // tiles (of 32 samples) between two steps
+#endif
+#ifndef SRK_PACE_LEAD
+#define SRK_PACE_LEAD 1   // dead band: mean lead over the group's other waves, in steps
+#endif
+constexpr uint32_t kPaceKeys = 8192;  // XCC (3 bits), then HW_ID's SE / SH / CU (8 bits), then the SIMD (2): tools/wave_census.py's simd_key
+constexpr uint32_t kPaceMember = 1u << 24;
+
+struct Pace {
+    uint32_t* word;    // this wave's group (null: not paced)
+    uint32_t mine;     // steps this wave has published
+#ifdef SRK_WAVE_CENSUS
+    uint32_t key, max_lead;
+#endif
+};
+
+SRK_DEV uint32_t pace_key()
+{
+    const uint32_t hw = (uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID: wave 3:0, SIMD 5:4, pipe 7:6, CU 11:8, SH 12, SE 15:13
+    const uint32_t xcc = (uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 20);  // HW_REG_XCC_ID
+    return ((xcc & 7u) << 10) | (((hw >> 8) & 0xffu) << 2) | ((hw >> 4) & 3u);
+}
+
+// At entry: join the group.  `slice` = this launch's kPaceKeys words, or null.
+SRK_DEV Pace pace_join(uint32_t* slice, int lane)
+{
+    Pace p{};
+    if (!slice) return p;
+    const uint32_t key = pace_key();
+    p.word = slice + key;
+    if (lane == 0) atomicAdd(p.word, kPaceMember);
+#ifdef SRK_WAVE_CENSUS
+    p.key = key;
+#endif
+    return p;
+}
+
+// Before the samples of a FULL tile, `tile` its index in the launch: SRK_PACE_TILES more tiles done => publish a step (a launch shorter
+// than that takes none).  Returns whether it did; `seen` (lane 0) is what the atomic returned, for pace_apply after the tile's samples
+// in the same block of code: the frame stores share the vector-memory counter, so a value consumed at once would wait behind the
+// stores in flight, and a value alive at the loop's end would make every tile wait for all of them.
+SRK_DEV bool pace_step(Pace& p, uint32_t tile, int lane, uint32_t& seen)
+{
+    seen = 0u;
+    if (!p.word || tile == 0u || tile % SRK_PACE_TILES != 0u) return false;
+    p.mine++;
+    if (lane == 0) seen = atomicAdd(p.word, 1u);
+    return true;
+}
+
+// The priority that `seen` asks for: by this wave's lead over its group's other waves (wave-uniform scalar arithmetic)
+SRK_DEV void pace_apply(Pace& p, uint32_t seen)
+{
+    const uint32_t got = (uint32_t)__builtin_amdgcn_readfirstlane((int)seen);
+    const int n = (int)(got >> 24);
+    const int lead = n * (int)p.mine - (int)((got & (kPaceMember - 1u)) + 1u);  // my own step was not yet in `got`
+    const int band = SRK_PACE_LEAD * (n > 2 ? n - 1 : 1);
+    if (lead >= band)
+        __builtin_amdgcn_s_setprio(0);
+    else if (lead <= -band)
+        __builtin_amdgcn_s_setprio(2);
+    else
+        __builtin_amdgcn_s_setprio(1);
+#ifdef SRK_WAVE_CENSUS
+    const uint32_t al = (uint32_t)(lead < 0 ? -lead : lead);
+    p.max_lead = al > p.max_lead ? al : p.max_lead;
+#endif
+}
+
 }  // namespace dev
 
 constexpr int kMixRows = 32;

@@ -12,7 +12,9 @@ recorded, and reports per launch and over the call's full-length launches:
   * voice waves per SIMD (over the launch, and the most resident at one time),
   * the spread of the SIMDs' last end times and the spread of end times within a SIMD, in % of the launch,
   * when the control block ends, relative to the launch and to the last voice wave,
-  * wave lifetime / launch length (the counters' SQ_WAVE_CYCLES x 4 / SQ_WAVES over GRBM_GUI_ACTIVE / 8: 0.771 in profiles/r06_summary.json).
+  * wave lifetime / launch length (the counters' SQ_WAVE_CYCLES x 4 / SQ_WAVES over GRBM_GUI_ACTIVE / 8: 0.771 in profiles/r06_summary.json),
+  * the pacing groups (wave.hip.h pace_key: a SIMD's voice waves): how many keys have exactly four members, and — a paced launch records
+    them — the steps each wave took and the largest lead any wave saw.
 """
 import argparse
 import ctypes as C
@@ -49,6 +51,35 @@ def load_variant(lib_path):
 
 def pct(x, span):
     return round(100.0 * float(x) / span, 2)
+
+
+def pace_key(hw, xcc):
+    """wave.hip.h pace_key: XCC (3 bits), HW_ID's CU / SH / SE bits 8 .. 15, the SIMD — not the pipe, not the wave slot."""
+    hw, xcc = np.asarray(hw, np.int64), np.asarray(xcc, np.int64)
+    return ((xcc & 7) << 10) | (((hw >> 8) & 0xFF) << 2) | ((hw >> 4) & 3)
+
+
+def pace_groups(rec):
+    """The pacing groups of one launch's records: the voice waves by pace key.  Word [6] of a paced wave: 4 = paced, bits 3 .. 15 the key
+    the wave used, bits 16 .. 23 the largest lead it saw (steps summed over the group's other waves), bits 24 .. 31 the steps it took."""
+    rec = np.asarray(rec, np.uint32).reshape(-1, 8)
+    flags = rec[:, 6]
+    voice = ((flags & 1) != 0) & ((flags & 2) == 0)
+    if not voice.any():
+        return None
+    key = pace_key(rec[:, 4], rec[:, 5])
+    members = Counter(int(k) for k in key[voice])
+    sizes = Counter(members.values())
+    out = {"keys": len(members), "keys_with_four": int(sizes.get(4, 0)), "members_per_key": {str(k): v for k, v in sorted(sizes.items())}}
+    paced = voice & ((flags & 4) != 0)
+    out["paced_waves"] = int(paced.sum())
+    if paced.any():
+        f = flags[paced].astype(np.int64)
+        out["key_mismatches"] = int((((f >> 3) & 0x1FFF) != key[paced]).sum())   # the key the wave used against the decode of its HW_ID here
+        out["largest_lead"] = int(((f >> 16) & 0xFF).max())
+        steps = (f >> 24) & 0xFF
+        out["steps"] = {"min": int(steps.min()), "max": int(steps.max())}
+    return out
 
 
 def analyse(rec):
@@ -109,6 +140,7 @@ def analyse(rec):
         out["control"] = {"start_pct": pct(t0[i] - begin, span), "end_pct": pct(t1[i] - begin, span),
                           "end_minus_last_voice_pct": pct(t1[i] - t1[voice].max(), span), "xcc": int(xcc[i]), "simd": int(simd[i]),
                           "voice_waves_on_its_simd": len(per_simd.get(int(simd_key[i]), []))}
+    out["pace"] = pace_groups(rec)
     return out
 
 
@@ -192,7 +224,8 @@ def main():
         if x and "span_ticks_10ns" in x:
             print(f"launch {k:2d}: {x['span_ticks_10ns'] / 1e5:.3f} ms  waves/SIMD {x['waves_per_simd']}  peak {x['peak_resident_per_simd']}  "
                   f"life/launch {x['voice_lifetime_over_launch']:.3f}  SIMD last-end spread {x['simd_last_end_spread_pct']} %  "
-                  f"within-SIMD max {x['end_spread_within_simd_pct']['max']} %  ctl end {x.get('control', {}).get('end_pct')} %")
+                  f"within-SIMD max {x['end_spread_within_simd_pct']['max']} %  ctl end {x.get('control', {}).get('end_pct')} %  "
+                  f"pace keys with four {x['pace']['keys_with_four']} / {x['pace']['keys']}  largest lead {x['pace'].get('largest_lead')}")
         else:
             print(f"launch {k:2d}: {x}")
 

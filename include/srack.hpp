@@ -155,6 +155,22 @@ public:
     // one mix per bus.  The table is not part of the program: changing it between execute_batch calls restarts nothing.
     void set_buses(uint32_t n_buses, const int* bus = nullptr, const float* gain = nullptr) { check(srack_voices_set_buses(p_, n_buses, bus, gain)); }
     uint32_t get_buses(int* bus = nullptr, float* gain = nullptr, uint32_t cap = 0) const { return (uint32_t)check(srack_voices_get_buses(p_, bus, gain, cap)); }
+    // A wave per voice for a SampleModule: a bank of n_waves waves back to back (lengths, rates; copied) and, per voice, an index into it
+    // or SRACK_WAVE_OWN (the module's own wave).  Voice v plays what a one-voice patch plays after set_wave(bank wave wave[v], its rate).
+    void set_wave_bank(const SharedSynthModule& m, const float* samples, const int* lengths, const float* sample_rates, uint32_t n_waves)
+    {
+        check(srack_patch_set_wave_bank(p_, m.index(), samples, lengths, sample_rates, n_waves));
+    }
+    uint32_t get_wave_bank(const SharedSynthModule& m, int* lengths = nullptr, float* sample_rates = nullptr, uint32_t cap = 0) const
+    {
+        return (uint32_t)check(srack_patch_get_wave_bank(p_, m.index(), lengths, sample_rates, cap));
+    }
+    uint32_t get_wave_bank_samples(const SharedSynthModule& m, int wave, float* samples = nullptr, uint32_t cap = 0) const
+    {
+        return (uint32_t)check(srack_patch_get_wave_bank_samples(p_, m.index(), wave, samples, cap));
+    }
+    void set_voice_waves(const SharedSynthModule& m, const int* wave) { check(srack_voices_set_waves(p_, m.index(), wave)); }  // nullptr clears
+    uint32_t get_voice_waves(const SharedSynthModule& m, int* wave = nullptr, uint32_t cap = 0) const { return (uint32_t)check(srack_voices_get_waves(p_, m.index(), wave, cap)); }
     // execute_batch plus d_bus_mix, f32 [n_buses][channels][n_samples] (written); d_frames, d_mix, d_stats may each be null
     void execute_batch_buses(uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags = 0, void* stream = nullptr)
     {

@@ -313,6 +313,31 @@ int srack_voices_configure(srack_patch* p, uint32_t n_voices);
 int srack_voices_set_field_f32(srack_patch* p, int module, int field, const float* values);
 int srack_voices_set_field_f64(srack_patch* p, int module, int field, const double* values);
 
+/* ---- a wave bank: every voice of a SampleModule its own recording --------------------------- */
+/* The bank: `n_waves` waves laid back to back in `samples`; wave k has lengths[k] >= 0 samples (0: the reference's empty wave, which
+ * plays 0.0) and the rate sample_rates[k].  Copied; any f32 is accepted.  n_waves == 0 removes the bank (pointers may be NULL).  A bank
+ * does nothing until voices are assigned to it: the module's own wave (srack_patch_set_wave) and SRACK_SAMPLE_WAVE_SAMPLE_RATE stay as
+ * they are, and a patch with a bank and no assignment renders the same bits through the same kernel as without one.  Setting a bank
+ * drops the module's voice assignment (the voices play the own wave again, as after a srack_patch_set_wave of it).
+ * get_wave_bank copies up to `cap` lengths and rates (either may be NULL) and returns n_waves; get_wave_bank_samples copies up to `cap`
+ * samples of one wave and returns that wave's length.
+ * The assignment: wave[v] in [0, n_waves), or SRACK_WAVE_OWN: that voice plays the module's own wave at the rate of the field (or its
+ * per-voice override), exactly as without a bank.  A voice with wave[v] >= 0 renders what a one-voice patch renders after
+ * srack_patch_set_wave(bank wave wave[v], its rate): the bank's rate replaces wave_sample_rate, and a per-voice override of that field
+ * applies to the SRACK_WAVE_OWN voices only.  `wave` has n_voices entries; NULL clears the assignment.  A bad index (outside
+ * [-1, n_waves), or >= 0 without a bank) is SRACK_ERR_INVALID and leaves the earlier assignment in place.
+ * Changing the assignment loads a wave (WaveBox::load: new = true): the patch is re-flattened and the next render starts every voice
+ * of that player at pos = 0, playing = false — also under srack_patch_keep_state, where everything else carries over.
+ * srack_voices_configure drops assignments.  Rack files carry neither bank nor assignment (no counterpart in the reference).  A sharded
+ * host sets the same bank on every rank and each rank's own voices' indices.
+ * get_waves copies up to `cap` entries and returns n_voices, or 0 when no assignment is set. */
+#define SRACK_WAVE_OWN (-1)
+int srack_patch_set_wave_bank(srack_patch* p, int module, const float* samples, const int* lengths, const float* sample_rates, uint32_t n_waves);
+int srack_patch_get_wave_bank(const srack_patch* p, int module, int* lengths, float* sample_rates, uint32_t cap);
+int srack_patch_get_wave_bank_samples(const srack_patch* p, int module, int wave, float* samples, uint32_t cap);
+int srack_voices_set_waves(srack_patch* p, int module, const int* wave);
+int srack_voices_get_waves(const srack_patch* p, int module, int* wave, uint32_t cap);
+
 /* ---- render (needs the GPU) ---------------------------------------------------------------- */
 /* Number of distinct wires feeding the OutputModule's channels and, per channel, which plane of
  * `d_frames` it is (-1 = unconnected => silence).  P1/P2 wire both channels to one source => 1 plane. */

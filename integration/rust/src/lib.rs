@@ -58,6 +58,11 @@ mod ffi {
         pub fn srack_render_stats(p: *mut SrackPatch, n_samples: u32, d_frames: *mut f32, d_mix: *mut f32, d_stats: *mut f64, flags: u32, stream: *mut c_void) -> c_int;
         pub fn srack_voices_set_buses(p: *mut SrackPatch, n_buses: u32, bus: *const c_int, gain: *const f32) -> c_int;
         pub fn srack_voices_get_buses(p: *const SrackPatch, bus: *mut c_int, gain: *mut f32, cap: u32) -> c_int;
+        pub fn srack_patch_set_wave_bank(p: *mut SrackPatch, module: c_int, samples: *const f32, lengths: *const c_int, sample_rates: *const f32, n_waves: u32) -> c_int;
+        pub fn srack_patch_get_wave_bank(p: *const SrackPatch, module: c_int, lengths: *mut c_int, sample_rates: *mut f32, cap: u32) -> c_int;
+        pub fn srack_patch_get_wave_bank_samples(p: *const SrackPatch, module: c_int, wave: c_int, samples: *mut f32, cap: u32) -> c_int;
+        pub fn srack_voices_set_waves(p: *mut SrackPatch, module: c_int, wave: *const c_int) -> c_int;
+        pub fn srack_voices_get_waves(p: *const SrackPatch, module: c_int, wave: *mut c_int, cap: u32) -> c_int;
         pub fn srack_render_buses(p: *mut SrackPatch, n_samples: u32, d_frames: *mut f32, d_mix: *mut f32, d_stats: *mut f64, d_bus_mix: *mut f32, flags: u32, stream: *mut c_void) -> c_int;
         pub fn srack_device_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
         pub fn srack_device_free(d_ptr: *mut c_void) -> c_int;
@@ -90,6 +95,8 @@ pub mod stat {
 /// Mix buses (`SRACK_MAX_BUSES`, `SRACK_BUS_NONE`).
 pub const MAX_BUSES: u32 = 65536;
 pub const BUS_NONE: i32 = -1;
+/// A voice that plays its SampleModule's own wave, not one of the bank (`SRACK_WAVE_OWN`).
+pub const WAVE_OWN: i32 = -1;
 
 /// Render flags (values of `SRACK_RENDER_*`).
 pub mod render_flags {
@@ -288,6 +295,38 @@ impl Patch {
         let (mut b, mut g) = (vec![0 as c_int; n_voices], vec![0f32; n_voices]);
         let n = check(unsafe { ffi::srack_voices_get_buses(self.raw, b.as_mut_ptr(), g.as_mut_ptr(), n_voices as u32) })?;
         Ok((n as u32, b, g))
+    }
+    /// A bank of waves for a SampleModule, laid back to back in `samples`: wave k has `lengths[k]` samples and the rate `sample_rates[k]`
+    /// (`srack_patch_set_wave_bank`; an empty bank removes it).  Inert until `set_voice_waves` assigns voices to it.
+    pub fn set_wave_bank(&mut self, module: i32, samples: &[f32], lengths: &[i32], sample_rates: &[f32]) -> Result<(), Error> {
+        assert!(lengths.len() == sample_rates.len() && lengths.iter().map(|&n| n.max(0) as usize).sum::<usize>() <= samples.len());
+        check(unsafe { ffi::srack_patch_set_wave_bank(self.raw, module, samples.as_ptr(), lengths.as_ptr() as *const c_int, sample_rates.as_ptr(), lengths.len() as u32) }).map(|_| ())
+    }
+    /// `(lengths, sample_rates)` of the bank; empty without one.
+    pub fn get_wave_bank(&self, module: i32) -> Result<(Vec<i32>, Vec<f32>), Error> {
+        let n = check(unsafe { ffi::srack_patch_get_wave_bank(self.raw, module, std::ptr::null_mut(), std::ptr::null_mut(), 0) })? as usize;
+        let (mut l, mut r) = (vec![0 as c_int; n], vec![0f32; n]);
+        check(unsafe { ffi::srack_patch_get_wave_bank(self.raw, module, l.as_mut_ptr(), r.as_mut_ptr(), n as u32) })?;
+        Ok((l, r))
+    }
+    /// The samples of one wave of the bank.
+    pub fn get_wave_bank_samples(&self, module: i32, wave: i32) -> Result<Vec<f32>, Error> {
+        let n = check(unsafe { ffi::srack_patch_get_wave_bank_samples(self.raw, module, wave, std::ptr::null_mut(), 0) })? as usize;
+        let mut s = vec![0f32; n];
+        check(unsafe { ffi::srack_patch_get_wave_bank_samples(self.raw, module, wave, s.as_mut_ptr(), n as u32) })?;
+        Ok(s)
+    }
+    /// Which wave of the bank every voice plays: `wave[v]` in `0 .. n_waves` or `WAVE_OWN` (the module's own wave); None clears.  Voice v
+    /// renders what a one-voice patch renders after `set_wave(bank wave wave[v], its rate)` (`srack_voices_set_waves`).
+    pub fn set_voice_waves(&mut self, module: i32, wave: Option<&[i32]>) -> Result<(), Error> {
+        let w = wave.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        check(unsafe { ffi::srack_voices_set_waves(self.raw, module, w) }).map(|_| ())
+    }
+    /// The assignment, `n_voices` entries; None when none is set.
+    pub fn get_voice_waves(&self, module: i32, n_voices: usize) -> Result<Option<Vec<i32>>, Error> {
+        let mut w = vec![0 as c_int; n_voices];
+        let n = check(unsafe { ffi::srack_voices_get_waves(self.raw, module, w.as_mut_ptr(), n_voices as u32) })?;
+        Ok(if n == 0 { None } else { Some(w) })
     }
     /// `execute_batch` plus one weighted mix per bus: `bus_mix` is `[n_buses][channels][n_samples]` f32, written by the call
     /// (`srack_render_buses`); frames, mix and statistics may each be None.

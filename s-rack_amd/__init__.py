@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libsrack_hip.so")
 
 OK, ERR_INVALID, ERR_PORT, ERR_NO_OUTPUT, ERR_SELF_LOOP, ERR_STATE, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8
 MAX_BUSES, BUS_NONE = 65536, -1
+WAVE_OWN = -1
 STAT_SUM, STAT_SUM_SQ, STAT_PEAK_POS, STAT_PEAK_NEG, STAT_NONFINITE, STAT_CLIPPED, STAT_COUNT = 0, 1, 2, 3, 4, 5, 6
 RENDER_DEFAULT, RENDER_EXACT_OSC, RENDER_NO_FUSION, RENDER_NO_UNIFORM_HOIST, RENDER_NO_CTL_STAGES, RENDER_NO_SPECIALIZE, RENDER_SPECIALIZE, RENDER_KEEP_DEFAULT = 0, 1, 2, 4, 8, 16, 32, 64
 
@@ -30,6 +31,7 @@ ABI_SYMBOLS = [
     "srack_patch_plan", "srack_patch_plan_list", "srack_patch_removed_edges", "srack_patch_delayed_edges",
     "srack_voices_configure", "srack_voices_set_field_f32", "srack_voices_set_field_f64", "srack_render_planes", "srack_render", "srack_render_stats", "srack_render_reserve",
     "srack_voices_set_buses", "srack_voices_get_buses", "srack_voices_bus_plan", "srack_render_buses",
+    "srack_patch_set_wave_bank", "srack_patch_get_wave_bank", "srack_patch_get_wave_bank_samples", "srack_voices_set_waves", "srack_voices_get_waves",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
     "srack_device_alloc", "srack_device_free", "srack_device_to_host", "srack_device_from_host", "srack_device_sync",
     "srack_dist_unique_id", "srack_dist_init", "srack_dist_comm_count", "srack_dist_destroy", "srack_dist_reduce_mix",
@@ -99,6 +101,12 @@ def _load():
         L.srack_voices_get_buses.argtypes = [vp, ip, fp, u32]
         L.srack_voices_bus_plan.argtypes = [vp, ip, u32, ip, u32]
         L.srack_render_buses.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp]
+    if hasattr(L, "srack_voices_set_waves"):  # (tools/ alternate older builds of the library under this binding)
+        L.srack_patch_set_wave_bank.argtypes = [vp, i32, fp, ip, fp, u32]
+        L.srack_patch_get_wave_bank.argtypes = [vp, i32, ip, fp, u32]
+        L.srack_patch_get_wave_bank_samples.argtypes = [vp, i32, i32, fp, u32]
+        L.srack_voices_set_waves.argtypes = [vp, i32, ip]
+        L.srack_voices_get_waves.argtypes = [vp, i32, ip, u32]
     L.srack_render_reserve.argtypes = [vp, u32, i32, u32]
     L.srack_render_info.argtypes = [vp, C.c_char_p, sz]
     L.srack_render_kernel_ms.argtypes = [vp, dp, ip, i32]
@@ -307,6 +315,47 @@ class Patch:
         a = np.zeros(n, dtype=np.float32)
         _check(lib.srack_patch_get_wave(self.h, module, a.ctypes.data_as(C.POINTER(C.c_float)), n, C.byref(sr)))
         return a, sr.value
+
+    def set_wave_bank(self, module, waves, rates):
+        """A bank of waves for a SampleModule (srack_patch_set_wave_bank): `waves` a list of f32 arrays (any lengths, 0 included), `rates`
+        their sample rates.  An empty list removes the bank.  Inert until set_voice_waves assigns voices to it."""
+        waves = [np.ascontiguousarray(w, dtype=np.float32).ravel() for w in waves]
+        assert len(waves) == len(rates)
+        flat = np.concatenate(waves) if waves else np.zeros(0, dtype=np.float32)
+        lengths = np.array([w.size for w in waves], dtype=np.intc)
+        sr = np.ascontiguousarray(rates, dtype=np.float32)
+        _check(lib.srack_patch_set_wave_bank(self.h, module, flat.ctypes.data_as(C.POINTER(C.c_float)), lengths.ctypes.data_as(C.POINTER(C.c_int)),
+                                             sr.ctypes.data_as(C.POINTER(C.c_float)), len(waves)))
+
+    def get_wave_bank(self, module):
+        """-> (list of f32 arrays, f32 array of rates); ([], empty) without a bank"""
+        n = _check(lib.srack_patch_get_wave_bank(self.h, module, None, None, 0))
+        lengths, sr = np.zeros(n, dtype=np.intc), np.zeros(n, dtype=np.float32)
+        _check(lib.srack_patch_get_wave_bank(self.h, module, lengths.ctypes.data_as(C.POINTER(C.c_int)), sr.ctypes.data_as(C.POINTER(C.c_float)), n))
+        waves = []
+        for k in range(n):
+            a = np.zeros(int(lengths[k]), dtype=np.float32)
+            _check(lib.srack_patch_get_wave_bank_samples(self.h, module, k, a.ctypes.data_as(C.POINTER(C.c_float)), a.size))
+            waves.append(a)
+        return waves, sr
+
+    def set_voice_waves(self, module, idx):
+        """Which wave of the bank every voice plays (srack_voices_set_waves): idx[v] in [0, n_waves) or WAVE_OWN; None clears."""
+        if idx is None:
+            _check(lib.srack_voices_set_waves(self.h, module, None))
+            return
+        a = np.ascontiguousarray(idx, dtype=np.intc)
+        assert a.shape == (self.n_voices,), a.shape
+        _check(lib.srack_voices_set_waves(self.h, module, a.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def get_voice_waves(self, module):
+        """-> int32 [V], or None when no assignment is set"""
+        n = _check(lib.srack_voices_get_waves(self.h, module, None, 0))
+        if n == 0:
+            return None
+        a = np.empty(n, dtype=np.intc)
+        _check(lib.srack_voices_get_waves(self.h, module, a.ctypes.data_as(C.POINTER(C.c_int)), n))
+        return a
 
     def connect(self, src, src_port, sink, sink_port):
         _check(lib.srack_patch_connect(self.h, src, src_port, sink, sink_port))

@@ -345,6 +345,8 @@ struct Analysis {
         case SRACK_MOD_SAMPLE: {
             double w = 0.0;
             for (float x : mod.wave) w = std::max(w, (double)std::fabs(x));
+            if (!mod.voice_wave.empty() && mod.bank)  // voices play waves of the bank: the loudest sample of any of them
+                for (float x : *mod.bank) w = std::max(w, (double)std::fabs(x));
             o = {std::isfinite(w) ? w : kInf};
             mv = {(uint32_t)(kJumpAudio | kJumpNoise)};  // (whatever was recorded)
             break;

@@ -261,6 +261,87 @@ int srack_patch_get_wave(const srack_patch* p, int module, float* samples, uint3
     });
 }
 
+int srack_patch_set_wave_bank(srack_patch* p, int module, const float* samples, const int* lengths, const float* sample_rates, uint32_t n_waves)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        const int rc = p->h.graph.set_wave_bank(module, samples, lengths, sample_rates, n_waves);
+        if (rc == SRACK_OK) p->h.voices_revision++;  // (the assignment, if there was one, is gone)
+        return rc;
+    });
+}
+
+static const Module* get_player(const srack_patch* p, int module, const char* who)
+{
+    const Module* m = get_module(p, module);
+    if (!m || m->type != SRACK_MOD_SAMPLE) {
+        set_error(std::string(who) + ": not a SampleModule");
+        return nullptr;
+    }
+    return m;
+}
+
+int srack_patch_get_wave_bank(const srack_patch* p, int module, int* lengths, float* sample_rates, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        const Module* m = get_player(p, module, "get_wave_bank");
+        if (!m) return SRACK_ERR_INVALID;
+        for (size_t k = 0; k < m->bank_len.size() && k < (size_t)cap; k++) {
+            if (lengths) lengths[k] = m->bank_len[k];
+            if (sample_rates) sample_rates[k] = m->bank_sr[k];
+        }
+        return (int)m->bank_len.size();
+    });
+}
+
+int srack_patch_get_wave_bank_samples(const srack_patch* p, int module, int wave, float* samples, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        const Module* m = get_player(p, module, "get_wave_bank_samples");
+        if (!m) return SRACK_ERR_INVALID;
+        if (wave < 0 || wave >= (int)m->bank_len.size()) {
+            set_error("get_wave_bank_samples: no such wave");
+            return SRACK_ERR_INVALID;
+        }
+        size_t first = 0;
+        for (int k = 0; k < wave; k++) first += (size_t)m->bank_len[(size_t)k];
+        const size_t n = (size_t)m->bank_len[(size_t)wave];
+        if (samples)
+            for (size_t i = 0; i < n && i < (size_t)cap; i++) samples[i] = (*m->bank)[first + i];
+        return (int)n;
+    });
+}
+
+int srack_voices_set_waves(srack_patch* p, int module, const int* wave)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        PatchHandle& h = p->h;
+        if (!get_player(p, module, "voices_set_waves")) return SRACK_ERR_INVALID;
+        if (h.n_voices == 0) {
+            set_error("voices_set_waves: call srack_voices_configure first");
+            return SRACK_ERR_STATE;
+        }
+        const int rc = h.graph.set_voice_waves(module, wave, h.n_voices);
+        if (rc == SRACK_OK) h.voices_revision++;
+        return rc;
+    });
+}
+
+int srack_voices_get_waves(const srack_patch* p, int module, int* wave, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        const Module* m = get_player(p, module, "voices_get_waves");
+        if (!m) return SRACK_ERR_INVALID;
+        if (wave)
+            for (size_t v = 0; v < m->voice_wave.size() && v < (size_t)cap; v++) wave[v] = m->voice_wave[v];
+        return (int)m->voice_wave.size();
+    });
+}
+
 int srack_patch_load_srk(const void* bytes, size_t n_bytes, uint32_t sample_rate, uint32_t buffer_size, uint32_t channels, srack_patch** out)
 {
     return guarded([&]() -> int {
@@ -519,6 +600,7 @@ int srack_voices_configure(srack_patch* p, uint32_t n_voices)
         }
         p->h.n_voices = n_voices;
         p->h.overrides.clear();
+        p->h.graph.drop_voice_waves();  // (no revision of the graph: voices_revision below re-flattens)
         p->h.voices_revision++;
         p->h.voices_fresh = true;
         p->h.n_buses = 0;  // the mix table belonged to the voices that were
@@ -700,6 +782,7 @@ int srack_render_info(srack_patch* p, char* buf, size_t cap)
         const char* k = device_kernel_name(p->h);
         // (the kernel's name stays LAST: hosts and tests read it with split("kernel="))
         s += device_bus_note(p->h);
+        s += device_waves_note(p->h);
         s += device_jit_note(p->h);
         if (k && *k) s += std::string(" kernel=") + k;
         if (buf && cap) {

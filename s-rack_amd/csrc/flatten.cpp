@@ -225,6 +225,7 @@ int Builder::build()
 
     std::map<std::pair<int, int>, int> wire_of;  // (module, port) -> wire id; in_slot / out_slot hold WIRE ids until the scan
     std::vector<std::pair<int, const VoiceOverride*>> deferred, deferred_delta;
+    std::vector<std::pair<int, std::vector<uint32_t>>> deferred_raw;  // parameter rows that are not a field's override (a banked sample player's), as bits
     std::vector<int> seq_ops;  // sequencer ops: each gets one read-only row to stage its 64 cells in
     auto new_wire = [&](int def_op) {
         wires.push_back(Wire{def_op, def_op, -1});
@@ -428,13 +429,50 @@ int Builder::build()
             }
             param(op, SMP_P_SR, m, SRACK_SAMPLE_SAMPLE_RATE, deferred);
             param(op, SMP_P_WAVE_SR, m, SRACK_SAMPLE_WAVE_SAMPLE_RATE, deferred);
-            if (mod.wave.size() >= (size_t)1 << 31) {
-                set_error("flatten: wave longer than 2^31 - 1 samples");
+            // a wave per voice (srack_voices_set_waves): the own wave, then the whole bank, contiguously; which stretch of it a voice plays,
+            // how long it is and its rate are rows of the voice table.  Never in a control program (flatten(), step 3).
+            const bool banked = !is_ctl && mod.voice_wave.size() == (size_t)V && !mod.voice_wave.empty();
+            const size_t n_bank = banked && mod.bank ? mod.bank->size() : 0;
+            if (mod.wave.size() >= (size_t)1 << 31 || out.seqtab.size() + mod.wave.size() + n_bank + 8 >= (size_t)1 << 31) {
+                set_error("flatten: waves longer than 2^31 - 1 samples");
                 return SRACK_ERR_UNSUPPORTED;
             }
-            op.seq_len = (int)mod.wave.size();
+            op.seq_len = (int)(mod.wave.size() + n_bank);
             op.aux = (int)out.seqtab.size();
             for (float f : mod.wave) out.seqtab.push_back(f32_bits(f));
+            if (banked) {
+                op.flags |= SMP_BANK;
+                if (n_bank) {
+                    const size_t at = out.seqtab.size();
+                    out.seqtab.resize(at + n_bank);
+                    std::memcpy(&out.seqtab[at], mod.bank->data(), 4 * n_bank);
+                }
+                std::vector<uint32_t> first(mod.bank_len.size());
+                uint32_t run = (uint32_t)mod.wave.size();
+                for (size_t k = 0; k < first.size(); k++) {
+                    first[k] = run;
+                    run += (uint32_t)mod.bank_len[k];
+                }
+                const VoiceOverride* own_sr = find_override(m, SRACK_SAMPLE_WAVE_SAMPLE_RATE);
+                std::vector<uint32_t> sr(V), off(V), len(V);
+                for (uint32_t v = 0; v < V; v++) {
+                    const int w = mod.voice_wave[v];
+                    if (w >= (int)first.size()) {  // (graph.cpp checks the indices against the bank they were set with, and a new bank drops them)
+                        set_error("flatten: a voice names a wave the bank does not have");
+                        return SRACK_ERR_INVALID;
+                    }
+                    sr[v] = f32_bits(w >= 0 ? mod.bank_sr[(size_t)w] : (float)(own_sr ? own_sr->values[v] : field(m, SRACK_SAMPLE_WAVE_SAMPLE_RATE)));
+                    off[v] = w >= 0 ? first[(size_t)w] : 0u;
+                    len[v] = w >= 0 ? (uint32_t)mod.bank_len[(size_t)w] : (uint32_t)mod.wave.size();
+                }
+                if (op.par_row[SMP_P_WAVE_SR] == -2)  // the override's row is replaced by the merged one
+                    deferred.pop_back();
+                const int at = (int)out.ops.size() * kMaxPar;
+                op.par_row[SMP_P_WAVE_SR] = op.par_row[SMP_P_WAVE_OFF] = op.par_row[SMP_P_WAVE_LEN] = -2;
+                deferred_raw.emplace_back(at + SMP_P_WAVE_SR, std::move(sr));
+                deferred_raw.emplace_back(at + SMP_P_WAVE_OFF, std::move(off));
+                deferred_raw.emplace_back(at + SMP_P_WAVE_LEN, std::move(len));
+            }
             break;
         }
         case SRACK_MOD_GRID_SEQUENCER:
@@ -563,6 +601,11 @@ int Builder::build()
         for (uint32_t v = 0; v < V; v++) row[v] = f32_bits((float)d.second->values[v]);
         op.par_row[d.first % kMaxPar] = r;
     }
+    for (auto& d : deferred_raw) {
+        const int r = new_row();
+        rows[(size_t)r] = std::move(d.second);
+        out.ops[(size_t)(d.first / kMaxPar)].par_row[d.first % kMaxPar] = r;
+    }
     for (auto& d : deferred_delta) {
         DevOp& op = out.ops[(size_t)d.first];
         std::vector<double> delta(V);
@@ -673,6 +716,11 @@ int Builder::build()
         H.tile = tile;
     }
 
+    for (const DevOp& op : out.ops)
+        if (op.kind == OP_SAMPLE && (op.flags & SMP_BANK)) {  // a lane's window reads aligned groups of four dwords, one group ahead: past the last wave's end
+            out.seqtab.resize(out.seqtab.size() + 8, 0u);
+            break;
+        }
     out.table.resize((size_t)H.n_rows * V);
     for (int r = 0; r < H.n_rows; r++) std::memcpy(&out.table[(size_t)r * V], rows[(size_t)r].data(), sizeof(uint32_t) * V);
 
@@ -926,6 +974,11 @@ int flatten(Graph& g, uint32_t n_voices, const std::vector<VoiceOverride>& overr
             return SRACK_ERR_UNSUPPORTED;
         }
     }
+    for (const Module& mod : g.modules)
+        if (!mod.voice_wave.empty() && mod.voice_wave.size() != n_voices) {
+            set_error("flatten: a wave assignment for another number of voices");
+            return SRACK_ERR_INVALID;
+        }
     Analysis A;
     A.live.assign((size_t)n_mod, 0);
     A.port_live.assign((size_t)n_mod, 0);
@@ -1008,6 +1061,8 @@ int flatten(Graph& g, uint32_t n_voices, const std::vector<VoiceOverride>& overr
         std::vector<char>& u = A.in_ctl;
         for (int m = 0; m < n_mod; m++) u[(size_t)m] = A.live[(size_t)m] && m != output && g.modules[(size_t)m].type != SRACK_MOD_NOISE;  // every voice draws its own noise
         for (const auto& o : overrides) u[(size_t)o.module] = 0;
+        for (int m = 0; m < n_mod; m++)
+            if (!g.modules[(size_t)m].voice_wave.empty()) u[(size_t)m] = 0;  // a wave per voice (srack_voices_set_waves)
         const auto& pos = g.plan.position;
         for (bool changed = true; changed;) {
             changed = false;
@@ -1183,6 +1238,8 @@ int flatten(Graph& g, uint32_t n_voices, const std::vector<VoiceOverride>& overr
     if (out.n_tracks > 0) d << " tracks=" << out.n_tracks;
     d << " B=" << g.cfg.buffer_size;
     if (!out.approx_note.empty()) d << " approx[" << out.approx_note << "]";
+    for (const DevOp& op : out.voice.ops)
+        if (op.kind == OP_SAMPLE && (op.flags & SMP_BANK)) out.n_bank_waves += (int)g.modules[(size_t)op.module].bank_len.size();
     out.description = d.str();
     return SRACK_OK;
 }

@@ -314,6 +314,85 @@ int Graph::set_wave(int module, const float* samples, uint32_t n, float sample_r
     return SRACK_OK;
 }
 
+// A change of what some voice plays is a load of its wave (WaveBox::load: new = true): every voice of the player starts at pos = 0
+static void wave_loaded(Graph& g, Module& m)
+{
+    m.fields[SRACK_SAMPLE_WAVE_NEW] = 1.0;
+    g.revision++;
+    m.wave_revision = g.revision;
+}
+
+int Graph::set_wave_bank(int module, const float* samples, const int* lengths, const float* sample_rates, uint32_t n_waves)
+{
+    if (module < 0 || module >= (int)modules.size() || modules[(size_t)module].type != SRACK_MOD_SAMPLE) {
+        set_error("set_wave_bank: not a SampleModule");
+        return SRACK_ERR_INVALID;
+    }
+    if (n_waves && (!lengths || !sample_rates)) {
+        set_error("set_wave_bank: lengths / sample_rates is null");
+        return SRACK_ERR_INVALID;
+    }
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < n_waves; k++) {
+        if (lengths[k] < 0) {
+            set_error("set_wave_bank: wave " + std::to_string(k) + " has a negative length");
+            return SRACK_ERR_INVALID;
+        }
+        total += (uint64_t)lengths[k];
+    }
+    if (total && !samples) {
+        set_error("set_wave_bank: samples is null");
+        return SRACK_ERR_INVALID;
+    }
+    // (built aside: an allocation failure leaves the old bank in place)
+    std::shared_ptr<const std::vector<float>> bank;
+    if (n_waves) bank = std::make_shared<const std::vector<float>>(samples, samples + total);
+    std::vector<int32_t> len(lengths, lengths + (n_waves ? n_waves : 0));
+    std::vector<float> sr(sample_rates, sample_rates + (n_waves ? n_waves : 0));
+    Module& m = modules[(size_t)module];
+    m.bank = std::move(bank);
+    m.bank_len = std::move(len);
+    m.bank_sr = std::move(sr);
+    if (!m.voice_wave.empty()) {  // the voices go back to the own wave: a load.  Without an assignment the bank is inert: nothing to restart
+        m.voice_wave.clear();
+        wave_loaded(*this, m);
+    } else {
+        revision++;
+    }
+    return SRACK_OK;
+}
+
+int Graph::set_voice_waves(int module, const int* wave, uint32_t n_voices)
+{
+    if (module < 0 || module >= (int)modules.size() || modules[(size_t)module].type != SRACK_MOD_SAMPLE) {
+        set_error("voices_set_waves: not a SampleModule");
+        return SRACK_ERR_INVALID;
+    }
+    Module& m = modules[(size_t)module];
+    if (!wave) {
+        if (!m.voice_wave.empty()) {
+            m.voice_wave.clear();
+            wave_loaded(*this, m);
+        }
+        return SRACK_OK;
+    }
+    const int n_waves = (int)m.bank_len.size();
+    for (uint32_t v = 0; v < n_voices; v++)
+        if (wave[v] < SRACK_WAVE_OWN || wave[v] >= n_waves) {
+            set_error("voices_set_waves: voice " + std::to_string(v) + " names wave " + std::to_string(wave[v]) + " of " + std::to_string(n_waves));
+            return SRACK_ERR_INVALID;
+        }
+    std::vector<int32_t> w(wave, wave + n_voices);
+    m.voice_wave = std::move(w);
+    wave_loaded(*this, m);
+    return SRACK_OK;
+}
+
+void Graph::drop_voice_waves()
+{
+    for (Module& m : modules) m.voice_wave.clear();
+}
+
 // Contents of one output buffer as a loaded .srk leaves them: only observable through a broken feedback edge, whose
 // sink reads the source's buffer before the source has run.
 int Graph::set_output_buffer(int module, int port, const float* samples, uint32_t n)

@@ -12,6 +12,7 @@
 // identity, synth.rs:109); fields are stored as doubles (exact for f32 / f64 / bool / enum).
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -34,6 +35,13 @@ struct Module {
     std::vector<uint32_t> cells;
     std::vector<float> wave;  // SampleModule: wavebox.samples
     uint64_t wave_revision = 0;  // Graph::revision when the wave (and with it wavebox.new) was last set
+    // SampleModule, no counterpart in the reference: a bank of waves back to back (shared between copies of the graph: a bank may be
+    // hundreds of megabytes) with each wave's length and rate, and which of them every voice plays (n_voices entries, SRACK_WAVE_OWN =
+    // the module's own wave; empty: no assignment — the bank is inert)
+    std::shared_ptr<const std::vector<float>> bank;
+    std::vector<int32_t> bank_len;
+    std::vector<float> bank_sr;
+    std::vector<int32_t> voice_wave;
     // what a .srk file carries besides the fields (ui.rs:578-586): the module's UUID string, its workspace position,
     // and the contents of its output buffers — the latter is what the sink of a broken feedback edge reads during
     // the first block after a load (empty = zeros, AudioBuffer::new)
@@ -80,6 +88,9 @@ public:
     int set_step(int module, int channel, int step, int state, int value);
     int get_step(int module, int channel, int step, int* state, int* value) const;
     int set_wave(int module, const float* samples, uint32_t n, float sample_rate);
+    int set_wave_bank(int module, const float* samples, const int* lengths, const float* sample_rates, uint32_t n_waves);
+    int set_voice_waves(int module, const int* wave, uint32_t n_voices);  // wave == nullptr clears
+    void drop_voice_waves();                                              // srack_voices_configure: every module's assignment
     int set_output_buffer(int module, int port, const float* samples, uint32_t n);  // n == buffer_size, or 0 to clear
     int connect(int src, int src_port, int sink, int sink_port);
     int disconnect(int sink, int sink_port);

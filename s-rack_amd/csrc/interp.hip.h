@@ -538,7 +538,8 @@ __device__ __noinline__ void tile_noise(const Ctx c_v, COp& op_v, uint64_t n_abs
 
 // SampleModule (sample.rs:192-240) in two passes over the tile: the position state machine does not depend on the
 // samples it reads, so pass 1 leaves each sample's read INDEX in the output wire and pass 2 turns indices into
-// samples with independent gathers from the shared wave (8 loads in flight per lane instead of one per step).
+// samples with independent gathers from the wave (8 loads in flight per lane instead of one per step).  SMP_BANK: the lane's own
+// wave — its length, its rate and where it starts behind the own wave are rows of the voice table.
 template <bool kExact>
 __device__ __noinline__ void tile_sample(const Ctx c_v, COp& op_v, CArgs& a_v)
 {
@@ -552,7 +553,8 @@ __device__ __noinline__ void tile_sample(const Ctx c_v, COp& op_v, CArgs& a_v)
     s.playing = ROW(sr + SMP_S_PLAYING) != 0;
     s.gate_last = ROW(sr + SMP_S_GATE_LAST) != 0;
     const float ratio = par(c, op, SMP_P_WAVE_SR) / par(c, op, SMP_P_SR);
-    const uint32_t n_wave = (uint32_t)op.seq_len;
+    const bool bank = (fl & SMP_BANK) != 0;
+    const uint32_t n_wave = bank ? ROW(op.par_row[SMP_P_WAVE_LEN]) : (uint32_t)op.seq_len;
     const Port in[2] = {in_port(c, op.in_slot[0]), in_port(c, op.in_slot[1])};
     const Port out[1] = {out_port(c, op.out_slot[0])};
     tile_run<2, 1>(c, in, out, [&](const float* x, float* y) { y[0] = __uint_as_float(sample_advance(fl, s, ratio, n_wave, x[0], x[1])); });
@@ -560,7 +562,7 @@ __device__ __noinline__ void tile_sample(const Ctx c_v, COp& op_v, CArgs& a_v)
     ROW(sr + SMP_S_PLAYING) = s.playing ? 1u : 0u;
     ROW(sr + SMP_S_GATE_LAST) = s.gate_last ? 1u : 0u;
     if (op.out_slot[0] < 0) return;
-    const uint32_t* wave = a.seqtab + op.aux;
+    const uint32_t* wave = a.seqtab + op.aux + (bank ? ROW(op.par_row[SMP_P_WAVE_OFF]) : 0u);  // (index < n_wave: inside the lane's own wave)
     const Port w = out[0];
     int i = 0;
     for (; i + 8 <= c.n; i += 8) {

@@ -25,6 +25,7 @@ struct JitFetchInfo {  // how one kernel was come by
     double compile_ms = 0.0;  // hiprtc time when how == 2
     int waves = 0;            // the register budget the kernel was compiled under (waves per SIMD; 0: none asked for)
     int vgprs = 0;            // its VGPRs
+    bool bank_lds = false;    // a banked sample player's waves are staged in LDS (part of the source: jit.cpp, gen_sample)
 };
 
 struct JitCacheStats {  // process-wide, since start (srack_kernel_cache_stats)

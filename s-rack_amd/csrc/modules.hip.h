@@ -1955,5 +1955,43 @@ SRK_DEV uint32_t sample_advance(uint32_t flags, SmpRegs& s, float ratio, uint32_
     return idx;
 }
 
+// A lane's window on its own wave of a bank in global memory (jit.cpp, gen_sample): the aligned group of four dwords that holds the
+// last index read (`cur`, group `g0` of the table) and the group behind it (`nxt`), which is loaded ahead.  An index in `cur` is served
+// from registers; one in `nxt` shifts the window and issues the load of the next group, whose result nothing waits for until the lane
+// gets there; any other index (a retrigger, a large step, a wrap) loads both groups anew.  The table is read-only for the launch and
+// the window lives in registers for the launch: what it serves is what the plain gather would have read.  The groups it loads may
+// reach up to seven dwords past the index — the flattener pads the table's tail by eight.
+typedef uint32_t smp_u4 __attribute__((ext_vector_type(4)));
+struct SmpWindow {
+    uint32_t g0;  // first dword of `cur` in the table (a multiple of 4), or a value no group has
+    smp_u4 cur, nxt;
+};
+
+SRK_DEV SmpWindow smp_window_init()
+{
+    SmpWindow w;
+    w.g0 = 0xfffffff0u;  // (the table's offsets are < 2^31)
+    w.cur = w.nxt = smp_u4{0u, 0u, 0u, 0u};
+    return w;
+}
+
+// table[at]; `table` is 16-byte aligned (the start of the device allocation)
+SRK_DEV uint32_t smp_window_read(SmpWindow& w, const uint32_t* table, uint32_t at)
+{
+    const uint32_t g = at & ~3u;
+    if (g != w.g0) {
+        if (g - w.g0 == 4u) {
+            w.cur = w.nxt;
+        } else {
+            w.cur = *(const smp_u4*)(table + g);
+        }
+        w.nxt = *(const smp_u4*)(table + g + 4u);
+        w.g0 = g;
+    }
+    const uint32_t j = at & 3u;
+    const uint32_t lo = (j & 1u) ? w.cur.y : w.cur.x, hi = (j & 1u) ? w.cur.w : w.cur.z;
+    return (j & 2u) ? hi : lo;
+}
+
 }  // namespace dev
 }  // namespace srack

@@ -183,9 +183,11 @@ struct DeviceState {
     uint64_t bus_revision = 0;
     float* d_bus_part = nullptr;
     size_t bus_part_bytes = 0;
+    bool last_bank_lds = false;  // the last render's kernel read its wave banks from LDS (srack_render_info)
     uint32_t last_buses = 0;  // bus mixes the last render filled (srack_render_info)
     std::shared_ptr<const JitKernel> jit[5];  // the specialised voice kernel per output mode (1 frames, 2 mix, 3 both, 4 neither), co-owned with the cache
     bool jit_failed = false;  // specialisation was tried by default and is not available: the interpreter renders
+    bool bank_lds[5] = {false, false, false, false, false};  // per output mode: the specialised kernel stages its banked players' waves in LDS
     std::string jit_note;     // for srack_render_info: how the kernel was come by (compiled in N ms / disk cache / memory), or why there is none
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timings;  // (start, stop) pairs of the dominant kernel, not yet read
     std::vector<hipEvent_t> pool;
@@ -759,7 +761,9 @@ static int resolve_specialized(PatchHandle& h, uint32_t flags, uint32_t n_sample
         else
             std::snprintf(note, sizeof note, " jit=%s%s", how.how == 1 ? "disk-cache" : "memory-cache", budget);
         d->jit_note = note;
+        d->bank_lds[out_mode] = how.bank_lds;
     }
+    d->last_bank_lds = d->bank_lds[out_mode];
     *out = d->jit[out_mode].get();
     *with_ctl = ctl;
     return SRACK_OK;
@@ -1683,6 +1687,12 @@ int device_read_rows(PatchHandle& h, int ctl_stage, int first_row, int n_rows, u
 
 const char* device_kernel_name(const PatchHandle& h) { return h.dev ? h.dev->kernel_name : ""; }
 std::string device_bus_note(const PatchHandle& h) { return h.dev && h.dev->last_buses ? " buses=" + std::to_string(h.dev->last_buses) + "[fold]" : std::string(); }
+std::string device_waves_note(const PatchHandle& h)
+{
+    if (!h.prog_valid || h.prog.n_bank_waves == 0) return std::string();
+    const bool lds = h.dev && h.dev->last_bank_lds && std::strncmp(h.dev->kernel_name, "render_specialized", 18) == 0;
+    return " waves=" + std::to_string(h.prog.n_bank_waves) + (lds ? "[lds]" : "[global]");
+}
 std::string device_jit_note(const PatchHandle& h) { return h.dev ? h.dev->jit_note : std::string(); }
 
 }  // namespace srack

@@ -171,6 +171,19 @@ public:
     }
     void set_voice_waves(const SharedSynthModule& m, const int* wave) { check(srack_voices_set_waves(p_, m.index(), wave)); }  // nullptr clears
     uint32_t get_voice_waves(const SharedSynthModule& m, int* wave = nullptr, uint32_t cap = 0) const { return (uint32_t)check(srack_voices_get_waves(p_, m.index(), wave, cap)); }
+    // A sequence per voice for a grid (C = 1) or pattern (C = 8) sequencer: a bank of sequences — states u8 [n][C][64] as set_step's, the
+    // grid's note values u16 [n][64] (nullptr: all 0), lengths [n] in 1..64 — and, per voice, an index into it or SRACK_SEQ_OWN (the
+    // module's own cells and length).  An assignment edits cells: under keep_state every voice's step and held CV carry over.
+    void set_sequence_bank(const SharedSynthModule& m, const uint8_t* states, const uint16_t* values, const int* lengths, uint32_t n_sequences)
+    {
+        check(srack_patch_set_sequence_bank(p_, m.index(), states, values, lengths, n_sequences));
+    }
+    uint32_t get_sequence_bank(const SharedSynthModule& m, uint8_t* states = nullptr, uint16_t* values = nullptr, int* lengths = nullptr, uint32_t cap = 0) const
+    {
+        return (uint32_t)check(srack_patch_get_sequence_bank(p_, m.index(), states, values, lengths, cap));
+    }
+    void set_voice_sequences(const SharedSynthModule& m, const int* seq) { check(srack_voices_set_sequences(p_, m.index(), seq)); }  // nullptr clears
+    uint32_t get_voice_sequences(const SharedSynthModule& m, int* seq = nullptr, uint32_t cap = 0) const { return (uint32_t)check(srack_voices_get_sequences(p_, m.index(), seq, cap)); }
     // execute_batch plus d_bus_mix, f32 [n_buses][channels][n_samples] (written); d_frames, d_mix, d_stats may each be null
     void execute_batch_buses(uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags = 0, void* stream = nullptr)
     {

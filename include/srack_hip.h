@@ -338,6 +338,38 @@ int srack_patch_get_wave_bank_samples(const srack_patch* p, int module, int wave
 int srack_voices_set_waves(srack_patch* p, int module, const int* wave);
 int srack_voices_get_waves(const srack_patch* p, int module, int* wave, uint32_t cap);
 
+/* ---- a sequence bank: every voice of a sequencer its own notes, pattern and length ----------- */
+/* The bank: `n_sequences` sequences for a GridSequencerModule (C = 1) or a PatternSequencerModule (C = 8, its gate channels):
+ *   states  : u8 [n_sequences][C][64]  SRACK_STEP_NONE / _ON / _HOLD, exactly srack_patch_set_step's `state`
+ *   values  : u16 [n_sequences][64]    the grid sequencer's note index; NULL = all 0; ignored (may be NULL) for a pattern sequencer
+ *   lengths : int [n_sequences]        1..64: what SRACK_GRIDSEQ_LENGTH / SRACK_PATSEQ_LENGTH is for the module's own sequence
+ * Copied (and shared between copies of the graph); cells at or past a sequence's length are never played and are not kept: they read
+ * back as SRACK_STEP_NONE, as does the value of a SRACK_STEP_NONE cell as 0.  n_sequences == 0 removes the bank (pointers may be NULL).
+ * A bank does nothing until voices are assigned to it: the module's own cells (srack_patch_set_step) and *_LENGTH stay as they are, and
+ * a patch with a bank and no assignment renders the same bits through the same kernel as without one.  Setting a bank drops the
+ * module's voice assignment.  SRACK_ERR_INVALID, with the earlier bank and assignment left in place, for a module that is no
+ * sequencer, a state outside 0..2, a length outside 1..64 and n_sequences > SRACK_MAX_SEQUENCES.
+ * get_sequence_bank copies up to `cap` sequences (any pointer may be NULL) and returns n_sequences.
+ * The assignment: seq[v] in [0, n_sequences), or SRACK_SEQ_OWN: that voice plays the module's own cells at *_LENGTH, exactly as without
+ * a bank.  A voice with seq[v] >= 0 renders what a one-voice patch renders whose module holds that bank sequence's cells
+ * (srack_patch_set_step) and length (*_LENGTH).  steps_per_octave stays the module's field (it can differ per voice on its own).
+ * `seq` has n_voices entries; NULL clears the assignment.  A bad index (outside [-1, n_sequences), or >= 0 without a bank) is
+ * SRACK_ERR_INVALID and leaves the earlier assignment in place; SRACK_ERR_STATE before srack_voices_configure.
+ * An assignment is an edit of cells — what the reference's grid editor does — not a load: the patch is re-flattened like after
+ * srack_patch_set_step, so by default the voices restart, and under srack_patch_keep_state current_step, both edge detectors and the
+ * grid sequencer's held CV carry over per voice; a current_step at or past the voice's new length wraps to 0 on the next sample (the
+ * sequencer's own rule).  This differs on purpose from the wave bank, where an assignment loads a wave.
+ * srack_voices_configure drops assignments.  Rack files carry neither bank nor assignment (no counterpart in the reference).  A sharded
+ * host sets the same bank on every rank and each rank's own voices' indices.
+ * get_sequences copies up to `cap` entries and returns n_voices, or 0 when no assignment is set.
+ * (`states` and `values` are declared as untyped pointers: they point at uint8_t and uint16_t arrays of the layouts above.) */
+#define SRACK_SEQ_OWN (-1)
+#define SRACK_MAX_SEQUENCES 65536
+int srack_patch_set_sequence_bank(srack_patch* p, int module, const void* states, const void* values, const int* lengths, uint32_t n_sequences);
+int srack_patch_get_sequence_bank(const srack_patch* p, int module, void* states, void* values, int* lengths, uint32_t cap);
+int srack_voices_set_sequences(srack_patch* p, int module, const int* seq);
+int srack_voices_get_sequences(const srack_patch* p, int module, int* seq, uint32_t cap);
+
 /* ---- render (needs the GPU) ---------------------------------------------------------------- */
 /* Number of distinct wires feeding the OutputModule's channels and, per channel, which plane of
  * `d_frames` it is (-1 = unconnected => silence).  P1/P2 wire both channels to one source => 1 plane. */

@@ -63,6 +63,10 @@ mod ffi {
         pub fn srack_patch_get_wave_bank_samples(p: *const SrackPatch, module: c_int, wave: c_int, samples: *mut f32, cap: u32) -> c_int;
         pub fn srack_voices_set_waves(p: *mut SrackPatch, module: c_int, wave: *const c_int) -> c_int;
         pub fn srack_voices_get_waves(p: *const SrackPatch, module: c_int, wave: *mut c_int, cap: u32) -> c_int;
+        pub fn srack_patch_set_sequence_bank(p: *mut SrackPatch, module: c_int, states: *const u8, values: *const c_void, lengths: *const c_int, n_sequences: u32) -> c_int;
+        pub fn srack_patch_get_sequence_bank(p: *const SrackPatch, module: c_int, states: *mut u8, values: *mut c_void, lengths: *mut c_int, cap: u32) -> c_int;
+        pub fn srack_voices_set_sequences(p: *mut SrackPatch, module: c_int, seq: *const c_int) -> c_int;
+        pub fn srack_voices_get_sequences(p: *const SrackPatch, module: c_int, seq: *mut c_int, cap: u32) -> c_int;
         pub fn srack_render_buses(p: *mut SrackPatch, n_samples: u32, d_frames: *mut f32, d_mix: *mut f32, d_stats: *mut f64, d_bus_mix: *mut f32, flags: u32, stream: *mut c_void) -> c_int;
         pub fn srack_device_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
         pub fn srack_device_free(d_ptr: *mut c_void) -> c_int;
@@ -97,6 +101,10 @@ pub const MAX_BUSES: u32 = 65536;
 pub const BUS_NONE: i32 = -1;
 /// A voice that plays its SampleModule's own wave, not one of the bank (`SRACK_WAVE_OWN`).
 pub const WAVE_OWN: i32 = -1;
+/// A voice that plays its sequencer's own cells at the module's length, not a sequence of the bank (`SRACK_SEQ_OWN`).
+pub const SEQ_OWN: i32 = -1;
+/// The most sequences a bank may hold (`SRACK_MAX_SEQUENCES`).
+pub const MAX_SEQUENCES: u32 = 65536;
 
 /// Render flags (values of `SRACK_RENDER_*`).
 pub mod render_flags {
@@ -327,6 +335,34 @@ impl Patch {
         let mut w = vec![0 as c_int; n_voices];
         let n = check(unsafe { ffi::srack_voices_get_waves(self.raw, module, w.as_mut_ptr(), n_voices as u32) })?;
         Ok(if n == 0 { None } else { Some(w) })
+    }
+    /// A bank of sequences for a grid (C = 1) or pattern (C = 8 gate channels) sequencer: `states` is `[n][C][64]` step states (0 none, 1 on,
+    /// 2 hold, as `set_step`), `values` the grid's `[n][64]` note indices (None: all 0; unused by a pattern sequencer), `lengths` `[n]` in
+    /// 1..=64 (`srack_patch_set_sequence_bank`; an empty bank removes it).  Inert until `set_voice_sequences` assigns voices to it.
+    pub fn set_sequence_bank(&mut self, module: i32, states: &[u8], values: Option<&[u16]>, lengths: &[i32]) -> Result<(), Error> {
+        assert!(states.len() >= lengths.len() * 64 && values.map_or(true, |v| v.len() >= lengths.len() * 64));
+        let v = values.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void);
+        check(unsafe { ffi::srack_patch_set_sequence_bank(self.raw, module, states.as_ptr(), v, lengths.as_ptr() as *const c_int, lengths.len() as u32) }).map(|_| ())
+    }
+    /// `(states [n][channels][64], values [n][64], lengths [n])` of the bank, `channels` = 1 for a grid and 8 for a pattern sequencer; empty
+    /// without a bank.
+    pub fn get_sequence_bank(&self, module: i32, channels: usize) -> Result<(Vec<u8>, Vec<u16>, Vec<i32>), Error> {
+        let n = check(unsafe { ffi::srack_patch_get_sequence_bank(self.raw, module, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), 0) })? as usize;
+        let (mut s, mut v, mut l) = (vec![0u8; n * channels * 64], vec![0u16; n * 64], vec![0 as c_int; n]);
+        check(unsafe { ffi::srack_patch_get_sequence_bank(self.raw, module, s.as_mut_ptr(), v.as_mut_ptr() as *mut c_void, l.as_mut_ptr(), n as u32) })?;
+        Ok((s, v, l))
+    }
+    /// Which sequence of the bank every voice plays: `seq[v]` in `0 .. n_sequences` or `SEQ_OWN` (the module's own cells and length); None
+    /// clears.  An edit of cells, not a load: under `keep_state` every voice's step and held CV carry over (`srack_voices_set_sequences`).
+    pub fn set_voice_sequences(&mut self, module: i32, seq: Option<&[i32]>) -> Result<(), Error> {
+        let q = seq.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        check(unsafe { ffi::srack_voices_set_sequences(self.raw, module, q) }).map(|_| ())
+    }
+    /// The assignment, `n_voices` entries; None when none is set.
+    pub fn get_voice_sequences(&self, module: i32, n_voices: usize) -> Result<Option<Vec<i32>>, Error> {
+        let mut q = vec![0 as c_int; n_voices];
+        let n = check(unsafe { ffi::srack_voices_get_sequences(self.raw, module, q.as_mut_ptr(), n_voices as u32) })?;
+        Ok(if n == 0 { None } else { Some(q) })
     }
     /// `execute_batch` plus one weighted mix per bus: `bus_mix` is `[n_buses][channels][n_samples]` f32, written by the call
     /// (`srack_render_buses`); frames, mix and statistics may each be None.

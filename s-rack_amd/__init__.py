@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libsrack_hip.so")
 OK, ERR_INVALID, ERR_PORT, ERR_NO_OUTPUT, ERR_SELF_LOOP, ERR_STATE, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8
 MAX_BUSES, BUS_NONE = 65536, -1
 WAVE_OWN = -1
+SEQ_OWN, MAX_SEQUENCES = -1, 65536
 STAT_SUM, STAT_SUM_SQ, STAT_PEAK_POS, STAT_PEAK_NEG, STAT_NONFINITE, STAT_CLIPPED, STAT_COUNT = 0, 1, 2, 3, 4, 5, 6
 RENDER_DEFAULT, RENDER_EXACT_OSC, RENDER_NO_FUSION, RENDER_NO_UNIFORM_HOIST, RENDER_NO_CTL_STAGES, RENDER_NO_SPECIALIZE, RENDER_SPECIALIZE, RENDER_KEEP_DEFAULT = 0, 1, 2, 4, 8, 16, 32, 64
 
@@ -32,6 +33,7 @@ ABI_SYMBOLS = [
     "srack_voices_configure", "srack_voices_set_field_f32", "srack_voices_set_field_f64", "srack_render_planes", "srack_render", "srack_render_stats", "srack_render_reserve",
     "srack_voices_set_buses", "srack_voices_get_buses", "srack_voices_bus_plan", "srack_render_buses",
     "srack_patch_set_wave_bank", "srack_patch_get_wave_bank", "srack_patch_get_wave_bank_samples", "srack_voices_set_waves", "srack_voices_get_waves",
+    "srack_patch_set_sequence_bank", "srack_patch_get_sequence_bank", "srack_voices_set_sequences", "srack_voices_get_sequences",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
     "srack_device_alloc", "srack_device_free", "srack_device_to_host", "srack_device_from_host", "srack_device_sync",
     "srack_dist_unique_id", "srack_dist_init", "srack_dist_comm_count", "srack_dist_destroy", "srack_dist_reduce_mix",
@@ -107,6 +109,11 @@ def _load():
         L.srack_patch_get_wave_bank_samples.argtypes = [vp, i32, i32, fp, u32]
         L.srack_voices_set_waves.argtypes = [vp, i32, ip]
         L.srack_voices_get_waves.argtypes = [vp, i32, ip, u32]
+    if hasattr(L, "srack_voices_set_sequences"):
+        L.srack_patch_set_sequence_bank.argtypes = [vp, i32, vp, vp, ip, u32]
+        L.srack_patch_get_sequence_bank.argtypes = [vp, i32, vp, vp, ip, u32]
+        L.srack_voices_set_sequences.argtypes = [vp, i32, ip]
+        L.srack_voices_get_sequences.argtypes = [vp, i32, ip, u32]
     L.srack_render_reserve.argtypes = [vp, u32, i32, u32]
     L.srack_render_info.argtypes = [vp, C.c_char_p, sz]
     L.srack_render_kernel_ms.argtypes = [vp, dp, ip, i32]
@@ -355,6 +362,46 @@ class Patch:
             return None
         a = np.empty(n, dtype=np.intc)
         _check(lib.srack_voices_get_waves(self.h, module, a.ctypes.data_as(C.POINTER(C.c_int)), n))
+        return a
+
+    def set_sequence_bank(self, module, states, values=None, lengths=None):
+        """A bank of sequences for a sequencer (srack_patch_set_sequence_bank): `states` u8 [n][64] for a grid sequencer or [n][8][64] for a
+        pattern sequencer (STEP_NONE / _ON / _HOLD), `values` the grid's u16 [n][64] note indices (None: all 0), `lengths` [n] in 1..64
+        (None: all 64).  An empty `states` removes the bank.  Inert until set_voice_sequences assigns voices to it."""
+        st = np.ascontiguousarray(states, dtype=np.uint8)
+        n = st.shape[0] if st.ndim > 1 else 0
+        assert n == 0 or st.shape[-1] == 64, st.shape
+        vals = None if values is None else np.ascontiguousarray(values, dtype=np.uint16)
+        assert vals is None or vals.shape == (n, 64), vals.shape
+        ln = np.full(n, 64, dtype=np.intc) if lengths is None else np.ascontiguousarray(lengths, dtype=np.intc)
+        assert ln.shape == (n,), ln.shape
+        _check(lib.srack_patch_set_sequence_bank(self.h, module, st.ctypes.data if n else None, None if vals is None or n == 0 else vals.ctypes.data,
+                                                 ln.ctypes.data_as(C.POINTER(C.c_int)), n))
+
+    def get_sequence_bank(self, module, channels=1):
+        """-> (states u8 [n][channels][64], values u16 [n][64], lengths int32 [n]); channels: 1 for a grid, 8 for a pattern sequencer"""
+        n = _check(lib.srack_patch_get_sequence_bank(self.h, module, None, None, None, 0))
+        st, vals, ln = np.zeros((n, channels, 64), dtype=np.uint8), np.zeros((n, 64), dtype=np.uint16), np.zeros(n, dtype=np.intc)
+        if n:
+            _check(lib.srack_patch_get_sequence_bank(self.h, module, st.ctypes.data, vals.ctypes.data, ln.ctypes.data_as(C.POINTER(C.c_int)), n))
+        return st, vals, ln
+
+    def set_voice_sequences(self, module, idx):
+        """Which sequence of the bank every voice plays (srack_voices_set_sequences): idx[v] in [0, n_sequences) or SEQ_OWN; None clears."""
+        if idx is None:
+            _check(lib.srack_voices_set_sequences(self.h, module, None))
+            return
+        a = np.ascontiguousarray(idx, dtype=np.intc)
+        assert a.shape == (self.n_voices,), a.shape
+        _check(lib.srack_voices_set_sequences(self.h, module, a.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def get_voice_sequences(self, module):
+        """-> int32 [V], or None when no assignment is set"""
+        n = _check(lib.srack_voices_get_sequences(self.h, module, None, 0))
+        if n == 0:
+            return None
+        a = np.empty(n, dtype=np.intc)
+        _check(lib.srack_voices_get_sequences(self.h, module, a.ctypes.data_as(C.POINTER(C.c_int)), n))
         return a
 
     def connect(self, src, src_port, sink, sink_port):

@@ -368,6 +368,9 @@ struct Analysis {
             const double spo = std::max(1.0, field(m, SRACK_GRIDSEQ_STEPS_PER_OCTAVE).lo);
             for (uint32_t c : mod.cells)
                 if (c >> 31) note = std::max(note, (double)(c & 0xffffu) / spo);
+            if (!mod.voice_seq.empty() && mod.seq_bank)  // voices play sequences of the bank: the highest note of any of them
+                for (uint32_t c : *mod.seq_bank)
+                    if (c >> 31) note = std::max(note, (double)(c & 0xffffu) / spo);
             const double gate = std::max(1.0, connected(m, SRACK_SEQ_IN_STEP) ? in_mag(m, SRACK_SEQ_IN_STEP) : 0.0);
             o = {note, gate, 1.0};
             const uint32_t clocked = clock_motion(m);  // (a sequencer steps as often as its clock ticks)

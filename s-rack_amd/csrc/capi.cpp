@@ -342,6 +342,83 @@ int srack_voices_get_waves(const srack_patch* p, int module, int* wave, uint32_t
     });
 }
 
+static const Module* get_sequencer(const srack_patch* p, int module, const char* who)
+{
+    const Module* m = get_module(p, module);
+    if (!m || (m->type != SRACK_MOD_GRID_SEQUENCER && m->type != SRACK_MOD_PATTERN_SEQUENCER)) {
+        set_error(std::string(who) + ": not a sequencer");
+        return nullptr;
+    }
+    return m;
+}
+
+int srack_patch_set_sequence_bank(srack_patch* p, int module, const void* states, const void* values, const int* lengths, uint32_t n_sequences)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        const int rc = p->h.graph.set_sequence_bank(module, (const uint8_t*)states, (const uint16_t*)values, lengths, n_sequences);
+        if (rc == SRACK_OK) p->h.voices_revision++;  // (the assignment, if there was one, is gone)
+        return rc;
+    });
+}
+
+int srack_patch_get_sequence_bank(const srack_patch* p, int module, void* states_out, void* values_out, int* lengths, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        uint8_t* const states = (uint8_t*)states_out;
+        uint16_t* const values = (uint16_t*)values_out;
+        const Module* m = get_sequencer(p, module, "get_sequence_bank");
+        if (!m) return SRACK_ERR_INVALID;
+        const bool grid = m->type == SRACK_MOD_GRID_SEQUENCER;
+        const size_t C = grid ? 1 : 8;
+        for (size_t k = 0; k < m->seq_bank_len.size() && k < (size_t)cap; k++) {
+            if (lengths) lengths[k] = m->seq_bank_len[k];
+            for (size_t step = 0; step < 64; step++) {
+                const uint32_t cell = (*m->seq_bank)[k * 64 + step];
+                if (grid) {
+                    if (states) states[k * 64 + step] = (uint8_t)(!(cell & 0x80000000u) ? SRACK_STEP_NONE : ((cell & 0x40000000u) ? SRACK_STEP_HOLD : SRACK_STEP_ON));
+                } else if (states) {
+                    for (size_t c = 0; c < C; c++) {
+                        const uint32_t b = (cell >> (2 * c)) & 3u;
+                        states[(k * C + c) * 64 + step] = (uint8_t)(!(b & 1u) ? SRACK_STEP_NONE : ((b & 2u) ? SRACK_STEP_HOLD : SRACK_STEP_ON));
+                    }
+                }
+                if (values) values[k * 64 + step] = grid ? (uint16_t)(cell & 0xffffu) : (uint16_t)0;
+            }
+        }
+        return (int)m->seq_bank_len.size();
+    });
+}
+
+int srack_voices_set_sequences(srack_patch* p, int module, const int* seq)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        PatchHandle& h = p->h;
+        if (!get_sequencer(p, module, "voices_set_sequences")) return SRACK_ERR_INVALID;
+        if (h.n_voices == 0) {
+            set_error("voices_set_sequences: call srack_voices_configure first");
+            return SRACK_ERR_STATE;
+        }
+        const int rc = h.graph.set_voice_sequences(module, seq, h.n_voices);
+        if (rc == SRACK_OK) h.voices_revision++;
+        return rc;
+    });
+}
+
+int srack_voices_get_sequences(const srack_patch* p, int module, int* seq, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        const Module* m = get_sequencer(p, module, "voices_get_sequences");
+        if (!m) return SRACK_ERR_INVALID;
+        if (seq)
+            for (size_t v = 0; v < m->voice_seq.size() && v < (size_t)cap; v++) seq[v] = m->voice_seq[v];
+        return (int)m->voice_seq.size();
+    });
+}
+
 int srack_patch_load_srk(const void* bytes, size_t n_bytes, uint32_t sample_rate, uint32_t buffer_size, uint32_t channels, srack_patch** out)
 {
     return guarded([&]() -> int {
@@ -783,6 +860,7 @@ int srack_render_info(srack_patch* p, char* buf, size_t cap)
         // (the kernel's name stays LAST: hosts and tests read it with split("kernel="))
         s += device_bus_note(p->h);
         s += device_waves_note(p->h);
+        s += device_sequences_note(p->h);
         s += device_jit_note(p->h);
         if (k && *k) s += std::string(" kernel=") + k;
         if (buf && cap) {

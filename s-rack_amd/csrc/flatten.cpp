@@ -490,8 +490,30 @@ int Builder::build()
                 param(op, GRIDSEQ_P_SPO, m, SRACK_GRIDSEQ_STEPS_PER_OCTAVE, deferred);
             }
             op.seq_len = (int)field(m, grid ? SRACK_GRIDSEQ_LENGTH : SRACK_PATSEQ_LENGTH);
+            // a sequence per voice (srack_voices_set_sequences): the own 64 cells, then the whole bank, 64 cells per sequence; where a voice's
+            // cells start and how long its sequence is are rows of the voice table.  Never in a control program (flatten(), step 3).
+            const bool banked = !is_ctl && mod.voice_seq.size() == (size_t)V && !mod.voice_seq.empty();
             op.aux = (int)out.seqtab.size();
             out.seqtab.insert(out.seqtab.end(), mod.cells.begin(), mod.cells.end());
+            if (banked) {
+                op.flags |= SEQ_BANK;
+                const size_t n_seq = mod.seq_bank_len.size();
+                if (n_seq) out.seqtab.insert(out.seqtab.end(), mod.seq_bank->begin(), mod.seq_bank->end());
+                std::vector<uint32_t> off(V), len(V);
+                for (uint32_t v = 0; v < V; v++) {
+                    const int w = mod.voice_seq[v];
+                    if (w >= (int)n_seq) {  // (graph.cpp checks the indices against the bank they were set with, and a new bank drops them)
+                        set_error("flatten: a voice names a sequence the bank does not have");
+                        return SRACK_ERR_INVALID;
+                    }
+                    off[v] = w >= 0 ? 64u * (uint32_t)(w + 1) : 0u;
+                    len[v] = w >= 0 ? (uint32_t)mod.seq_bank_len[(size_t)w] : (uint32_t)std::min(std::max(op.seq_len, 0), 64);  // (a lane never reads past its own 64 cells)
+                }
+                const int at = (int)out.ops.size() * kMaxPar;
+                op.par_row[SEQ_P_CELL_OFF] = op.par_row[SEQ_P_LEN] = -2;
+                deferred_raw.emplace_back(at + SEQ_P_CELL_OFF, std::move(off));
+                deferred_raw.emplace_back(at + SEQ_P_LEN, std::move(len));
+            }
             seq_ops.push_back(oi);
             break;
         }
@@ -979,6 +1001,11 @@ int flatten(Graph& g, uint32_t n_voices, const std::vector<VoiceOverride>& overr
             set_error("flatten: a wave assignment for another number of voices");
             return SRACK_ERR_INVALID;
         }
+    for (const Module& mod : g.modules)
+        if (!mod.voice_seq.empty() && mod.voice_seq.size() != n_voices) {
+            set_error("flatten: a sequence assignment for another number of voices");
+            return SRACK_ERR_INVALID;
+        }
     Analysis A;
     A.live.assign((size_t)n_mod, 0);
     A.port_live.assign((size_t)n_mod, 0);
@@ -1062,7 +1089,7 @@ int flatten(Graph& g, uint32_t n_voices, const std::vector<VoiceOverride>& overr
         for (int m = 0; m < n_mod; m++) u[(size_t)m] = A.live[(size_t)m] && m != output && g.modules[(size_t)m].type != SRACK_MOD_NOISE;  // every voice draws its own noise
         for (const auto& o : overrides) u[(size_t)o.module] = 0;
         for (int m = 0; m < n_mod; m++)
-            if (!g.modules[(size_t)m].voice_wave.empty()) u[(size_t)m] = 0;  // a wave per voice (srack_voices_set_waves)
+            if (!g.modules[(size_t)m].voice_wave.empty() || !g.modules[(size_t)m].voice_seq.empty()) u[(size_t)m] = 0;  // a wave / a sequence per voice (srack_voices_set_waves / _set_sequences)
         const auto& pos = g.plan.position;
         for (bool changed = true; changed;) {
             changed = false;
@@ -1240,6 +1267,8 @@ int flatten(Graph& g, uint32_t n_voices, const std::vector<VoiceOverride>& overr
     if (!out.approx_note.empty()) d << " approx[" << out.approx_note << "]";
     for (const DevOp& op : out.voice.ops)
         if (op.kind == OP_SAMPLE && (op.flags & SMP_BANK)) out.n_bank_waves += (int)g.modules[(size_t)op.module].bank_len.size();
+    for (const DevOp& op : out.voice.ops)
+        if ((op.kind == OP_GRIDSEQ || op.kind == OP_PATSEQ) && (op.flags & SEQ_BANK)) out.n_bank_sequences += (int)g.modules[(size_t)op.module].seq_bank_len.size();
     out.description = d.str();
     return SRACK_OK;
 }

@@ -72,6 +72,7 @@ struct FlatPair {
     int n_tracks = 0;           // rows of the track buffer
     uint32_t effective_flags = 0;  // the render flags the programs were built for (the request, plus what flatten had to add)
     int n_bank_waves = 0;          // waves in the banks of the sample players that render with a voice assignment (SMP_BANK), 0: none does
+    int n_bank_sequences = 0;      // sequences in the banks of the sequencers that render with a voice assignment (SEQ_BANK), 0: none does
     std::string approx_note;       // default mode: the first-order error bound of the forms taken (approx.cpp), or why the patch went exact
     std::vector<char> in_ctl;   // per module: evaluated by the control program
     std::vector<int> ctl_stage; // per module: its unit, -1 if not in the control program

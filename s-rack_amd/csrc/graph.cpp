@@ -390,7 +390,95 @@ int Graph::set_voice_waves(int module, const int* wave, uint32_t n_voices)
 
 void Graph::drop_voice_waves()
 {
-    for (Module& m : modules) m.voice_wave.clear();
+    for (Module& m : modules) {
+        m.voice_wave.clear();
+        m.voice_seq.clear();
+    }
+}
+
+// A bank of sequences (no counterpart in the reference): each one is what srack_patch_set_step would have left in the module's 64
+// cells, with its own length.  Cells past the length are stored as zero: nothing reads them (seq_advance wraps before).
+int Graph::set_sequence_bank(int module, const uint8_t* states, const uint16_t* values, const int* lengths, uint32_t n_sequences)
+{
+    if (module < 0 || module >= (int)modules.size() ||
+        (modules[(size_t)module].type != SRACK_MOD_GRID_SEQUENCER && modules[(size_t)module].type != SRACK_MOD_PATTERN_SEQUENCER)) {
+        set_error("set_sequence_bank: not a sequencer");
+        return SRACK_ERR_INVALID;
+    }
+    Module& m = modules[(size_t)module];
+    const bool grid = m.type == SRACK_MOD_GRID_SEQUENCER;
+    const size_t C = grid ? 1 : 8;
+    if (n_sequences > SRACK_MAX_SEQUENCES) {
+        set_error("set_sequence_bank: more than SRACK_MAX_SEQUENCES sequences");
+        return SRACK_ERR_INVALID;
+    }
+    if (n_sequences && (!states || !lengths)) {
+        set_error("set_sequence_bank: states / lengths is null");
+        return SRACK_ERR_INVALID;
+    }
+    for (uint32_t k = 0; k < n_sequences; k++) {
+        if (lengths[k] < 1 || lengths[k] > 64) {
+            set_error("set_sequence_bank: sequence " + std::to_string(k) + " has a length outside 1..64");
+            return SRACK_ERR_INVALID;
+        }
+        for (size_t i = 0; i < C * 64; i++)
+            if (states[(size_t)k * C * 64 + i] > SRACK_STEP_HOLD) {
+                set_error("set_sequence_bank: sequence " + std::to_string(k) + " holds a state outside 0..2");
+                return SRACK_ERR_INVALID;
+            }
+    }
+    // (built aside: an allocation failure leaves the old bank in place)
+    std::shared_ptr<const std::vector<uint32_t>> bank;
+    std::vector<int32_t> len(lengths, lengths + (n_sequences ? n_sequences : 0));
+    if (n_sequences) {
+        std::vector<uint32_t> cells((size_t)n_sequences * 64, 0u);
+        for (uint32_t k = 0; k < n_sequences; k++)
+            for (int step = 0; step < lengths[k]; step++) {
+                uint32_t cell = 0u;
+                for (size_t c = 0; c < C; c++) {
+                    const uint8_t st = states[((size_t)k * C + c) * 64 + (size_t)step];
+                    if (st == SRACK_STEP_NONE) continue;
+                    if (grid)
+                        cell = 0x80000000u | (st == SRACK_STEP_HOLD ? 0x40000000u : 0u) | (values ? (uint32_t)values[(size_t)k * 64 + (size_t)step] : 0u);
+                    else
+                        cell |= (1u | (st == SRACK_STEP_HOLD ? 2u : 0u)) << (2 * c);
+                }
+                cells[(size_t)k * 64 + (size_t)step] = cell;
+            }
+        bank = std::make_shared<const std::vector<uint32_t>>(std::move(cells));
+    }
+    m.seq_bank = std::move(bank);
+    m.seq_bank_len = std::move(len);
+    m.voice_seq.clear();  // (the voices play the own cells again: an edit of cells, like set_step)
+    revision++;
+    return SRACK_OK;
+}
+
+int Graph::set_voice_sequences(int module, const int* seq, uint32_t n_voices)
+{
+    if (module < 0 || module >= (int)modules.size() ||
+        (modules[(size_t)module].type != SRACK_MOD_GRID_SEQUENCER && modules[(size_t)module].type != SRACK_MOD_PATTERN_SEQUENCER)) {
+        set_error("voices_set_sequences: not a sequencer");
+        return SRACK_ERR_INVALID;
+    }
+    Module& m = modules[(size_t)module];
+    if (!seq) {
+        if (!m.voice_seq.empty()) {
+            m.voice_seq.clear();
+            revision++;
+        }
+        return SRACK_OK;
+    }
+    const int n = (int)m.seq_bank_len.size();
+    for (uint32_t v = 0; v < n_voices; v++)
+        if (seq[v] < SRACK_SEQ_OWN || seq[v] >= n) {
+            set_error("voices_set_sequences: voice " + std::to_string(v) + " names sequence " + std::to_string(seq[v]) + " of " + std::to_string(n));
+            return SRACK_ERR_INVALID;
+        }
+    std::vector<int32_t> s(seq, seq + n_voices);
+    m.voice_seq = std::move(s);
+    revision++;  // an edit of cells (the reference's grid editor, sequencer.rs:137-184, 437-478), not a load: no state is reset
+    return SRACK_OK;
 }
 
 // Contents of one output buffer as a loaded .srk leaves them: only observable through a broken feedback edge, whose

@@ -42,6 +42,12 @@ struct Module {
     std::vector<int32_t> bank_len;
     std::vector<float> bank_sr;
     std::vector<int32_t> voice_wave;
+    // sequencers, no counterpart in the reference: a bank of sequences, 64 cells each in the device format above (cells past a
+    // sequence's length are zero) with each sequence's length, shared between copies of the graph, and which of them every voice
+    // plays (n_voices entries, SRACK_SEQ_OWN = the module's own cells at *_LENGTH; empty: no assignment — the bank is inert)
+    std::shared_ptr<const std::vector<uint32_t>> seq_bank;
+    std::vector<int32_t> seq_bank_len;
+    std::vector<int32_t> voice_seq;
     // what a .srk file carries besides the fields (ui.rs:578-586): the module's UUID string, its workspace position,
     // and the contents of its output buffers — the latter is what the sink of a broken feedback edge reads during
     // the first block after a load (empty = zeros, AudioBuffer::new)
@@ -90,7 +96,9 @@ public:
     int set_wave(int module, const float* samples, uint32_t n, float sample_rate);
     int set_wave_bank(int module, const float* samples, const int* lengths, const float* sample_rates, uint32_t n_waves);
     int set_voice_waves(int module, const int* wave, uint32_t n_voices);  // wave == nullptr clears
-    void drop_voice_waves();                                              // srack_voices_configure: every module's assignment
+    void drop_voice_waves();                                              // srack_voices_configure: every module's assignment (waves and sequences)
+    int set_sequence_bank(int module, const uint8_t* states, const uint16_t* values, const int* lengths, uint32_t n_sequences);
+    int set_voice_sequences(int module, const int* seq, uint32_t n_voices);  // seq == nullptr clears
     int set_output_buffer(int module, int port, const float* samples, uint32_t n);  // n == buffer_size, or 0 to clear
     int connect(int src, int src_port, int sink, int sink_port);
     int disconnect(int sink, int sink_port);

@@ -582,7 +582,7 @@ __device__ __noinline__ void tile_sample(const Ctx c_v, COp& op_v, CArgs& a_v)
 
 // Sequencers (sequencer.rs:190-246, 482-533): the step machine and the cell decoding live in modules.hip.h.  The 64 grid cells
 // are wave-shared data: staged once per tile in an LDS row indexed by STEP (not by lane); every lane then gathers the cell
-// of its own current_step.
+// of its own current_step.  With a sequence per voice (SEQ_BANK) nothing is staged: each lane reads its own cells.
 template <bool kExact>
 __device__ __noinline__ void tile_seq(const Ctx c_v, COp& op_v, CArgs& a_v)
 {
@@ -594,11 +594,18 @@ __device__ __noinline__ void tile_seq(const Ctx c_v, COp& op_v, CArgs& a_v)
     s.current_step = ROW(sr + SEQ_S_CURRENT);
     s.step_last = ROW(sr + SEQ_S_STEP_LAST) != 0;
     s.sync_last = ROW(sr + SEQ_S_SYNC_LAST) != 0;
-    __syncthreads();
-    c.rows[op.seq_row * 64 + c.lane] = a.seqtab[op.aux + c.lane];
-    __syncthreads();
+    // SEQ_BANK (a sequence per voice: srack_voices_set_sequences): the lane's length is a row of the voice table and its cell is
+    // gathered from the lane's own 64 cells in seqtab, which start CELL_OFF dwords behind the own ones (cs < length <= 64: inside them).
+    const bool bank = (op.flags & SEQ_BANK) != 0;  // wave-uniform
+    if (!bank) {
+        __syncthreads();
+        c.rows[op.seq_row * 64 + c.lane] = a.seqtab[op.aux + c.lane];
+        __syncthreads();
+    }
     const lds_u32* cells = c.rows + op.seq_row * 64;
-    const uint32_t length = (uint32_t)op.seq_len;
+    const uint32_t* own = a.seqtab + op.aux + (bank ? ROW(op.par_row[SEQ_P_CELL_OFF]) : 0u);
+    const uint32_t length = bank ? ROW(op.par_row[SEQ_P_LEN]) : (uint32_t)op.seq_len;
+    auto cell_at = [&](uint32_t cs) { return bank ? own[cs] : cells[cs]; };
     const Port in[2] = {in_port(c, op.in_slot[0]), in_port(c, op.in_slot[1])};
     if (op.kind == OP_GRIDSEQ) {
         float last = __uint_as_float(ROW(sr + GRIDSEQ_S_LAST));
@@ -606,7 +613,7 @@ __device__ __noinline__ void tile_seq(const Ctx c_v, COp& op_v, CArgs& a_v)
         const Port out[3] = {out_port(c, op.out_slot[0]), out_port(c, op.out_slot[1]), out_port(c, op.out_slot[2])};
         tile_run<2, 3>(c, in, out, [&](const float* x, float* y) {
             const uint32_t cs = seq_advance(s, x[0], x[1], length);
-            gridseq_outputs(cells[cs], cs, x[0], inv_spo, last, y[0], y[1], y[2]);
+            gridseq_outputs(cell_at(cs), cs, x[0], inv_spo, last, y[0], y[1], y[2]);
         });
         ROW(sr + GRIDSEQ_S_LAST) = __float_as_uint(last);
     } else {
@@ -632,7 +639,7 @@ __device__ __noinline__ void tile_seq(const Ctx c_v, COp& op_v, CArgs& a_v)
             for (int u = 0; u < kU; u++) {
                 if (u >= m) break;
                 const uint32_t cs = seq_advance(s, step_in[u], sync_in[u], length);
-                cell[u] = cells[cs];
+                cell[u] = cell_at(cs);
                 first[u] = cs == 0u;
             }
 #pragma unroll

@@ -104,6 +104,7 @@ enum : uint32_t {
     // OP_GRIDSEQ / OP_PATSEQ: bit k = output port k is read; SEQ_HAS_* in bits 16..17
     SEQ_HAS_STEP = 1u << 16,
     SEQ_HAS_SYNC = 1u << 17,
+    SEQ_BANK = 1u << 18,      // voices are assigned sequences of a bank (srack_voices_set_sequences): where the lane's 64 cells start and its length are per-voice rows
     // OP_DELAY_*
     DELAY_RING_GLOBAL = 1u << 0  // ring in HBM ([B][V] f32); otherwise B consecutive LDS rows
 };
@@ -129,6 +130,7 @@ enum { VCA_P_NEG = 0 };
 enum { MIX_P_GAIN0 = 0 };
 enum { MATH_P_CONST = 0 };
 enum { GRIDSEQ_P_SPO = 0 };  // steps_per_octave as f32
+enum { SEQ_P_CELL_OFF = 1, SEQ_P_LEN = 2 };  // (both sequencers, with SEQ_BANK only: u32 rows — the voice's 64 cells start CELL_OFF dwords behind DevOp::aux, its sequence has LEN steps)
 enum { NONLIN_P_CONST = 0 };
 enum { SMP_P_SR = 0, SMP_P_WAVE_SR = 1, SMP_P_WAVE_OFF = 2, SMP_P_WAVE_LEN = 3 };  // (the last two with SMP_BANK only: u32 rows — the voice's wave starts WAVE_OFF dwords behind DevOp::aux and has WAVE_LEN samples)
 
@@ -151,9 +153,9 @@ struct DevOp {
     // OP_OSC without CV: delta = 440 * 2^val / sample_rate, hoisted to the host in f64
     // (bit-equal to the reference's per-sample value, oscillator.rs:43-48,132)
     int32_t delta_row;          // >= 0: two per-voice rows (lo, hi); -1: uniform => delta.  OP_FREEVERB: first row of its block in KernelArgs::fv
-    int32_t aux;                // OP_OUT: plane; OP_DELAY_*: ring id / first LDS row; sequencers: dword offset of the 64 cells in seqtab; OP_SAMPLE: dword offset of the wave in seqtab (SMP_BANK: of the own wave, the bank behind it)
+    int32_t aux;                // OP_OUT: plane; OP_DELAY_*: ring id / first LDS row; sequencers: dword offset of the 64 cells in seqtab (SEQ_BANK: of the own cells, the bank behind them); OP_SAMPLE: dword offset of the wave in seqtab (SMP_BANK: of the own wave, the bank behind it)
     int32_t seq_row;            // sequencers: LDS row the 64 cells are staged in (shared by the wave, indexed by step)
-    int32_t seq_len;            // sequencers: sequence length (1..64); OP_SAMPLE: wave length in samples (SMP_BANK: own wave + bank, the whole region)
+    int32_t seq_len;            // sequencers: sequence length (1..64; SEQ_BANK: the own sequence's, what SRACK_SEQ_OWN voices play); OP_SAMPLE: wave length in samples (SMP_BANK: own wave + bank, the whole region)
     double delta;               // OP_NOISE: the bit pattern of the module's u64 base key
     double sample_rate;         // OP_OSC: f64(sample_rate), the divisor of oscillator.rs:132; OP_NOISE: the bit pattern of the u64 first_voice
 };

@@ -1693,6 +1693,11 @@ std::string device_waves_note(const PatchHandle& h)
     const bool lds = h.dev && h.dev->last_bank_lds && std::strncmp(h.dev->kernel_name, "render_specialized", 18) == 0;
     return " waves=" + std::to_string(h.prog.n_bank_waves) + (lds ? "[lds]" : "[global]");
 }
+std::string device_sequences_note(const PatchHandle& h)
+{
+    if (!h.prog_valid || h.prog.n_bank_sequences == 0) return std::string();
+    return " sequences=" + std::to_string(h.prog.n_bank_sequences) + "[global]";  // (every kernel gathers a lane's cell from seqtab: jit.cpp, gen_seq)
+}
 std::string device_jit_note(const PatchHandle& h) { return h.dev ? h.dev->jit_note : std::string(); }
 
 }  // namespace srack

@@ -20,6 +20,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "fused.hip.h"
@@ -503,7 +504,38 @@ static int grow(float*& p, size_t& have, size_t need)
     return SRACK_OK;
 }
 
-// ---- fused-kernel dispatch (template parameters from runtime port flags) ---------------------------
+// ---- kernel launches (template parameters from runtime port flags and output modes) ----------------
+// f(std::integral_constant<int, O>) with the output mode as a compile-time constant: 3 frames + mix, 1 frames, 2 mix; 0 for anything else —
+// the instantiation that decides at run time (a render that asks for neither only advances the voice state).  Every kernel family takes
+// its output mode from here; one that has no instantiation of its own for a mode says so where it calls.
+template <class Fn>
+static auto with_out_mode(int out_mode, Fn&& f)
+{
+    switch (out_mode) {
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 0>{});
+    }
+}
+
+// ... and f(std::integral_constant<uint32_t, P>) for the one of three output ports a flag word names (anything else: the last)
+template <uint32_t P0, uint32_t P1, uint32_t P2, class Fn>
+static void with_port(uint32_t port, Fn&& f)
+{
+    if (port == P0)
+        f(std::integral_constant<uint32_t, P0>{});
+    else if (port == P1)
+        f(std::integral_constant<uint32_t, P1>{});
+    else
+        f(std::integral_constant<uint32_t, P2>{});
+}
+template <class Fn>
+static void with_osc_port(uint32_t port, Fn&& f)
+{
+    with_port<OSC_OUT_SAW, OSC_OUT_SQUARE, OSC_OUT_SINE>(port, f);
+}
+
 template <uint32_t A, uint32_t F, bool E, int O>
 static void launch_fused4(bool track, const KernelArgs& ka, const ChainRoles& roles, const CtlWork& co, dim3 grid, hipStream_t st)
 {
@@ -524,127 +556,103 @@ static void launch_fused3(bool exact, int out_mode, bool track, const KernelArgs
         hipLaunchKernelGGL((render_voice_chain_track<A, F, true, 3>), grid, dim3(64), 0, st, ka, roles, co);
     else if (exact)  // otherwise one instantiation, output mode decided at run time
         launch_fused4<A, F, true, 0>(track, ka, roles, co, grid, st);
-    else if (out_mode == 3)
-        launch_fused4<A, F, false, 3>(track, ka, roles, co, grid, st);
-    else if (out_mode == 1)
-        launch_fused4<A, F, false, 1>(track, ka, roles, co, grid, st);
-    else if (out_mode == 2)
-        launch_fused4<A, F, false, 2>(track, ka, roles, co, grid, st);
-    else  // neither frames nor mix requested: the render only advances the voice state
-        launch_fused4<A, F, false, 0>(track, ka, roles, co, grid, st);
-}
-
-template <uint32_t A>
-static void launch_fused2(uint32_t vcf_port, bool exact, int out_mode, bool track, const KernelArgs& ka, const ChainRoles& roles, const CtlWork& co, dim3 grid,
-                          hipStream_t st)
-{
-    if (vcf_port == VCF_OUT_LP)
-        launch_fused3<A, VCF_OUT_LP>(exact, out_mode, track, ka, roles, co, grid, st);
-    else if (vcf_port == VCF_OUT_BP)
-        launch_fused3<A, VCF_OUT_BP>(exact, out_mode, track, ka, roles, co, grid, st);
     else
-        launch_fused3<A, VCF_OUT_HP>(exact, out_mode, track, ka, roles, co, grid, st);
+        with_out_mode(out_mode, [&](auto O) { launch_fused4<A, F, false, O>(track, ka, roles, co, grid, st); });
 }
 
 static void launch_fused(uint32_t osc_port, uint32_t vcf_port, bool exact, int out_mode, bool track, const KernelArgs& ka, const ChainRoles& roles,
                          const CtlWork& co, dim3 grid, hipStream_t st)
 {
-    if (osc_port == OSC_OUT_SAW)
-        launch_fused2<OSC_OUT_SAW>(vcf_port, exact, out_mode, track, ka, roles, co, grid, st);
-    else if (osc_port == OSC_OUT_SQUARE)
-        launch_fused2<OSC_OUT_SQUARE>(vcf_port, exact, out_mode, track, ka, roles, co, grid, st);
-    else
-        launch_fused2<OSC_OUT_SINE>(vcf_port, exact, out_mode, track, ka, roles, co, grid, st);
-}
-
-template <uint32_t kPort>
-static void launch_seq2(int out_mode, const KernelArgs& ka, const SeqRoles& r, dim3 grid, hipStream_t st)
-{
-    if (out_mode == 3)
-        hipLaunchKernelGGL((render_voice_chain_seq<kPort, 3>), grid, dim3(64), 0, st, ka, r);
-    else if (out_mode == 1)
-        hipLaunchKernelGGL((render_voice_chain_seq<kPort, 1>), grid, dim3(64), 0, st, ka, r);
-    else
-        hipLaunchKernelGGL((render_voice_chain_seq<kPort, 0>), grid, dim3(64), 0, st, ka, r);
+    with_osc_port(osc_port, [&](auto A) {
+        with_port<VCF_OUT_LP, VCF_OUT_BP, VCF_OUT_HP>(vcf_port, [&](auto F) { launch_fused3<decltype(A)::value, F>(exact, out_mode, track, ka, roles, co, grid, st); });
+    });
 }
 
 static void launch_seq(uint32_t osc_port, int out_mode, const KernelArgs& ka, const SeqRoles& r, dim3 grid, hipStream_t st)
 {
-    if (osc_port == OSC_OUT_SAW)
-        launch_seq2<OSC_OUT_SAW>(out_mode, ka, r, grid, st);
-    else if (osc_port == OSC_OUT_SQUARE)
-        launch_seq2<OSC_OUT_SQUARE>(out_mode, ka, r, grid, st);
-    else
-        launch_seq2<OSC_OUT_SINE>(out_mode, ka, r, grid, st);
+    with_osc_port(osc_port, [&](auto A) {
+        // (no instantiation for the mix alone: that request takes the one that decides at run time)
+        with_out_mode(out_mode == 2 ? 0 : out_mode, [&](auto O) {
+            if constexpr (O != 2) hipLaunchKernelGGL((render_voice_chain_seq<decltype(A)::value, O>), grid, dim3(64), 0, st, ka, r);
+        });
+    });
 }
 
-// kRing: the feedback delay is a ring in HBM (buffer_size >= 32) instead of last tick's value in a register (buffer_size 1)
-template <bool kRing>
-static void launch_fm_pair2(bool exact, int out_mode, const KernelArgs& ka, const ChainRoles& roles, dim3 grid, hipStream_t st)
+// The hand-written kernel a program takes (pick_kernel below).
+enum class Kernel { Interp, VoiceChain, VoiceChainTrack, SeqChain, FmPair, FmPairRing, FmPairSplit, FmPairBlock, FmPairBlockX, FmPairX };
+static const char* const kKernelName[] = {"render_interp", "render_voice_chain", "render_voice_chain_track", "render_voice_chain_seq", "render_fm_pair", "render_fm_pair_ring",
+                                          "render_fm_pair" /* (on two waves) */, "render_fm_pair_block", "render_fm_pair_block_x", "render_fm_pair_x"};
+
+// The FM pair one sample at a time.  variant 1: the feedback delay is a ring in HBM (buffer_size >= 32) instead of last tick's value in a
+// register (buffer_size 1); the latter in exact mode: on two waves per 64 voices, modulators / carriers (measured, see the kernel's comment)
+static Kernel fm_pair_kernel(int variant, bool exact)
 {
-#define SRK_FM(E, O)                                                                                   \
-    do {                                                                                               \
-        if (kRing)                                                                                     \
-            hipLaunchKernelGGL((render_fm_pair_ring<E, O>), grid, dim3(64), 0, st, ka, roles);         \
-        else if ((E) && knobs().fm_split) /* exact mode only: measured, see the kernel's comment */    \
-            hipLaunchKernelGGL((render_fm_pair_split<true, 0>), grid, dim3(128), 0, st, ka, roles);    \
-        else                                                                                           \
-            hipLaunchKernelGGL((render_fm_pair<E, O>), grid, dim3(64), 0, st, ka, roles);              \
-    } while (0)
-    if (exact)
-        SRK_FM(true, 0);
-    else if (out_mode == 3)
-        SRK_FM(false, 3);
-    else if (out_mode == 1)
-        SRK_FM(false, 1);
-    else if (out_mode == 2)
-        SRK_FM(false, 2);
+    return variant == 1 ? Kernel::FmPairRing : (exact && knobs().fm_split) ? Kernel::FmPairSplit : Kernel::FmPair;
+}
+
+static ChainRoles fm_pair_roles(const FlatProgram& P)
+{  // op order fixed by the matcher: DELAY_RD, MATH_FB, OSC_M, DELAY_WR, MATH_IDX, OSC_C, OUT
+    ChainRoles roles{};
+    roles.adsr = 1;
+    roles.osc_l = 2;
+    roles.vca = 4;
+    roles.osc_a = 5;
+    roles.out = 6;
+    roles.track = P.ops[0].aux;  // the ring's state row
+    return roles;
+}
+
+static void launch_fm_pair(Kernel kernel, bool exact, int out_mode, const KernelArgs& ka, const ChainRoles& roles, dim3 grid, hipStream_t st)
+{
+    if (kernel == Kernel::FmPairSplit) {
+        hipLaunchKernelGGL((render_fm_pair_split<true, 0>), grid, dim3(128), 0, st, ka, roles);
+        return;
+    }
+    auto launch = [&](auto E, auto O) {
+        if (kernel == Kernel::FmPairRing)
+            hipLaunchKernelGGL((render_fm_pair_ring<E, O>), grid, dim3(64), 0, st, ka, roles);
+        else
+            hipLaunchKernelGGL((render_fm_pair<E, O>), grid, dim3(64), 0, st, ka, roles);
+    };
+    if (exact)  // one instantiation, output mode decided at run time
+        launch(std::true_type{}, std::integral_constant<int, 0>{});
     else
-        SRK_FM(false, 0);
-#undef SRK_FM
+        with_out_mode(out_mode, [&](auto O) { launch(std::false_type{}, O); });
+}
+
+static void launch_fm_pair_x(int out_mode, const KernelArgs& ka, const ChainRoles& roles, dim3 grid, hipStream_t st)
+{
+    with_out_mode(out_mode, [&](auto O) { hipLaunchKernelGGL((render_fm_pair_x<O>), grid, dim3(128), 0, st, ka, roles); });
 }
 
 // The FM pair with a delay of 256 ... 1024 samples in default mode: time-parallel, 32 voices per 512-thread workgroup, ring in LDS.
-static bool fm_block_shape(const FlatProgram& P, uint32_t flags, uint32_t n_samples)
+template <class K>
+static int launch_blk(K kernel, size_t lds, const KernelArgs& ka, const ChainRoles& roles, hipStream_t st)
 {
-    return n_samples >= knobs().fm_block_min && P.fused == FUSED_FM_PAIR && P.fused_variant == 1 && !(flags & (SRACK_RENDER_EXACT_OSC | SRACK_RENDER_NO_FUSION)) && knobs().fm_block &&
-           P.hdr.buffer_size >= kBlkChunk && P.hdr.buffer_size <= 1024;
-}
-
-static int launch_fm_block(int out_mode, const KernelArgs& ka, const ChainRoles& roles, hipStream_t st)
-{
-    const size_t lds = sizeof(float) * (size_t)ka.prog.buffer_size * kBlkVoices + sizeof(double) * 2 * kBlkSlices * kBlkVoices + 16;
-    const dim3 grid(ka.n_waves), block(kBlkVoices * kBlkSlices);
-#define SRK_BLK(O)                                                                                                              \
-    do {                                                                                                                        \
-        /* more than 64 KB of dynamic LDS has to be asked for — per device (the attribute belongs to the current device's copy of the \
-           function) and from any thread: asked for before every launch, which costs nothing next to one */                    \
-        HIP_TRY(hipFuncSetAttribute((const void*)render_fm_pair_block<O>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((render_fm_pair_block<O>), grid, block, lds, st, ka, roles);                                         \
-    } while (0)
-    if (out_mode == 3)
-        SRK_BLK(3);
-    else if (out_mode == 1)
-        SRK_BLK(1);
-    else if (out_mode == 2)
-        SRK_BLK(2);
-    else
-        SRK_BLK(0);
-#undef SRK_BLK
+    // more than 64 KB of dynamic LDS has to be asked for — per device (the attribute belongs to the current device's copy of the
+    // function) and from any thread: asked for before every launch, which costs nothing next to one
+    HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(kernel, dim3(ka.n_waves), dim3(kBlkVoices * kBlkSlices), lds, st, ka, roles);
     return SRACK_OK;
 }
 
-static void launch_fm_pair(bool ring, bool exact, int out_mode, const KernelArgs& ka, const ChainRoles& roles, dim3 grid, hipStream_t st)
+static int launch_fm_block(bool x, int out_mode, const KernelArgs& ka, const ChainRoles& roles, hipStream_t st)
 {
-    if (ring)
-        launch_fm_pair2<true>(exact, out_mode, ka, roles, grid, st);
-    else
-        launch_fm_pair2<false>(exact, out_mode, ka, roles, grid, st);
+    const size_t B = (size_t)ka.prog.buffer_size;
+    return with_out_mode(out_mode, [&](auto O) {
+        if (x) return launch_blk(render_fm_pair_block_x<O>, fm_block_x_lds_bytes((uint32_t)B), ka, roles, st);
+        return launch_blk(render_fm_pair_block<O>, sizeof(float) * B * kBlkVoices + sizeof(double) * 2 * kBlkSlices * kBlkVoices + 16, ka, roles, st);
+    });
+}
+
+static size_t interp_lds_bytes(const DevProgram& H)
+{
+    return ((size_t)H.n_rows + 2 + (size_t)H.n_tracks + (size_t)H.n_slots * H.tile) * 256;  // + zero, trash and track rows
 }
 
 static void launch_interp(const FlatProgram& P, const KernelArgs& ka, hipStream_t st)
 {
-    size_t lds = ((size_t)P.hdr.n_rows + 2 + (size_t)P.hdr.n_tracks + (size_t)P.hdr.n_slots * P.hdr.tile) * 256;  // + zero, trash and track rows
+    const size_t lds = interp_lds_bytes(P.hdr);
     if (knobs().debug_occ) {  // tools/: what the runtime says about resident workgroups per CU for this LDS size
         int n = -1;
         hipError_t e = (P.render_flags & SRACK_RENDER_EXACT_OSC) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, render_interp<true>, 64, lds)
@@ -657,91 +665,99 @@ static void launch_interp(const FlatProgram& P, const KernelArgs& ka, hipStream_
         hipLaunchKernelGGL(render_interp<false>, dim3(ka.n_waves), dim3(64), lds, st, ka);
 }
 
-// ... and with the modulator exact as a whole (default mode's answer to the loop through its pitch, csrc/approx.cpp): render_fm_pair_block_x —
-// unless the host asked for a specialised kernel or the general path by name
-static bool fm_block_x_shape(const FlatProgram& P, uint32_t flags, uint32_t n_samples)
+// Voices per wave.  A full wave (64) is right whenever there are enough voices to give every SIMD work.
+// With few voices, half- or quarter-filled waves double / quadruple the number of waves: a VALU instruction
+// costs the same for 16 lanes as for 64, so this only pays while SIMDs would otherwise sit idle (VALU-bound
+// kernels: up to one wave per SIMD) or while waves are latency-bound (FM pair, interpreter: up to four).
+static uint32_t lanes_per_wave(uint32_t V)
 {
-    return P.fm_pair_x == 1 && n_samples >= knobs().fm_block_min && knobs().fm_block && P.hdr.buffer_size >= 256 && P.hdr.buffer_size <= 1024 &&
-           !(flags & (SRACK_RENDER_EXACT_OSC | SRACK_RENDER_NO_FUSION | SRACK_RENDER_SPECIALIZE));
+    const uint32_t want_waves = knobs().want_waves;
+    uint32_t lanes = 64;
+    while (lanes > 16 && (V + lanes - 1) / lanes * 2 <= want_waves) lanes >>= 1;
+    return lanes;
 }
 
-// ... and at buffer_size 1 (the fed-back sine in a register): render_fm_pair_x
-static bool fm_x_z1_shape(const FlatProgram& P, uint32_t flags)
-{
-    return P.fm_pair_x == 2 && !(flags & (SRACK_RENDER_EXACT_OSC | SRACK_RENDER_NO_FUSION | SRACK_RENDER_SPECIALIZE));
-}
-static void launch_fm_pair_x(int out_mode, const KernelArgs& ka, const ChainRoles& roles, dim3 grid, hipStream_t st)
-{
-    if (out_mode == 3)
-        hipLaunchKernelGGL((render_fm_pair_x<3>), grid, dim3(128), 0, st, ka, roles);
-    else if (out_mode == 1)
-        hipLaunchKernelGGL((render_fm_pair_x<1>), grid, dim3(128), 0, st, ka, roles);
-    else if (out_mode == 2)
-        hipLaunchKernelGGL((render_fm_pair_x<2>), grid, dim3(128), 0, st, ka, roles);
-    else
-        hipLaunchKernelGGL((render_fm_pair_x<0>), grid, dim3(128), 0, st, ka, roles);
-}
-
-static int launch_fm_block_x(int out_mode, const KernelArgs& ka, const ChainRoles& roles, hipStream_t st)
-{
-    const size_t lds = fm_block_x_lds_bytes((uint32_t)ka.prog.buffer_size);
-    const dim3 grid(ka.n_waves), block(kBlkVoices * kBlkSlices);
-#define SRK_BLK(O)                                                                                                              \
-    do {                                                                                                                        \
-        HIP_TRY(hipFuncSetAttribute((const void*)render_fm_pair_block_x<O>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((render_fm_pair_block_x<O>), grid, block, lds, st, ka, roles);                                       \
-    } while (0)
-    if (out_mode == 3)
-        SRK_BLK(3);
-    else if (out_mode == 1)
-        SRK_BLK(1);
-    else if (out_mode == 2)
-        SRK_BLK(2);
-    else
-        SRK_BLK(0);
-#undef SRK_BLK
-    return SRACK_OK;
-}
+// Which kernel renders one segment of a program, and what the schedule has to know about it.  pick_kernel decides, once; Segment,
+// device_reserve and resolve_specialized read.  (DESIGN.md section 4 is pick_kernel as a table.)
+struct KernelPick {
+    Kernel kernel = Kernel::Interp;  // the hand-written kernel the program takes ...
+    bool candidate = false;          // ... unless a specialised one (jit.cpp) takes its place: resolve_specialized's decision, recorded here
+    bool whole_segment = false;      // the time-parallel FM pairs: 32 voices per workgroup whatever the voice count, and the ring in LDS for a launch
+    uint32_t lanes = 64;             // voices per wave (per workgroup)
+    uint32_t chunk = 0;              // samples per launch of a render without a control program
+    const char* name = "";           // for srack_render_info
+    bool stats_in_kernel = false;    // srack_render_stats accumulated in registers as the kernel emits (wave.hip.h, EmitStats); otherwise folded from each launch's frames
+    bool paced = false;              // the voice waves pace themselves against their SIMD's other waves (wave.hip.h, notes/r10.md)
+};
 
 // The general path: a kernel specialised for the program (jit.cpp), or the tile interpreter.  Specialising costs a compilation
 // (~1 s) the first time a program structure is seen, so by default it is reserved for renders wide enough to repay it.
 constexpr uint32_t kSpecializeMinVoices = 4096;
-// Which programs take a specialised kernel: those no hand-written kernel matches, and the shapes whose hand-written kernels the
-// specialised ones outrun or tie on MI355X (P1 with everything per voice: 21.2 -> 18.1 ms per step; the sequencer-driven chain P3:
-// 29.5 -> 24.5; since round 3 the z^-1 FM pair in default mode: the generator derives what render_fm_pair proves by hand — bounded pitch
-// CVs, the wave's vote, a loop copy per class: the same 48 f64-rate instructions per voice-sample in the ISA — and config 4 runs 7.26 -
-// 7.28 ms per step through it against 7.46 - 7.49 on the same box).  The flagship track kernel keeps its hand-written form (fixed-point
-// phase), so do the FM pair's ring variant (per-tile votes on what the ring hands over) and its exact-mode two-wave split.
-// SRACK_FM_FUSED=1 (tools/) keeps render_fm_pair for A/B runs.
-static bool specializable_shape(const FlatProgram& P, uint32_t flags)
+
+static KernelPick pick_kernel(const FlatPair& prog, uint32_t flags, uint32_t n_samples)
 {
-    if (P.fused == FUSED_FM_PAIR) {
-        static const bool keep_fused = [] {
-            const char* e = getenv("SRACK_FM_FUSED");
-            return e && e[0] == '1';
-        }();
-        return P.fused_variant == 0 && !(flags & SRACK_RENDER_EXACT_OSC) && !keep_fused;
+    const FlatProgram& P = prog.voice;
+    const Knobs& k = knobs();
+    const bool exact = (flags & SRACK_RENDER_EXACT_OSC) != 0, general = (flags & SRACK_RENDER_NO_FUSION) != 0;
+    const uint32_t B = (uint32_t)P.hdr.buffer_size;
+    // the time-parallel FM pairs take calls of fm_block_min samples or more: a host that ticks block by block would move the ring between HBM and LDS every call (Knobs)
+    const bool blk = k.fm_block && n_samples >= k.fm_block_min && !exact && !general && B <= 1024;
+    KernelPick p;
+    // The FM pair with the modulator exact as a whole (default mode's answer to the loop through its pitch, csrc/approx.cpp; `fused` is
+    // FUSED_NONE) has kernels of its own — unless the host asked for a specialised kernel or the general path by name
+    if (P.fm_pair_x == 2 && !exact && !general && !(flags & SRACK_RENDER_SPECIALIZE)) {
+        p.kernel = Kernel::FmPairX;  // buffer_size 1: the fed-back sine in a register
+    } else if (P.fm_pair_x == 1 && blk && B >= 256 && !(flags & SRACK_RENDER_SPECIALIZE)) {
+        p.kernel = Kernel::FmPairBlockX;
+    } else if (P.fused == FUSED_FM_PAIR) {
+        p.kernel = P.fused_variant == 1 && blk && B >= (uint32_t)kBlkChunk ? Kernel::FmPairBlock : fm_pair_kernel(P.fused_variant, exact);
+    } else {
+        p.kernel = P.fused == FUSED_VOICE_CHAIN ? Kernel::VoiceChain : P.fused == FUSED_VOICE_CHAIN_TRACK ? Kernel::VoiceChainTrack : P.fused == FUSED_VOICE_CHAIN_SEQ ? Kernel::SeqChain : Kernel::Interp;
     }
-    return P.fused == FUSED_NONE || P.fused == FUSED_VOICE_CHAIN || P.fused == FUSED_VOICE_CHAIN_SEQ;
+    p.name = kKernelName[(int)p.kernel];
+    // Which programs take a specialised kernel: those no hand-written kernel matches, and the shapes whose hand-written kernels the
+    // specialised ones outrun or tie on MI355X (P1 with everything per voice: 21.2 -> 18.1 ms per step; the sequencer-driven chain P3:
+    // 29.5 -> 24.5; since round 3 the z^-1 FM pair in default mode: the generator derives what render_fm_pair proves by hand — bounded pitch
+    // CVs, the wave's vote, a loop copy per class: the same 48 f64-rate instructions per voice-sample in the ISA — and config 4 runs 7.26 -
+    // 7.28 ms per step through it against 7.46 - 7.49 on the same box).  The flagship track kernel keeps its hand-written form (fixed-point
+    // phase), so do the FM pair's ring variant (per-tile votes on what the ring hands over) and its exact-mode two-wave split.
+    // SRACK_FM_FUSED=1 (tools/) keeps render_fm_pair for A/B runs.
+    static const bool keep_fm_fused = [] {
+        const char* e = getenv("SRACK_FM_FUSED");
+        return e && e[0] == '1';
+    }();
+    const bool fm_z1 = P.fused == FUSED_FM_PAIR && P.fused_variant == 0 && !exact;
+    p.candidate = (fm_z1 ? !keep_fm_fused : p.kernel == Kernel::VoiceChain || p.kernel == Kernel::SeqChain || (p.kernel == Kernel::Interp && P.fused == FUSED_NONE)) &&
+                  !(flags & SRACK_RENDER_NO_SPECIALIZE) && !P.ops.empty();
+    p.whole_segment = p.kernel == Kernel::FmPairBlock || p.kernel == Kernel::FmPairBlockX;
+    p.lanes = p.whole_segment ? (uint32_t)kBlkVoices : lanes_per_wave(P.n_voices);
+    // Launch length without a control program to overlap with: short launches still win — the waves of a launch stay within a few samples
+    // of each other, so their frame rows land in the same DRAM pages (FM pair 13.2 -> 9.9 ms per step).  The z^-1 FM pair (one wave per SIMD
+    // at config 4's 65 536 voices, no ring traffic) wants them shorter still: 2048 samples 7.26 ms per step, 4096 7.39, 1536 7.31, 1024 7.43,
+    // 8192 7.85 (tools/ab_env.sh, one box); its ring variant and the flagship are flat from 3072 to 6144.  The time-parallel pairs load and
+    // store the ring once per launch: the whole segment by default.
+    p.chunk = p.whole_segment ? k.fm_block_chunk : (p.kernel == Kernel::FmPairX || (fm_z1 && !general)) ? std::min(k.chunk_max, 2048u) : k.chunk_max;
+    p.stats_in_kernel = p.kernel == Kernel::VoiceChain || p.kernel == Kernel::VoiceChainTrack;
+    p.paced = p.kernel == Kernel::VoiceChainTrack && k.pace;
+    return p;
 }
 
-static uint32_t lanes_per_wave(uint32_t V);
-
-static int resolve_specialized(PatchHandle& h, uint32_t flags, uint32_t n_samples, int out_mode, const JitKernel** out, bool* with_ctl)
+// Does a candidate get its specialised kernel?  If so the pick says what renders from here on.
+static int resolve_specialized(PatchHandle& h, KernelPick& pick, uint32_t flags, int out_mode, const JitKernel** out, bool* with_ctl)
 {
     *out = nullptr;
     *with_ctl = false;
     const FlatProgram& P = h.prog.voice;
     DeviceState* d = h.dev;
-    if (!specializable_shape(P, flags) || (flags & SRACK_RENDER_NO_SPECIALIZE) || P.ops.empty() || fm_block_x_shape(P, flags, n_samples) || fm_x_z1_shape(P, flags)) return SRACK_OK;
+    if (!pick.candidate) return SRACK_OK;
     const bool forced = (flags & SRACK_RENDER_SPECIALIZE) != 0;
     if (!forced && (P.n_voices < kSpecializeMinVoices || d->jit_failed || !jit_supported(P))) return SRACK_OK;
     // the control program's units ride along in the same launches whenever the generator covers them all
     const bool ctl = h.prog.n_tracks > 0 && knobs().special_ctl && jit_ctl_supported(h.prog);
+    const uint32_t n_waves = (P.n_voices + pick.lanes - 1) / pick.lanes;
     if (!d->jit[out_mode]) {
         JitFetchInfo how;
         // (how many waves per SIMD this render has for the kernel: one wave per 64 voices on 1024 SIMDs)
-        const uint32_t n_waves = (P.n_voices + lanes_per_wave(P.n_voices) - 1) / lanes_per_wave(P.n_voices);
         const int rc = jit_get(h.prog, out_mode, ctl, &d->jit[out_mode], &how, (int)std::min(4u, (n_waves + 1023u) / 1024u));
         if (rc != SRACK_OK) {
             if (forced) return rc;  // asked for explicitly: fail loudly
@@ -766,15 +782,12 @@ static int resolve_specialized(PatchHandle& h, uint32_t flags, uint32_t n_sample
     d->last_bank_lds = d->bank_lds[out_mode];
     *out = d->jit[out_mode].get();
     *with_ctl = ctl;
+    pick.name = "render_specialized";
+    pick.stats_in_kernel = pick.paced = false;  // (a specialised kernel never carries the statistics: asked for them, it writes frames — the host's or scratch — to fold)
+    // A specialised kernel without rings in HBM at one wave per SIMD or fewer is in the z^-1 FM pair's position (config 4 through the
+    // general path: 7.36 - 7.46 ms per step at 4096, 7.26 - 7.28 at 2048, two rounds on one box)
+    if (P.hdr.n_rings == 0 && n_waves <= 1024 && !(flags & SRACK_RENDER_EXACT_OSC)) pick.chunk = std::min(knobs().chunk_max, 2048u);
     return SRACK_OK;
-}
-
-// Per-voice statistics (srack_render_stats): the fused voice chains, render_voice_chain and the flagship render_voice_chain_track,
-// accumulate them in registers as they emit (wave.hip.h, EmitStats: no frames need to exist); every other kernel's frames are folded
-// after each launch (stats_fold).  Neither changes which kernel renders, the chunks, or any bit of frames, mix or state.
-static bool stats_in_kernel(const FlatProgram& P, const JitKernel* special)
-{
-    return !special && (P.fused == FUSED_VOICE_CHAIN || P.fused == FUSED_VOICE_CHAIN_TRACK);
 }
 
 static void launch_ctl(const FlatProgram& Cp, const KernelArgs& kc, hipStream_t st)
@@ -784,14 +797,8 @@ static void launch_ctl(const FlatProgram& Cp, const KernelArgs& kc, hipStream_t 
                   Cp.ops[0].flags & (OSC_OUT_SINE | OSC_OUT_SQUARE | OSC_OUT_SAW | OSC_EXACT), nullptr, 0u};
         hipLaunchKernelGGL(render_ctl_gate_env, dim3(1), dim3(64), 0, st, w);
     } else if (Cp.fused == FUSED_FM_PAIR) {
-        ChainRoles roles{};
-        roles.adsr = 1;
-        roles.osc_l = 2;
-        roles.vca = 4;
-        roles.osc_a = 5;
-        roles.out = 6;
-        roles.track = Cp.ops[0].aux;
-        launch_fm_pair(Cp.fused_variant == 1, (Cp.render_flags & SRACK_RENDER_EXACT_OSC) != 0, 1, kc, roles, dim3(1), st);
+        const bool exact = (Cp.render_flags & SRACK_RENDER_EXACT_OSC) != 0;
+        launch_fm_pair(fm_pair_kernel(Cp.fused_variant, exact), exact, 1, kc, fm_pair_roles(Cp), dim3(1), st);
     } else {
         launch_interp(Cp, kc, st);
     }
@@ -857,14 +864,6 @@ extern "C" int srack_census_read(uint32_t* out, uint32_t max_slots, uint32_t* sl
 // How a render is scheduled.  Without a control program: one launch of the voice kernel.  With one: the
 // render is cut into chunks; control chunk k (one wave, a latency chain) runs on its own stream and voice
 // chunk k waits only for it, so all but the first control chunk hide behind voice kernels of earlier chunks.
-static uint32_t lanes_per_wave(uint32_t V)
-{
-    const uint32_t want_waves = knobs().want_waves;
-    uint32_t lanes = 64;
-    while (lanes > 16 && (V + lanes - 1) / lanes * 2 <= want_waves) lanes >>= 1;
-    return lanes;
-}
-
 // One segment [t_seg, t_seg + T) of a render of T_total samples (d_frames / d_mix point at the WHOLE render's buffers), in the order it is
 // carried out: prepare (silence, scratch) -> plan (which kernel, how the control program overlaps, the chunk schedule, tick session or
 // not) -> control (what the control program must have finished before the first voice launch; a session's bookkeeping) -> roles (the
@@ -887,13 +886,7 @@ struct Segment {
     uint32_t bus_slab = 0;  // rows the fold takes at a time (the pitch of its partials)
     const hipStream_t st;
     int rc = SRACK_OK;
-    // Voices per wave.  A full wave (64) is right whenever there are enough voices to give every SIMD work.
-    // With few voices, half- or quarter-filled waves double / quadruple the number of waves: a VALU instruction
-    // costs the same for 16 lanes as for 64, so this only pays while SIMDs would otherwise sit idle (VALU-bound
-    // kernels: up to one wave per SIMD) or while waves are latency-bound (FM pair, interpreter: up to four).
-    const bool fm_block;  // 32 voices per workgroup, whatever the voice count
-    const bool fm_block_x;  // ... the same with the modulator exact (render_fm_pair_block_x)
-    const bool fm_x_z1;     // the z^-1 pair with the modulator exact (render_fm_pair_x)
+    KernelPick pick;  // which kernel renders (plan() asks resolve_specialized whether a specialised one takes over)
     const uint32_t lanes, n_waves;
     // plan
     bool has_ctl = false, co_ctl = false, special_ctl = false, tick = false;
@@ -905,7 +898,6 @@ struct Segment {
     ChainRoles roles{};
     SeqRoles seq{};
     uint32_t osc_port = 0, vcf_port = 0, seq_port = 0;
-    bool fused = false, track = false, seq_chain = false, fm_pair = false;
     // mix
     MixArgs m{};
     bool mix_aside = false;
@@ -913,8 +905,7 @@ struct Segment {
     Segment(PatchHandle& h_, uint32_t T_total_, uint32_t t_seg_, uint32_t T_, float* d_frames_, float* d_mix_, double* d_stats_, float* d_bus_, uint32_t flags_, hipStream_t st_)
         : h(h_), P(h_.prog.voice), d(h_.dev), tk(h_.dev->tick), V(h_.prog.voice.n_voices), C((uint32_t)h_.prog.voice.hdr.n_channels), T_total(T_total_),
           t_seg(t_seg_), T(T_), flags(flags_), d_frames(d_frames_ ? d_frames_ + (size_t)t_seg_ * h_.prog.voice.n_voices : nullptr),
-          d_mix(d_mix_ ? d_mix_ + t_seg_ : nullptr), d_stats(d_stats_), d_bus(d_bus_ ? d_bus_ + t_seg_ : nullptr), st(st_), fm_block(fm_block_shape(h_.prog.voice, flags_, T_)), fm_block_x(fm_block_x_shape(h_.prog.voice, flags_, T_)), fm_x_z1(fm_x_z1_shape(h_.prog.voice, flags_)),
-          lanes((fm_block || fm_block_x) ? (uint32_t)kBlkVoices : lanes_per_wave(h_.prog.voice.n_voices)), n_waves((h_.prog.voice.n_voices + lanes - 1) / lanes)
+          d_mix(d_mix_ ? d_mix_ + t_seg_ : nullptr), d_stats(d_stats_), d_bus(d_bus_ ? d_bus_ + t_seg_ : nullptr), st(st_), pick(pick_kernel(h_.prog, flags_, T_)), lanes(pick.lanes), n_waves((h_.prog.voice.n_voices + lanes - 1) / lanes)
     {
     }
 
@@ -938,36 +929,35 @@ struct Segment {
 
     // One argument block per (launch, control unit): launch j runs unit s on chunk j - lag[s]; chunk c is complete after launch
     // c + max_lag.  (A control program that was not cut into units is one unit with lag 0.)
-    KernelArgs stage_args(uint32_t s, uint32_t k)
+    KernelArgs unit_args(uint32_t s)  // what every launch of control unit s has: the unit's one wave is wave 0 of its program
     {
-        const uint32_t t_off = chunks[k].first, len = chunks[k].second;
         KernelArgs kc{};
         kc.ops = d->ctl[s].d_ops;
         kc.prog = h.prog.ctl[s].hdr;
+        kc.seqtab = d->ctl[s].d_seqtab;
+        kc.V = 1;
+        kc.n_waves = 1;
+        kc.lanes = 64;
+        kc.block0 = s;
+        return kc;
+    }
+    KernelArgs stage_args(uint32_t s, uint32_t k)
+    {
+        const uint32_t t_off = chunks[k].first, len = chunks[k].second;
+        KernelArgs kc = unit_args(s);
         kc.table = d->ctl[s].d_table;
         kc.rings = d->ctl[s].d_rings;
-        kc.seqtab = d->ctl[s].d_seqtab;
         kc.fv = d->ctl[s].d_fv;
         kc.frames = d->d_tracks + t_off;  // the control program's planes are the tracks: [n_tracks][T][1]
         kc.tracks = d->d_tracks + t_off;  // ... and later stages read earlier stages' tracks from the same buffer
         kc.plane_stride = T;
         kc.t_stride = T;
-        kc.V = 1;
         kc.T = len;
-        kc.n_waves = 1;
-        kc.lanes = 64;
         kc.n0 = h.samples_rendered + t_off;
         return kc;
     }
-    int upload_stage_slots(hipStream_t on)
+    int upload_slots(hipStream_t on)  // h_stage_slots to the device
     {
-        d->h_stage_slots.assign((size_t)n_ctl_launch * n_stages, KernelArgs{});
-        for (uint32_t s2 = 0; s2 < n_stages; s2++)
-            for (uint32_t k = 0; k < n_chunks; k++) {
-                KernelArgs& slot = d->h_stage_slots[(size_t)(k + (uint32_t)h.prog.ctl_lag[s2]) * n_stages + s2];
-                slot = stage_args(s2, k);
-                slot.block0 = s2;  // the unit's one wave is wave 0 of its program
-            }
         const size_t bytes = sizeof(KernelArgs) * d->h_stage_slots.size();
         if (bytes > d->stage_slots_cap) {
             (void)hipFree(d->d_stage_slots);
@@ -978,6 +968,13 @@ struct Segment {
         }
         HIP_TRY(hipMemcpyAsync(d->d_stage_slots, d->h_stage_slots.data(), bytes, hipMemcpyHostToDevice, on));
         return SRACK_OK;
+    }
+    int upload_stage_slots(hipStream_t on)
+    {
+        d->h_stage_slots.assign((size_t)n_ctl_launch * n_stages, KernelArgs{});
+        for (uint32_t s2 = 0; s2 < n_stages; s2++)
+            for (uint32_t k = 0; k < n_chunks; k++) d->h_stage_slots[(size_t)(k + (uint32_t)h.prog.ctl_lag[s2]) * n_stages + s2] = stage_args(s2, k);
+        return upload_slots(on);
     }
     // ---- tick session: argument blocks of unit s2 on chunk x, and the launches that start a session ----
     float* tick_tracks(uint64_t x)
@@ -1000,22 +997,15 @@ struct Segment {
     }
     KernelArgs tick_unit_args(uint32_t s2, uint64_t x)
     {
-        KernelArgs kc{};
-        kc.ops = d->ctl[s2].d_ops;
-        kc.prog = h.prog.ctl[s2].hdr;
+        KernelArgs kc = unit_args(s2);
         kc.table = tick_table(s2, x);
         kc.table_out = tick_table(s2, x + 1);
-        kc.seqtab = d->ctl[s2].d_seqtab;
         kc.frames = tick_tracks(x);
         kc.tracks = kc.frames;
         kc.plane_stride = tk.S;
         kc.t_stride = tk.S;
-        kc.V = 1;
         kc.T = tick_len(x);
-        kc.n_waves = 1;
-        kc.lanes = 64;
         kc.n0 = tick_n0(x);
-        kc.block0 = s2;
         return kc;
     }
     CtlWork tick_work(uint64_t x)
@@ -1036,15 +1026,7 @@ struct Segment {
                 for (uint32_t g = lag; g < fill; g++) d->h_stage_slots[(size_t)g * n_stages + s2] = tick_unit_args(s2, g - lag);
             for (uint32_t i = 0; i < batch; i++) d->h_stage_slots[(size_t)(fill + i) * n_stages + s2] = tick_unit_args(s2, base + i + fill - lag);
         }
-        const size_t bytes = sizeof(KernelArgs) * d->h_stage_slots.size();
-        if (bytes > d->stage_slots_cap) {
-            (void)hipFree(d->d_stage_slots);
-            d->d_stage_slots = nullptr;
-            d->stage_slots_cap = 0;
-            HIP_TRY(hipMalloc(&d->d_stage_slots, bytes));
-            d->stage_slots_cap = bytes;
-        }
-        HIP_TRY(hipMemcpyAsync(d->d_stage_slots, d->h_stage_slots.data(), bytes, hipMemcpyHostToDevice, st));
+        if ((rc = upload_slots(st)) != SRACK_OK) return rc;
         tk.slots_base = base;
         tk.slots_n = batch;
         return SRACK_OK;
@@ -1143,10 +1125,9 @@ struct Segment {
         n_stages = (uint32_t)h.prog.ctl.size();
         co_ctl = has_ctl && P.fused == FUSED_VOICE_CHAIN_TRACK && n_stages == 1 && h.prog.ctl[0].fused == FUSED_CTL_GATE_ENV && h.prog.n_tracks == 1;
         {
-            // (a specialised kernel never carries the statistics: asked for them, it writes frames — the host's or scratch — to fold)
             const int om = (d_frames || d_stats || d_bus ? 1 : 0) | (d_mix ? 2 : 0);
-            if ((rc = resolve_specialized(h, flags, T, om ? om : 4, &special, &special_ctl)) != SRACK_OK) return rc;
-            fold = d_stats && !stats_in_kernel(P, special);
+            if ((rc = resolve_specialized(h, pick, flags, om ? om : 4, &special, &special_ctl)) != SRACK_OK) return rc;
+            fold = d_stats && !pick.stats_in_kernel;
         }
         // chunk schedule: short first chunks (only control chunk 0 is exposed), doubling up to kChunkMax
         // With a control pipeline of depth L the first voice chunk waits for L + 1 control launches: those stay short.
@@ -1178,17 +1159,8 @@ struct Segment {
                 len = std::min(len, T - t_off);
                 chunks.emplace_back(t_off, len);
             }
-        } else {  // no control program to overlap with, but short launches still win: the waves of a launch stay within a few
-                  // samples of each other, so their frame rows land in the same DRAM pages (FM pair 13.2 -> 9.9 ms per step)
-            // The z^-1 FM pair (one wave per SIMD at config 4's 65 536 voices, no ring traffic) wants them shorter still: 2048 samples 7.26 ms per
-            // step, 4096 7.39, 1536 7.31, 1024 7.43, 8192 7.85 (tools/ab_env.sh, one box); its ring variant and the flagship are flat from 3072 to 6144.
-            // A specialised kernel without rings in HBM at one wave per SIMD or fewer is in the same position (config 4 through the general
-            // path: 7.36 - 7.46 ms per step at 4096, 7.26 - 7.28 at 2048, two rounds on one box).
-            const bool fm_z1 = fm_x_z1 || (P.fused == FUSED_FM_PAIR && P.fused_variant == 0 && !(flags & (SRACK_RENDER_NO_FUSION | SRACK_RENDER_EXACT_OSC)));
-            const bool lone_waves = special && P.hdr.n_rings == 0 && n_waves <= 1024 && !(flags & SRACK_RENDER_EXACT_OSC);
-            // (the time-parallel FM pair keeps its ring in LDS for a launch and moves it to and from HBM at the ends: one launch per segment)
-            const uint32_t len = (fm_block || fm_block_x) ? knobs().fm_block_chunk : (fm_z1 || lone_waves) ? std::min(kChunkMax, 2048u) : kChunkMax;
-            for (uint32_t t_off = 0; t_off < T; t_off += len) chunks.emplace_back(t_off, std::min(len, T - t_off));
+        } else {  // no control program to overlap with: launches of the length the kernel wants (pick_kernel)
+            for (uint32_t t_off = 0; t_off < T; t_off += pick.chunk) chunks.emplace_back(t_off, std::min(pick.chunk, T - t_off));
         }
         n_chunks = (uint32_t)chunks.size();
         n_ctl_launch = n_chunks + max_lag;
@@ -1301,10 +1273,7 @@ struct Segment {
             if (staged) {
                 const uint32_t n_launch = n_ctl_launch;
                 size_t lds = 0;
-                for (uint32_t s2 = 0; s2 < n_stages; s2++) {
-                    const DevProgram& H = h.prog.ctl[s2].hdr;
-                    lds = std::max(lds, ((size_t)H.n_rows + 2 + (size_t)H.n_tracks + (size_t)H.n_slots * H.tile) * 256);
-                }
+                for (uint32_t s2 = 0; s2 < n_stages; s2++) lds = std::max(lds, interp_lds_bytes(h.prog.ctl[s2].hdr));
                 if ((rc = upload_stage_slots(d->ctl_stream)) != SRACK_OK) return rc;
                 for (uint32_t j = 0; j < n_launch; j++) {
                     const KernelArgs* slots = d->d_stage_slots + (size_t)j * n_stages;
@@ -1327,12 +1296,11 @@ struct Segment {
         return SRACK_OK;
     }
 
-    // ---- roles: which op is what for the hand-written kernels, and the kernel's name for srack_render_info --------------------------------
+    // ---- roles: which op is what for the hand-written kernels ----------------------------------------------------------------------------
     void pick_roles()
     {
-        fused = P.fused == FUSED_VOICE_CHAIN || P.fused == FUSED_VOICE_CHAIN_TRACK;
-        track = P.fused == FUSED_VOICE_CHAIN_TRACK;
-        if (fused) {
+        const bool track = pick.kernel == Kernel::VoiceChainTrack;
+        if (track || pick.kernel == Kernel::VoiceChain) {
             for (int i = 0; i < (int)P.ops.size(); i++) {
                 const DevOp& op = P.ops[(size_t)i];
                 if (op.kind == OP_VCF) { roles.vcf = i; vcf_port = op.flags & (VCF_OUT_LP | VCF_OUT_BP | VCF_OUT_HP); }
@@ -1345,13 +1313,7 @@ struct Segment {
             roles.osc_a = P.op_of_module[(size_t)g.modules[(size_t)P.ops[(size_t)roles.vcf].module].in[0].src];
             if (!track) roles.osc_l = P.op_of_module[(size_t)g.modules[(size_t)P.ops[(size_t)roles.adsr].module].in[0].src];
             osc_port = P.ops[(size_t)roles.osc_a].flags & (OSC_OUT_SINE | OSC_OUT_SQUARE | OSC_OUT_SAW);
-            d->kernel_name = track ? "render_voice_chain_track" : "render_voice_chain";
-        } else {
-            d->kernel_name = "render_interp";
-        }
-
-        seq_chain = P.fused == FUSED_VOICE_CHAIN_SEQ;
-        if (seq_chain) {
+        } else if (pick.kernel == Kernel::SeqChain) {
             seq.math = seq.trk_cutoff = -1;
             auto track_row = [&](int slot) { return P.hdr.track_id[slot - kTrackSlot]; };
             for (int i = 0; i < (int)P.ops.size(); i++) {
@@ -1370,18 +1332,8 @@ struct Segment {
                 }
             }
             if (seq.math < 0) seq.trk_pitch = track_row(P.ops[(size_t)seq.osc].in_slot[0]);
-            d->kernel_name = "render_voice_chain_seq";
-        }
-        if (special) d->kernel_name = "render_specialized";
-        fm_pair = P.fused == FUSED_FM_PAIR || fm_block_x || fm_x_z1;
-        if (fm_pair) {  // op order fixed by the matcher: DELAY_RD, MATH_FB, OSC_M, DELAY_WR, MATH_IDX, OSC_C, OUT
-            roles.adsr = 1;
-            roles.osc_l = 2;
-            roles.vca = 4;
-            roles.osc_a = 5;
-            roles.out = 6;
-            roles.track = P.ops[0].aux;  // the ring's state row
-            if (!special) d->kernel_name = fm_x_z1 ? "render_fm_pair_x" : fm_block_x ? "render_fm_pair_block_x" : fm_block ? "render_fm_pair_block" : P.fused_variant == 1 ? "render_fm_pair_ring" : "render_fm_pair";
+        } else if (pick.kernel != Kernel::Interp) {  // the FM pairs
+            roles = fm_pair_roles(P);
         }
     }
 
@@ -1409,7 +1361,7 @@ struct Segment {
                 d->ev_mix.push_back(e);
             }
         }
-        const bool paced = fused && track && !special && knobs().pace;
+        const bool paced = pick.paced, exact = (flags & SRACK_RENDER_EXACT_OSC) != 0;
         if (paced && !d->d_pace) HIP_TRY(hipMalloc(&d->d_pace, sizeof(uint32_t) * dev::kPaceKeys * kPaceSlices));
         for (uint32_t k = 0; k < n_chunks; k++) {
             const uint32_t t_off = chunks[k].first, len = chunks[k].second;
@@ -1462,28 +1414,30 @@ struct Segment {
                 if ((rc = get_event(e0)) != SRACK_OK || (rc = get_event(e1)) != SRACK_OK) return rc;
                 HIP_TRY(hipEventRecord(e0, st));
             }
+            const int out_mode = (ka.frames ? 1 : 0) | (ka.mixpart ? 2 : 0);
             if (special) {
                 if ((rc = jit_launch(*special, ka, n_waves + ka.block0, st)) != SRACK_OK) return rc;
-            } else if (fused) {
-                const int out_mode = (ka.frames ? 1 : 0) | (ka.mixpart ? 2 : 0) | (ka.stats ? kOutStats : 0);
-#ifdef SRK_WAVE_CENSUS
-                if (track && (rc = census_arm(n_waves + 1, st)) != SRACK_OK) return rc;
-#endif
-                launch_fused(osc_port, vcf_port, (flags & SRACK_RENDER_EXACT_OSC) != 0, out_mode, track, ka, roles, co, dim3(n_waves + ka.block0), st);
-            } else if (seq_chain) {
-                const int out_mode = (ka.frames ? 1 : 0) | (ka.mixpart ? 2 : 0);
-                launch_seq(seq_port, out_mode, ka, seq, dim3(n_waves), st);
-            } else if (fm_pair && fm_x_z1) {
-                launch_fm_pair_x((ka.frames ? 1 : 0) | (ka.mixpart ? 2 : 0), ka, roles, dim3(n_waves), st);
-            } else if (fm_pair && fm_block_x) {
-                if ((rc = launch_fm_block_x((ka.frames ? 1 : 0) | (ka.mixpart ? 2 : 0), ka, roles, st)) != SRACK_OK) return rc;
-            } else if (fm_pair && fm_block) {
-                if ((rc = launch_fm_block((ka.frames ? 1 : 0) | (ka.mixpart ? 2 : 0), ka, roles, st)) != SRACK_OK) return rc;
-            } else if (fm_pair) {
-                const int out_mode = (ka.frames ? 1 : 0) | (ka.mixpart ? 2 : 0);
-                launch_fm_pair(P.fused_variant == 1, (flags & SRACK_RENDER_EXACT_OSC) != 0, out_mode, ka, roles, dim3(n_waves), st);
             } else {
-                launch_interp(P, ka, st);
+                switch (pick.kernel) {
+                case Kernel::VoiceChainTrack:
+#ifdef SRK_WAVE_CENSUS
+                    if ((rc = census_arm(n_waves + 1, st)) != SRACK_OK) return rc;
+#endif
+                    [[fallthrough]];
+                case Kernel::VoiceChain:
+                    launch_fused(osc_port, vcf_port, exact, out_mode | (ka.stats ? kOutStats : 0), pick.kernel == Kernel::VoiceChainTrack, ka, roles, co, dim3(n_waves + ka.block0), st);
+                    break;
+                case Kernel::SeqChain: launch_seq(seq_port, out_mode, ka, seq, dim3(n_waves), st); break;
+                case Kernel::FmPairX: launch_fm_pair_x(out_mode, ka, roles, dim3(n_waves), st); break;
+                case Kernel::FmPairBlock:
+                case Kernel::FmPairBlockX:
+                    if ((rc = launch_fm_block(pick.kernel == Kernel::FmPairBlockX, out_mode, ka, roles, st)) != SRACK_OK) return rc;
+                    break;
+                case Kernel::FmPair:
+                case Kernel::FmPairRing:
+                case Kernel::FmPairSplit: launch_fm_pair(pick.kernel, exact, out_mode, ka, roles, dim3(n_waves), st); break;
+                case Kernel::Interp: launch_interp(P, ka, st); break;
+                }
             }
             HIP_TRY(hipGetLastError());
             if (fold) {  // behind the launch on its stream; the next launch's writes to d_stat_frames wait for it
@@ -1574,6 +1528,7 @@ struct Segment {
             }
         } tick_guard{h, tk};
         if ((rc = plan()) != SRACK_OK || (rc = control()) != SRACK_OK) return rc;
+        d->kernel_name = pick.name;
         pick_roles();
         if ((rc = voices()) != SRACK_OK || (rc = mix()) != SRACK_OK || (rc = finish()) != SRACK_OK) return rc;
         tick_guard.done = true;
@@ -1630,7 +1585,8 @@ int device_reserve(PatchHandle& h, uint32_t n_samples, bool want_mix, uint32_t f
     const FlatProgram& P = h.prog.voice;
     const uint32_t T = std::min(n_samples, 65536u);  // one segment
     const uint32_t eff = h.prog.effective_flags | (flags & kLaunchPolicyFlags);
-    const uint32_t lanes = (fm_block_shape(P, eff, T) || fm_block_x_shape(P, eff, T)) ? (uint32_t)kBlkVoices : lanes_per_wave(P.n_voices), n_waves = (P.n_voices + lanes - 1) / lanes;
+    KernelPick pick = pick_kernel(h.prog, eff, T);
+    const uint32_t n_waves = (P.n_voices + pick.lanes - 1) / pick.lanes;
     if (want_mix && P.hdr.n_planes > 0) {
         if ((rc = grow(d->d_mixpart, d->mixpart_bytes, sizeof(float) * (size_t)P.hdr.n_planes * n_waves * T)) != SRACK_OK) return rc;
         if ((rc = grow(d->d_mixgroup, d->mixgroup_bytes, sizeof(float) * (size_t)P.hdr.n_planes * kMixSplit * T)) != SRACK_OK) return rc;
@@ -1638,8 +1594,7 @@ int device_reserve(PatchHandle& h, uint32_t n_samples, bool want_mix, uint32_t f
     if (h.prog.n_tracks > 0 && (rc = grow(d->d_tracks, d->tracks_bytes, sizeof(float) * (size_t)h.prog.n_tracks * T)) != SRACK_OK) return rc;
     const JitKernel* special = nullptr;  // compile now what the first render would otherwise compile (frames + mix, or frames only)
     bool special_ctl = false;
-    if ((rc = resolve_specialized(h, h.prog.effective_flags | (flags & kLaunchPolicyFlags), T, want_mix ? 3 : 1, &special, &special_ctl)) != SRACK_OK) return rc;
-    return SRACK_OK;
+    return resolve_specialized(h, pick, eff, want_mix ? 3 : 1, &special, &special_ctl);
 }
 
 int device_kernel_ms(PatchHandle& h, double* avg_ms, int* n_launches, int reset)

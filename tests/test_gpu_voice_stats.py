@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import srack_pkg
+from tests.patch_makers import bits, p2_overrides, patch_maker, workload_maker
 
 pytestmark = pytest.mark.gpu
 
@@ -44,10 +45,6 @@ def assert_stats_equal(got, want):
     assert got.shape == want.shape
     for k in range(6):  # every field bit for bit (peaks included: a peak of nothing is +0.0)
         np.testing.assert_array_equal(np.ascontiguousarray(got[:, k]).view(np.uint64), np.ascontiguousarray(want[:, k]).view(np.uint64), err_msg=f"field {k}")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def make_p1(S, V, B=1024, adsr="default", nan_voices=()):
@@ -210,17 +207,6 @@ def test_full_width(S):
 
 
 # ---- every other kernel: the statistics folded from each launch's frames (stats_fold) -------------------------------------------------
-def patch_maker(S, B, build, overrides, V):
-    def make():
-        p = S.Patch(48000, B, 2)
-        ids = build(p)
-        p.configure_voices(V)
-        for m, f, v in overrides(ids):
-            p.set_voice_field(m, f, v)
-        return p
-    return make
-
-
 def check_all_routes(S, make, T, flags, kernels=None):
     """frames + mix + stats against the loop over those frames; frames and mix against a plain render; statistics alone and mix +
     statistics (the kernel writes frames nobody asked for into the library's scratch) give the same bits"""
@@ -238,11 +224,6 @@ def check_all_routes(S, make, T, flags, kernels=None):
     assert_stats_equal(st2, st)
     np.testing.assert_array_equal(bits(mx2), bits(mx0))
     return fr, st
-
-
-def p2_overrides(S, V):
-    beta, index = S.p2_voice_params(V)
-    return lambda ids: [(ids["mul_fb"], S.MATH_CONSTANT, beta), (ids["mul_idx"], S.MATH_CONSTANT, index)]
 
 
 KEEP, EXACT, NO_FUSION, NO_SPEC, SPEC = 64, 1, 2, 16, 32
@@ -267,11 +248,7 @@ OTHER_KERNELS = [
 
 @pytest.mark.parametrize("w,B,V,T,flags,kernels", OTHER_KERNELS)
 def test_other_kernels_fold_the_same_statistics(S, w, B, V, T, flags, kernels):
-    if w == "p2":
-        make = patch_maker(S, B, S.build_p2, p2_overrides(S, V), V)
-    else:
-        B2, build, overrides = S.bench_workload(w, V)
-        make = patch_maker(S, B2, build, overrides, V)
+    make = workload_maker(S, w, B, V)
     fr, st = check_all_routes(S, make, T, flags, kernels)
     assert st.shape[0] == make().planes()[0]
     # run to run: the same bits again

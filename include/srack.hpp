@@ -184,6 +184,19 @@ public:
     }
     void set_voice_sequences(const SharedSynthModule& m, const int* seq) { check(srack_voices_set_sequences(p_, m.index(), seq)); }  // nullptr clears
     uint32_t get_voice_sequences(const SharedSynthModule& m, int* seq = nullptr, uint32_t cap = 0) const { return (uint32_t)check(srack_voices_get_sequences(p_, m.index(), seq, cap)); }
+    // A stereo Freeverb per mix bus, behind the mixer: params f64 [n_buses][SRACK_FREEVERB__NFIELDS] in FreeverbModule's field order
+    // (nullptr: the module's defaults), enabled [n_buses] (nullptr: every bus).  Calling set_bus_reverbs again is the slider: the
+    // coefficients change, the tails stay.  Not part of the program: restarts nothing, and the tails carry on across an edit of the patch.
+    void set_bus_reverbs(const double* params = nullptr, const int* enabled = nullptr) { check(srack_buses_set_reverb(p_, params, enabled)); }
+    uint32_t get_bus_reverbs(double* params = nullptr, int* enabled = nullptr, uint32_t cap = 0) const { return (uint32_t)check(srack_buses_get_reverb(p_, params, enabled, cap)); }
+    void reset_bus_reverbs() { check(srack_buses_reset_reverb(p_)); }  // lines and filter states to zero; the parameters stay
+    void bus_reverb_plan(int* line_lengths /* 24 */, int* block) const { check(srack_buses_reverb_plan(p_, line_lengths, block)); }
+    // d_bus_mix f32 [n_buses][channels][n_samples] -> d_bus_fx f32 [n_buses][2][n_samples] (no overlap), asynchronous on `stream`.  A sharded
+    // host reduces the per-rank bus mixes first and reverberates on the root.
+    void bus_reverb(uint32_t n_samples, const float* d_bus_mix, float* d_bus_fx, void* stream = nullptr)
+    {
+        check(srack_buses_reverb(p_, n_samples, d_bus_mix, d_bus_fx, stream));
+    }
     // execute_batch plus d_bus_mix, f32 [n_buses][channels][n_samples] (written); d_frames, d_mix, d_stats may each be null
     void execute_batch_buses(uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags = 0, void* stream = nullptr)
     {

@@ -452,6 +452,51 @@ int srack_voices_bus_plan(const srack_patch* p, int* segments, uint32_t segment_
 int srack_render_buses(srack_patch* p, uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats,
                        float* d_bus_mix, uint32_t flags, void* stream);
 
+/* ---- bus reverbs: a stereo Freeverb per mix bus, behind the mixer ------------------------------------------------
+ * In real patches FreeverbModule sits behind the mixer, on the sum: the voices of a bus share one room.  Every bus may carry one
+ * reverb.  The reverb of bus b renders what FreeverbModule renders (SRACK_MOD_FREEVERB above: the freeverb crate restated, f64, one
+ * rounding per operation), configured by the module's six parameters and ticked once per sample with
+ *   in0 = (double)bus_mix[b][0][t],  in1 = (double)bus_mix[b][1][t]  (0.0 for a patch of one channel: the module with Right
+ *   unconnected; channels beyond the second are ignored),            fx[b][0][t] = (float)out0,  fx[b][1][t] = (float)out1.
+ * A patch whose sample rate is below 784 Hz has no Freeverb (SRACK_ERR_UNSUPPORTED, as for the module).
+ *
+ * set_reverb: params is f64 [n_buses][SRACK_FREEVERB__NFIELDS] in the module's field order (DAMPENING, FREEZE, WET, WIDTH, ROOM_SIZE,
+ * DRY), NULL = the module's defaults (0.5, 0, 1, 0.5, 0.5, 0) for every bus; ANY f64 is accepted, as the reference accepts any (a NaN
+ * parameter makes that bus's output NaN and touches no other bus); FREEZE is zero or non-zero.  enabled is int [n_buses], zero = the
+ * bus has no reverb, NULL = every bus has one.  A bus without a reverb costs no state; its fx rows are the bus mix's channels 0 and 1,
+ * copied (channel 1 zeros for a patch of one channel).
+ * Calling it again is the reference's slider (set_freeverb(false)): the coefficients change, delay lines and filter states stay.  A
+ * bus enabled later starts with a fresh reverb (zeroed lines); disabling a bus drops its state.
+ * The reverbs are NOT part of the patch's program: setting, changing or ticking them does not re-flatten, restarts nothing, changes no
+ * bit of frames, mix, statistics, bus mixes or voice state and not the kernel a patch renders with; they carry on across an edit that
+ * re-flattens the patch.  srack_voices_configure drops parameters and state; so does srack_voices_set_buses with another n_buses
+ * (with the same n_buses both stay).  Rack files carry nothing of this (no counterpart in the reference).
+ * SRACK_ERR_INVALID for a null handle; SRACK_ERR_STATE for any of the five calls before srack_voices_configure or before a mix table
+ * exists, and for srack_buses_reverb / srack_buses_reset_reverb before srack_buses_set_reverb.  A failed call leaves the earlier
+ * setting in place.
+ * get_reverb copies up to cap buses (either pointer may be NULL) and returns n_buses, or 0 when no reverbs are set.
+ * reset_reverb: delay lines and filter states to zero, the sample counter to 0; the parameters stay.
+ * reverb_plan (diagnostics: tests, tools): the 24 line lengths at the patch's sample rate — line = 2 * unit + channel, units 0..7 the
+ * combs, 8..11 the allpasses; (uint32_t)(tuning * sample_rate / 44100.0), the right channel's tuning the left's plus 23 — and the number
+ * of samples the kernel takes at a time, min(256, shortest line).  Either pointer may be NULL.
+ *
+ * srack_buses_reverb is an entry of its own, not one more pointer on srack_render_buses: it runs on whatever bus mix the host hands it.
+ * A sharded host reduces the per-rank bus mixes first (srack_dist_reduce_mix) and reverberates on the root — the reverb of a sum is
+ * not, bit for bit, the sum of reverbs.
+ *   d_bus_mix : device, f32 [n_buses][channels][n_samples]      (what srack_render_buses writes)
+ *   d_bus_fx  : device, f32 [n_buses][2][n_samples], written; must not overlap d_bus_mix (SRACK_ERR_INVALID)
+ *   stream    : as for srack_render: asynchronous, and the library touches the stream only during the call.
+ * One sample counter per handle counts the samples processed since the last reset; every line's position is counter mod length, so
+ * the result does not depend on how the samples are cut into calls (a fresh reverb is all zeros, whatever its position: one counter
+ * serves reverbs enabled at different times).  State per enabled bus: 16 filter states and the 24 lines in f64 on the device (about
+ * 220 KB at 48 kHz), allocated at the first call that needs it; SRACK_ERR_NOMEM if that fails.  The kernel takes a workgroup per bus
+ * and min(256, shortest line) samples at a time (csrc/busfx.hip.h).  srack_render_info says " busfx=<enabled>[block <T>]" once a call has run. */
+int srack_buses_set_reverb(srack_patch* p, const double* params, const int* enabled);
+int srack_buses_get_reverb(const srack_patch* p, double* params, int* enabled, uint32_t cap);
+int srack_buses_reset_reverb(srack_patch* p);
+int srack_buses_reverb_plan(const srack_patch* p, int* line_lengths, int* block);
+int srack_buses_reverb(srack_patch* p, uint32_t n_samples, const float* d_bus_mix, float* d_bus_fx, void* stream);
+
 /* Optional: do everything a later srack_render(p, <= n_samples, ..., flags) would do on first use — flatten the graph,
  * upload the programs and the voice table, size the scratch buffers (mix partials when want_mix, control tracks) — so
  * that the first render costs what every render costs.  Renders nothing and leaves the voice state untouched. */
@@ -466,7 +511,7 @@ int srack_render_kernel_compile(srack_patch* p, uint32_t flags);
 /* Scratch the render needs for the mix-down partials etc. is owned by the handle; this reports it. */
 /* Human-readable: the programs (ops, rows, units), "approx[...]" — the default mode's error bound or why the flavour is exact —, any
  * SRACK_* tuning variable the process carries ("knobs=[...]": such a process does not render what was tested), "buses=<n>[fold]" when the
- * last render filled the mixes of n buses (by a fold over each launch's frames), where the kernel came from, and last "kernel=<name>".  Returns the length; copies at most cap - 1 characters (buf may be NULL to ask for the length). */
+ * last render filled the mixes of n buses (by a fold over each launch's frames), "busfx=<n>[block <T>]" once the bus reverbs have run, where the kernel came from, and last "kernel=<name>".  Returns the length; copies at most cap - 1 characters (buf may be NULL to ask for the length). */
 int srack_render_info(srack_patch* p, char* buf, size_t cap);
 
 /* Average duration in ms of the dominant render kernel over the renders since the last call with

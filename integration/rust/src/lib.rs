@@ -68,6 +68,11 @@ mod ffi {
         pub fn srack_voices_set_sequences(p: *mut SrackPatch, module: c_int, seq: *const c_int) -> c_int;
         pub fn srack_voices_get_sequences(p: *const SrackPatch, module: c_int, seq: *mut c_int, cap: u32) -> c_int;
         pub fn srack_render_buses(p: *mut SrackPatch, n_samples: u32, d_frames: *mut f32, d_mix: *mut f32, d_stats: *mut f64, d_bus_mix: *mut f32, flags: u32, stream: *mut c_void) -> c_int;
+        pub fn srack_buses_set_reverb(p: *mut SrackPatch, params: *const f64, enabled: *const c_int) -> c_int;
+        pub fn srack_buses_get_reverb(p: *const SrackPatch, params: *mut f64, enabled: *mut c_int, cap: u32) -> c_int;
+        pub fn srack_buses_reset_reverb(p: *mut SrackPatch) -> c_int;
+        pub fn srack_buses_reverb_plan(p: *const SrackPatch, line_lengths: *mut c_int, block: *mut c_int) -> c_int;
+        pub fn srack_buses_reverb(p: *mut SrackPatch, n_samples: u32, d_bus_mix: *const f32, d_bus_fx: *mut f32, stream: *mut c_void) -> c_int;
         pub fn srack_device_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
         pub fn srack_device_free(d_ptr: *mut c_void) -> c_int;
         pub fn srack_device_to_host(h_dst: *mut c_void, d_src: *const c_void, bytes: usize, stream: *mut c_void) -> c_int;
@@ -372,6 +377,40 @@ impl Patch {
         let m = mix.map_or(std::ptr::null_mut(), |b| b.as_f32());
         let s = stats.map_or(std::ptr::null_mut(), |b| b.as_f64());
         check(unsafe { ffi::srack_render_buses(self.raw, n_samples, f, m, s, bus_mix.as_f32(), flags, std::ptr::null_mut()) }).map(|_| ())
+    }
+    /// A stereo Freeverb per mix bus, behind the mixer (`srack_buses_set_reverb`): `params` is `[n_buses][6]` f64 in FreeverbModule's field
+    /// order — dampening, freeze, wet, width, room size, dry; None: the module's defaults — and `enabled` `[n_buses]` (None: every bus).
+    /// Calling it again is the slider: the coefficients change, the tails stay.  Not part of the program: restarts nothing.
+    pub fn set_bus_reverbs(&mut self, params: Option<&[f64]>, enabled: Option<&[i32]>) -> Result<(), Error> {
+        let a = params.map_or(std::ptr::null(), |x| x.as_ptr());
+        let e = enabled.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        check(unsafe { ffi::srack_buses_set_reverb(self.raw, a, e) }).map(|_| ())
+    }
+    /// `(params [n_buses][6], enabled [n_buses])` of the reverbs set; None when none are.
+    pub fn get_bus_reverbs(&self) -> Result<Option<(Vec<f64>, Vec<i32>)>, Error> {
+        let n = check(unsafe { ffi::srack_buses_get_reverb(self.raw, std::ptr::null_mut(), std::ptr::null_mut(), 0) })? as usize;
+        if n == 0 {
+            return Ok(None);
+        }
+        let (mut a, mut e) = (vec![0f64; n * 6], vec![0 as c_int; n]);
+        check(unsafe { ffi::srack_buses_get_reverb(self.raw, a.as_mut_ptr(), e.as_mut_ptr(), n as u32) })?;
+        Ok(Some((a, e)))
+    }
+    /// Delay lines and filter states to zero, the sample counter to 0; the parameters stay.
+    pub fn reset_bus_reverbs(&mut self) -> Result<(), Error> {
+        check(unsafe { ffi::srack_buses_reset_reverb(self.raw) }).map(|_| ())
+    }
+    /// `(the 24 line lengths at the patch's sample rate, the samples the kernel takes at a time)`.
+    pub fn bus_reverb_plan(&self) -> Result<([i32; 24], i32), Error> {
+        let (mut l, mut b) = ([0 as c_int; 24], 0 as c_int);
+        check(unsafe { ffi::srack_buses_reverb_plan(self.raw, l.as_mut_ptr(), &mut b) })?;
+        Ok((l, b))
+    }
+    /// The bus mixes through their reverbs: `bus_mix` `[n_buses][channels][n_samples]` f32 in, `bus_fx` `[n_buses][2][n_samples]` f32 out, two
+    /// buffers that do not overlap (`srack_buses_reverb`).  A sharded host reduces the per-rank bus mixes first (`MixComm::reduce_mix`) and
+    /// reverberates on the root: the reverb of a sum is not, bit for bit, the sum of reverbs.
+    pub fn bus_reverb(&mut self, n_samples: u32, bus_mix: &DeviceBuffer, bus_fx: &DeviceBuffer) -> Result<(), Error> {
+        check(unsafe { ffi::srack_buses_reverb(self.raw, n_samples, bus_mix.as_f32() as *const f32, bus_fx.as_f32(), std::ptr::null_mut()) }).map(|_| ())
     }
 }
 

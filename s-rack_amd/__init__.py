@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libsrack_hip.so")
 
 OK, ERR_INVALID, ERR_PORT, ERR_NO_OUTPUT, ERR_SELF_LOOP, ERR_STATE, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8
 MAX_BUSES, BUS_NONE = 65536, -1
+FREEVERB_DEFAULTS = (0.5, 0.0, 1.0, 0.5, 0.5, 0.0)  # FreeverbModule's six parameters in field order: what set_bus_reverbs(None) gives every bus
 WAVE_OWN = -1
 SEQ_OWN, MAX_SEQUENCES = -1, 65536
 STAT_SUM, STAT_SUM_SQ, STAT_PEAK_POS, STAT_PEAK_NEG, STAT_NONFINITE, STAT_CLIPPED, STAT_COUNT = 0, 1, 2, 3, 4, 5, 6
@@ -32,6 +33,7 @@ ABI_SYMBOLS = [
     "srack_patch_plan", "srack_patch_plan_list", "srack_patch_removed_edges", "srack_patch_delayed_edges",
     "srack_voices_configure", "srack_voices_set_field_f32", "srack_voices_set_field_f64", "srack_render_planes", "srack_render", "srack_render_stats", "srack_render_reserve",
     "srack_voices_set_buses", "srack_voices_get_buses", "srack_voices_bus_plan", "srack_render_buses",
+    "srack_buses_set_reverb", "srack_buses_get_reverb", "srack_buses_reset_reverb", "srack_buses_reverb_plan", "srack_buses_reverb",
     "srack_patch_set_wave_bank", "srack_patch_get_wave_bank", "srack_patch_get_wave_bank_samples", "srack_voices_set_waves", "srack_voices_get_waves",
     "srack_patch_set_sequence_bank", "srack_patch_get_sequence_bank", "srack_voices_set_sequences", "srack_voices_get_sequences",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
@@ -103,6 +105,12 @@ def _load():
         L.srack_voices_get_buses.argtypes = [vp, ip, fp, u32]
         L.srack_voices_bus_plan.argtypes = [vp, ip, u32, ip, u32]
         L.srack_render_buses.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp]
+    if hasattr(L, "srack_buses_reverb"):
+        L.srack_buses_set_reverb.argtypes = [vp, dp, ip]
+        L.srack_buses_get_reverb.argtypes = [vp, dp, ip, u32]
+        L.srack_buses_reset_reverb.argtypes = [vp]
+        L.srack_buses_reverb_plan.argtypes = [vp, ip, ip]
+        L.srack_buses_reverb.argtypes = [vp, u32, vp, vp, vp]
     if hasattr(L, "srack_voices_set_waves"):  # (tools/ alternate older builds of the library under this binding)
         L.srack_patch_set_wave_bank.argtypes = [vp, i32, fp, ip, fp, u32]
         L.srack_patch_get_wave_bank.argtypes = [vp, i32, ip, fp, u32]
@@ -480,6 +488,68 @@ class Patch:
         seg, order = np.zeros((n, 4), dtype=np.intc), np.zeros(max(1, self.n_voices), dtype=np.intc)
         _check(lib.srack_voices_bus_plan(self.h, seg.ctypes.data_as(C.POINTER(C.c_int)), n, order.ctypes.data_as(C.POINTER(C.c_int)), self.n_voices))
         return seg, order[:int(seg[:, 3].sum())]
+
+    # ---- bus reverbs: a Freeverb per mix bus, behind the mixer ---------------------------------------
+    def set_bus_reverbs(self, params=None, enabled=None):
+        """srack_buses_set_reverb: params f64 [n_buses][6] in FreeverbModule's field order (FREEVERB_DAMPENING, _FREEZE, _WET, _WIDTH,
+        _ROOM_SIZE, _DRY; None: the module's defaults), enabled [n_buses] (None: every bus).  Calling it again is the slider: the
+        coefficients change, the tails stay.  Not part of the program: restarts nothing."""
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        a = e = None
+        if params is not None:
+            a = np.ascontiguousarray(params, dtype=np.float64)
+            assert a.shape == (n_buses, 6), a.shape
+        if enabled is not None:
+            e = np.ascontiguousarray(np.asarray(enabled) != 0, dtype=np.intc)
+            assert e.shape == (n_buses,), e.shape
+        _check(lib.srack_buses_set_reverb(self.h, None if a is None else a.ctypes.data_as(C.POINTER(C.c_double)),
+                                          None if e is None else e.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def get_bus_reverbs(self):
+        """-> (n_buses, params f64 [n_buses][6], enabled int32 [n_buses]); (0, None, None) when no reverbs are set"""
+        n = _check(lib.srack_buses_get_reverb(self.h, None, None, 0))
+        if n == 0:
+            return 0, None, None
+        a, e = np.empty((n, 6), dtype=np.float64), np.empty(n, dtype=np.intc)
+        _check(lib.srack_buses_get_reverb(self.h, a.ctypes.data_as(C.POINTER(C.c_double)), e.ctypes.data_as(C.POINTER(C.c_int)), n))
+        return n, a, e
+
+    def reset_bus_reverbs(self):
+        """Delay lines and filter states to zero, the sample counter to 0; the parameters stay (srack_buses_reset_reverb)."""
+        _check(lib.srack_buses_reset_reverb(self.h))
+
+    def bus_reverb_plan(self):
+        """-> (the 24 line lengths at this sample rate, line = 2 * unit + channel, combs then allpasses; samples the kernel takes at a time)"""
+        ln, blk = np.zeros(24, dtype=np.intc), C.c_int(0)
+        _check(lib.srack_buses_reverb_plan(self.h, ln.ctypes.data_as(C.POINTER(C.c_int)), C.byref(blk)))
+        return ln, blk.value
+
+    def bus_reverb_raw(self, n_samples, d_bus_mix, d_bus_fx, stream=None):
+        """Device pointers in; asynchronous on `stream` (srack_buses_reverb): d_bus_mix f32 [n_buses][channels][n], d_bus_fx f32 [n_buses][2][n]."""
+        _check(lib.srack_buses_reverb(self.h, n_samples, d_bus_mix, d_bus_fx, stream))
+
+    def bus_reverb(self, bus_mix):
+        """Convenience for tests: bus_mix f32 [n_buses][channels][T] from the host through the reverbs -> fx f32 [n_buses][2][T]."""
+        bm = np.ascontiguousarray(bus_mix, dtype=np.float32)
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        assert bm.shape[:2] == (n_buses, self.channels), bm.shape
+        T = bm.shape[2]
+        fx = np.empty((n_buses, 2, T), dtype=np.float32)
+        d_in, d_out = C.c_void_p(), C.c_void_p()
+        try:
+            _check(lib.srack_device_alloc(C.byref(d_in), max(4, bm.nbytes)))
+            _check(lib.srack_device_alloc(C.byref(d_out), max(4, fx.nbytes)))
+            if bm.nbytes:
+                _check(lib.srack_device_from_host(d_in, bm.ctypes.data_as(C.c_void_p), bm.nbytes, None))
+            self.bus_reverb_raw(T, d_in, d_out, None)
+            if fx.nbytes:
+                _check(lib.srack_device_to_host(fx.ctypes.data_as(C.c_void_p), d_out, fx.nbytes, None))
+            _check(lib.srack_device_sync(None))
+            return fx
+        finally:
+            for d in (d_in, d_out):
+                if d.value:
+                    lib.srack_device_free(d)
 
     def get_voice_field(self, module, field):
         out = np.empty(self.n_voices, dtype=np.float64)

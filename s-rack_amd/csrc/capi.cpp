@@ -10,6 +10,7 @@
 #include <thread>
 #include <vector>
 
+#include "freeverb_params.hpp"
 #include "jit.hpp"
 #include "runtime.hpp"
 
@@ -685,6 +686,7 @@ int srack_voices_configure(srack_patch* p, uint32_t n_voices)
         p->h.bus_gain.clear();
         p->h.bus_plan = BusPlan();
         p->h.bus_revision++;
+        device_busfx_drop(p->h);  // the reverbs sat behind that table
         return SRACK_OK;
     });
 }
@@ -756,6 +758,7 @@ int srack_voices_set_buses(srack_patch* p, uint32_t n_buses, const int* bus, con
         if (bus) std::copy(bus, bus + h.n_voices, b.begin());
         if (gain) std::copy(gain, gain + h.n_voices, g.begin());
         BusPlan plan = bus_plan_make(h.n_voices, n_buses, b.data());
+        if (n_buses != h.n_buses) device_busfx_drop(h);  // other buses: their reverbs go, parameters and state (the same count keeps both)
         h.n_buses = n_buses;
         h.bus = std::move(b);
         h.bus_gain = std::move(g);
@@ -819,6 +822,141 @@ int srack_render_buses(srack_patch* p, uint32_t n_samples, float* d_frames, floa
     });
 }
 
+// ---- the bus reverbs ---------------------------------------------------------------------------------------------
+static const double kFvDefaults[SRACK_FREEVERB__NFIELDS] = {0.5, 0.0, 1.0, 0.5, 0.5, 0.0};  // FreeverbModule::new (freeverb.rs:36-60), in field order
+
+// what every one of the five calls asks first
+static int busfx_preamble(const srack_patch* p, const char* who)
+{
+    CHECK_HANDLE(p);
+    const PatchHandle& h = p->h;
+    if (h.n_voices == 0) {
+        set_error(std::string(who) + ": call srack_voices_configure first");
+        return SRACK_ERR_STATE;
+    }
+    if (h.n_buses == 0) {
+        set_error(std::string(who) + ": no mix table set: call srack_voices_set_buses first");
+        return SRACK_ERR_STATE;
+    }
+    return SRACK_OK;
+}
+
+static int busfx_lines(const srack_patch* p, const char* who, uint32_t len[kFvLines], uint32_t first[kFvLines], uint32_t* total, uint32_t* block)
+{
+    if (!fv_line_lengths(p->h.graph.cfg.sample_rate, len, first, total)) {
+        set_error(std::string(who) + ": a Freeverb needs a sample rate of at least 784 Hz");
+        return SRACK_ERR_UNSUPPORTED;
+    }
+    *block = 256u;
+    for (int j = 0; j < kFvLines; j++) *block = std::min(*block, len[j]);
+    return SRACK_OK;
+}
+
+int srack_buses_set_reverb(srack_patch* p, const double* params, const int* enabled)
+{
+    return guarded([&]() -> int {
+        int rc = busfx_preamble(p, "buses_set_reverb");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        BusFx& F = h.busfx;
+        uint32_t len[kFvLines], first[kFvLines], total = 0, block = 0;
+        if ((rc = busfx_lines(p, "buses_set_reverb", len, first, &total, &block)) != SRACK_OK) return rc;
+        const size_t n = h.n_buses;
+        // (built aside: an allocation failure leaves the earlier setting in place)
+        std::vector<double> par(n * SRACK_FREEVERB__NFIELDS);
+        std::vector<uint8_t> en(n, 1);
+        for (size_t b = 0; b < n; b++) {
+            for (int f = 0; f < SRACK_FREEVERB__NFIELDS; f++) par[b * SRACK_FREEVERB__NFIELDS + f] = params ? params[b * SRACK_FREEVERB__NFIELDS + f] : kFvDefaults[f];
+            if (enabled) en[b] = enabled[b] != 0;
+        }
+        if (!F.set) {
+            F.d_state.assign(n, nullptr);
+            F.fresh.assign(n, 1);
+            F.counter = 0;
+        }
+        for (size_t b = 0; b < n; b++)
+            if (F.set && F.enabled[b] && !en[b]) device_busfx_free_bus(h, (uint32_t)b);  // disabling drops the state: enabled again, the bus starts afresh
+        std::copy(len, len + kFvLines, F.len);
+        std::copy(first, first + kFvLines, F.first);
+        F.total = total;
+        F.block = block;
+        F.params = std::move(par);
+        F.enabled = std::move(en);
+        F.tab_dirty = true;  // coefficients change, lines and filter states stay: the reference's slider, set_freeverb(false)
+        F.set = true;
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_get_reverb(const srack_patch* p, double* params, int* enabled, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_get_reverb");
+        if (rc != SRACK_OK) return rc;
+        const PatchHandle& h = p->h;
+        const BusFx& F = h.busfx;
+        if (!F.set) return 0;
+        const size_t n = std::min<size_t>(cap, h.n_buses);
+        if (params) std::copy(F.params.begin(), F.params.begin() + n * SRACK_FREEVERB__NFIELDS, params);
+        for (size_t b = 0; enabled && b < n; b++) enabled[b] = F.enabled[b];
+        return (int)h.n_buses;
+    });
+}
+
+int srack_buses_reset_reverb(srack_patch* p)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_reset_reverb");
+        if (rc != SRACK_OK) return rc;
+        BusFx& F = p->h.busfx;
+        if (!F.set) {
+            set_error("buses_reset_reverb: no reverbs set: call srack_buses_set_reverb first");
+            return SRACK_ERR_STATE;
+        }
+        std::fill(F.fresh.begin(), F.fresh.end(), (uint8_t)1);  // zeroed on the next call's stream, before its kernel
+        F.counter = 0;
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_reverb_plan(const srack_patch* p, int* line_lengths, int* block)
+{
+    return guarded([&]() -> int {
+        int rc = busfx_preamble(p, "buses_reverb_plan");
+        if (rc != SRACK_OK) return rc;
+        uint32_t len[kFvLines], first[kFvLines], total = 0, T = 0;
+        if ((rc = busfx_lines(p, "buses_reverb_plan", len, first, &total, &T)) != SRACK_OK) return rc;
+        for (int j = 0; line_lengths && j < kFvLines; j++) line_lengths[j] = (int)len[j];
+        if (block) *block = (int)T;
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_reverb(srack_patch* p, uint32_t n_samples, const float* d_bus_mix, float* d_bus_fx, void* stream)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_reverb");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        if (!h.busfx.set) {
+            set_error("buses_reverb: no reverbs set: call srack_buses_set_reverb first");
+            return SRACK_ERR_STATE;
+        }
+        if (n_samples == 0) return SRACK_OK;
+        if (!d_bus_mix || !d_bus_fx) {
+            set_error("buses_reverb: d_bus_mix and d_bus_fx must be given");
+            return SRACK_ERR_INVALID;
+        }
+        const uintptr_t in0 = (uintptr_t)d_bus_mix, out0 = (uintptr_t)d_bus_fx;
+        const uint64_t in_bytes = 4ull * h.n_buses * h.graph.cfg.channels * n_samples, out_bytes = 4ull * h.n_buses * 2 * n_samples;
+        if (in0 < out0 + out_bytes && out0 < in0 + in_bytes) {
+            set_error("buses_reverb: d_bus_fx overlaps d_bus_mix");
+            return SRACK_ERR_INVALID;
+        }
+        return device_buses_reverb(h, n_samples, d_bus_mix, d_bus_fx, stream);
+    });
+}
+
 int srack_render_reserve(srack_patch* p, uint32_t n_samples, int want_mix, uint32_t flags)
 {
     return guarded([&]() -> int {
@@ -859,6 +997,7 @@ int srack_render_info(srack_patch* p, char* buf, size_t cap)
         const char* k = device_kernel_name(p->h);
         // (the kernel's name stays LAST: hosts and tests read it with split("kernel="))
         s += device_bus_note(p->h);
+        s += device_busfx_note(p->h);
         s += device_waves_note(p->h);
         s += device_sequences_note(p->h);
         s += device_jit_note(p->h);

@@ -23,11 +23,13 @@
 #include <type_traits>
 #include <vector>
 
+#include "busfx.hip.h"
 #include "fused.hip.h"
 #include "interp.hip.h"
 #include "jit.hpp"
 #include "kernel_args.hip.h"
 #include "modules.hip.h"
+#include "freeverb_params.hpp"
 #include "runtime.hpp"
 
 namespace srack {
@@ -233,6 +235,7 @@ void device_release(DeviceState* d)
 
 PatchHandle::~PatchHandle()
 {
+    device_busfx_drop(*this);
     device_release(dev);
     device_release(dev_old);
 }
@@ -1638,6 +1641,118 @@ int device_read_rows(PatchHandle& h, int ctl_stage, int first_row, int n_rows, u
         std::memcpy(host_dst, P.table.data() + (size_t)first_row * V, sizeof(uint32_t) * V * (size_t)n_rows);
     }
     return SRACK_OK;
+}
+
+// ---- the bus reverbs (busfx.hip.h) ------------------------------------------------------------------------------------------------
+// One workgroup per bus.  The state of an enabled bus is allocated on first use and zeroed on the call's stream; the table of the
+// buses (state pointer, derived doubles) is rewritten only after a change of parameters — behind a host-side wait for the last call's
+// kernel, which may still be reading it —, so a tick session of unchanged reverbs is one launch and one event per call.
+static void busfx_wait(BusFx& F)
+{
+    if (F.ev_done) (void)hipEventSynchronize((hipEvent_t)F.ev_done);
+}
+
+void device_busfx_free_bus(PatchHandle& h, uint32_t bus)
+{
+    BusFx& F = h.busfx;
+    if (bus >= F.d_state.size() || !F.d_state[bus]) return;
+    busfx_wait(F);
+    (void)hipFree(F.d_state[bus]);
+    F.d_state[bus] = nullptr;
+    F.tab_dirty = true;
+}
+
+void device_busfx_drop(PatchHandle& h)
+{
+    BusFx& F = h.busfx;
+    busfx_wait(F);
+    for (double* p : F.d_state)
+        if (p) (void)hipFree(p);
+    if (F.d_tab) (void)hipFree(F.d_tab);
+    if (F.ev_done) (void)hipEventDestroy((hipEvent_t)F.ev_done);
+    F = BusFx();
+}
+
+int device_buses_reverb(PatchHandle& h, uint32_t n_samples, const float* d_bus_mix, float* d_bus_fx, void* stream)
+{
+    BusFx& F = h.busfx;
+    const hipStream_t st = (hipStream_t)stream;
+    const uint32_t n_buses = h.n_buses;
+    if (!F.ev_done) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        F.ev_done = e;
+    } else {
+        HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)F.ev_done, 0));  // (calls may come on different streams: the state is one)
+    }
+    const size_t state_bytes = sizeof(double) * ((size_t)kFvStates + F.total);
+    uint32_t n_enabled = 0;
+    for (uint32_t b = 0; b < n_buses; b++) {
+        if (!F.enabled[b]) continue;
+        n_enabled++;
+        if (!F.d_state[b]) {
+            void* p = nullptr;
+            if (hipMalloc(&p, state_bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("buses_reverb: out of device memory for the state of bus " + std::to_string(b) + " (" + std::to_string(state_bytes) + " bytes per enabled bus)");
+                return SRACK_ERR_NOMEM;
+            }
+            F.d_state[b] = (double*)p;
+            F.fresh[b] = 1;
+            F.tab_dirty = true;
+        }
+        if (F.fresh[b]) {  // DelayLine::new is vec![0.0; n], filter_state 0.0
+            HIP_TRY(hipMemsetAsync(F.d_state[b], 0, state_bytes, st));
+            F.fresh[b] = 0;
+        }
+    }
+    if (F.tab_dirty || !F.d_tab) {
+        std::vector<BusFxDev> tab(n_buses);
+        for (uint32_t b = 0; b < n_buses; b++) {
+            tab[b].state = F.enabled[b] ? F.d_state[b] : nullptr;
+            fv_derive(&F.params[(size_t)b * SRACK_FREEVERB__NFIELDS], tab[b].par);
+        }
+        busfx_wait(F);
+        if (F.tab_buses < n_buses) {
+            if (F.d_tab) (void)hipFree(F.d_tab);
+            F.d_tab = nullptr;
+            F.tab_buses = 0;
+            if (hipMalloc(&F.d_tab, sizeof(BusFxDev) * n_buses) != hipSuccess) {
+                (void)hipGetLastError();
+                F.d_tab = nullptr;
+                set_error("buses_reverb: out of device memory for the table of the buses");
+                return SRACK_ERR_NOMEM;
+            }
+            F.tab_buses = n_buses;
+        }
+        HIP_TRY(hipMemcpy(F.d_tab, tab.data(), sizeof(BusFxDev) * n_buses, hipMemcpyHostToDevice));
+        F.tab_dirty = false;
+    }
+    BusFxArgs a;
+    a.in = d_bus_mix;
+    a.out = d_bus_fx;
+    a.tab = (const BusFxDev*)F.d_tab;
+    a.n = n_samples;
+    a.channels = h.graph.cfg.channels;
+    a.block = F.block;
+    for (int j = 0; j < kFvLines; j++) {
+        a.len[j] = F.len[j];
+        a.first[j] = F.first[j];
+        a.pos[j] = (uint32_t)(F.counter % F.len[j]);
+    }
+    hipLaunchKernelGGL(bus_reverb, dim3(n_buses), dim3(kBusFxThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord((hipEvent_t)F.ev_done, st));
+    F.counter += n_samples;
+    F.last_enabled = n_enabled;
+    F.last_block = F.block;
+    F.ran = true;
+    return SRACK_OK;
+}
+
+std::string device_busfx_note(const PatchHandle& h)
+{
+    return h.busfx.ran ? " busfx=" + std::to_string(h.busfx.last_enabled) + "[block " + std::to_string(h.busfx.last_block) + "]" : std::string();
 }
 
 const char* device_kernel_name(const PatchHandle& h) { return h.dev ? h.dev->kernel_name : ""; }

@@ -14,6 +14,26 @@ namespace srack {
 
 struct DeviceState;  // HIP side, render.hip
 
+// The bus reverbs (srack_buses_set_reverb): one Freeverb per mix bus, behind the mixer.  NOT part of the program, and not part of
+// DeviceState either — that is replaced on every re-flatten, and a reverb's tail carries on across an edit of the patch.
+struct BusFx {
+    bool set = false;
+    std::vector<double> params;     // [n_buses][SRACK_FREEVERB__NFIELDS], as the host gave them
+    std::vector<uint8_t> enabled;   // [n_buses]
+    uint32_t len[kFvLines] = {}, first[kFvLines] = {}, total = 0;  // the lines at the patch's sample rate (freeverb_params.hpp)
+    uint32_t block = 0;             // samples the kernel takes at a time: min(256, shortest line)
+    uint64_t counter = 0;           // samples processed since the last reset: every line's position is counter mod length
+    // device side (render.hip); nothing of it exists before the first srack_buses_reverb
+    std::vector<double*> d_state;   // [n_buses] filter states + lines of an enabled bus; null: disabled, or not allocated yet
+    std::vector<uint8_t> fresh;     // [n_buses] the state is to be zeroed before the next call uses it
+    void* d_tab = nullptr;          // BusFxDev [n_buses]
+    size_t tab_buses = 0;
+    bool tab_dirty = true;
+    void* ev_done = nullptr;        // hipEvent_t recorded behind every call's kernel: the next call, and whoever frees or rewrites, waits for it
+    uint32_t last_enabled = 0, last_block = 0;  // srack_render_info, once a call has run
+    bool ran = false;
+};
+
 struct PatchHandle {
     Graph graph;
     uint32_t n_voices = 0;
@@ -48,6 +68,7 @@ struct PatchHandle {
     std::vector<float> bus_gain;
     BusPlan bus_plan;
     uint64_t bus_revision = 0;
+    BusFx busfx;                    // the bus reverbs; dropped with the table (srack_voices_configure, another n_buses)
     bool timing_armed = false;      // srack_render_kernel_ms has been called: renders bracket the dominant kernel with HIP events
 
     ~PatchHandle();
@@ -67,6 +88,11 @@ int device_read_rows(PatchHandle& h, int ctl_stage /* -1: the voice program */, 
 bool read_device_state(PatchHandle& h, int module, int field, std::vector<double>& values);
 void device_release(DeviceState* d);
 const char* device_kernel_name(const PatchHandle& h);
+// The bus reverbs: one call's work enqueued on `stream` (allocating and zeroing what is missing); state handling without a call.
+int device_buses_reverb(PatchHandle& h, uint32_t n_samples, const float* d_bus_mix, float* d_bus_fx, void* stream);
+void device_busfx_free_bus(PatchHandle& h, uint32_t bus);  // the bus's state, once no call uses it any more
+void device_busfx_drop(PatchHandle& h);                    // parameters and state of every bus
+std::string device_busfx_note(const PatchHandle& h);  // " busfx=3[block 244]" once a call has run, else ""
 std::string device_bus_note(const PatchHandle& h);  // " buses=4096[fold]" when the last render filled bus mixes, else ""
 std::string device_waves_note(const PatchHandle& h);  // " waves=9[lds]" / " waves=9[global]" for a patch that renders with a wave assignment, else ""
 std::string device_sequences_note(const PatchHandle& h);  // " sequences=9[global]" for a patch that renders with a sequence assignment, else ""

@@ -408,10 +408,24 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
         cosc_init(ca, sa.pos, ka.delta);
         if (a.T > 0) x = cosc_step<kOscAPort>(ca);
     }
-    // The envelope track is wave-uniform data written by an earlier launch: it is read through the scalar unit (constant
-    // address space => s_load_dwordx8/x16 straight into SGPRs, a tile at a time), costing no vector instruction at all.
+    // The envelope track is wave-uniform data written by an earlier launch: it is read through the scalar unit (constant address
+    // space), costing no vector instruction.  A full tile takes it eight samples at a time (uniform_load8, wave.hip.h: one
+    // s_load_dwordx8, the next eight requested while these are consumed — four loads and four waits per tile); a short last tile one
+    // dword per sample.  Left to itself the compiler loads one dword per sample, unrolled or not: the predicated PolyBLEP regions
+    // split the tile into a block per sample, and nothing is merged across blocks.
     typedef const __attribute__((address_space(4))) float CFloat;
     CFloat* env_s = (CFloat*)(uintptr_t)env_track;
+    // The VCA's gate, (negative || cv > 0) ? y * cv : 0, asks the same question of a wave-uniform cv on every sample.  It is answered
+    // once per tile instead: lane l looks at sample l & 31 of the NEXT tile (a vector load at the top of this full tile, its ballot taken
+    // after this tile's samples — in flight behind the frame stores, never waited for at once; clamped to the launch's last sample),
+    // and a full tile whose 32 values are all > 0 runs a copy of the samples with o = y * cv alone: the select would have taken the
+    // product on every one of them, whatever `negative` is.  Any other tile runs the copy that asks per sample.  a.tile_plain = 0
+    // (SRACK_TILE_PLAIN=0, tools/ and tests/): always that one — every value then looks negative to the ballot.
+    const uint32_t* env_bits = (const uint32_t*)env_track;
+    const uint32_t l32 = (uint32_t)lane & (uint32_t)(kMixRows - 1);
+    const uint32_t gate_force = a.tile_plain != 0u ? 0u : 0x80000000u;
+    auto all_pos = [&](uint32_t bits) { return __builtin_amdgcn_ballot_w64(!(((bits | gate_force) - 1u) < 0x7f800000u)) == 0; };
+    bool plain = a.T >= (uint32_t)kMixRows && all_pos(env_bits[l32]);
     // Exact mode, saw: the oscillator writes a whole tile first (modules.hip.h, XSaw: windowless values, then each lane repairs
     // its own PolyBLEP rows with the reference's f64 division), into the rows of the mix tile that the samples' outputs overwrite
     // one by one afterwards.  Its preconditions also make every filter input finite, which licenses the v_med3 clamps.
@@ -426,78 +440,120 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
     const uint32_t prio1_at = (uint32_t)(((uint64_t)a.T * SRK_PRIO_AT1) >> 6), prio0_at = (uint32_t)(((uint64_t)a.T * SRK_PRIO_AT0) >> 6);
     Pace pace = pace_join(a.pace, lane);
     __builtin_amdgcn_s_setprio(2);
-    for (uint32_t t0 = 0; t0 < a.T; t0 += kMixRows) {
-        const int n = (int)min((uint32_t)kMixRows, a.T - t0);
+    auto sample_x = [&](int i, float xin, float env, bool gated, bool pinned) __attribute__((always_inline)) {
+        float lp, bp, hp;
+        vcf_step<false, true>(sv, xin, lp, bp, hp);
+        const float y = kVcfPort == VCF_OUT_LP ? lp : (kVcfPort == VCF_OUT_BP ? bp : hp);
+        const bool cv_pos = (uint32_t)(__float_as_int(env) - 1) < 0x7f800000u;
+        const float o = (!gated || negative || cv_pos) ? y * env : 0.0f;
+        emit_put<kOut>(em, mix_tile, o, i, V);
+        if (pinned) emit_row_pin<kOut>(em);
+    };
+    auto sample = [&](int i, float env, bool gated, bool pinned) __attribute__((always_inline)) {
+        if (kExact) {
+            float sine = 0.0f, square = 0.0f, saw = 0.0f;
+            osc_step(fa, sa, ka, 0.0f, 0.0f, sine, square, saw);
+            x = kOscAPort == OSC_OUT_SINE ? sine : (kOscAPort == OSC_OUT_SQUARE ? square : saw);
+        }
+        float lp, bp, hp;
+        vcf_run<!kExact>(sv, sv_fin, x, lp, bp, hp);
+        const float y = kVcfPort == VCF_OUT_LP ? lp : (kVcfPort == VCF_OUT_BP ? bp : hp);
+        if (kFixed) {
+            fpos_lo = fa_osc.lo;
+            fpos_hi = fa_osc.hi;
+            x = fosc_saw(fa_osc);  // sample t+1
+        } else if (!kExact) {
+            pos_a = ca.pos;
+            x = cosc_step<kOscAPort>(ca);  // sample t+1
+        }
+        // vca.rs:132: (negative || cv > 0.0) ? audio * cv : 0.0 — cv is wave-uniform here, so `cv > 0.0` is decided
+        // on the scalar unit from the bit pattern: positive, non-zero, not NaN  <=>  0 < bits <= 0x7f800000
+        const bool cv_pos = (uint32_t)(__float_as_int(env) - 1) < 0x7f800000u;
+        const float o = (!gated || negative || cv_pos) ? y * env : 0.0f;  // (gated = false: the tile's 32 values are known to be > 0)
+        emit_put<kOut>(em, mix_tile, o, i, V);
+        if (pinned) emit_row_pin<kOut>(em);
+    };
+    // One full tile at t0 (constant trip count: unrollable — readlane is convergent, so a runtime count is not).  kX: the tile-wise
+    // exact saw; gated: the copy that keeps the VCA's gate.
+    auto full_tile = [&](uint32_t t0, auto kX, bool gated) __attribute__((always_inline)) {
         if (!pace.word) {
             if (t0 >= prio1_at && t0 < prio1_at + kMixRows) __builtin_amdgcn_s_setprio(1);
             if (t0 >= prio0_at && t0 < prio0_at + kMixRows) __builtin_amdgcn_s_setprio(0);
         }
-        if (xs) {
-            xsaw_tile(xo, mix_tile + lane, kMixPitch, n);
-            auto sample_x = [&](int i, float xin) {
-                const float env = env_s[t0 + (uint32_t)i];
-                float lp, bp, hp;
-                vcf_step<false, true>(sv, xin, lp, bp, hp);
-                const float y = kVcfPort == VCF_OUT_LP ? lp : (kVcfPort == VCF_OUT_BP ? bp : hp);
-                const bool cv_pos = (uint32_t)(__float_as_int(env) - 1) < 0x7f800000u;
-                const float o = (negative || cv_pos) ? y * env : 0.0f;
-                emit_put<kOut>(em, mix_tile, o, i, V);
-            };
-            if (n == kMixRows) {  // eight rows of the tile in flight per LDS round trip; a row is read before its output overwrites it
-                uint32_t pace_seen;
-                const bool pace_now = pace_step(pace, t0 / kMixRows, lane, pace_seen);
+        if (decltype(kX)::value) xsaw_tile(xo, mix_tile + lane, kMixPitch, kMixRows);
+        // pacing: the step's atomic before the tile's samples, its value looked at after them — in this block alone, so that the value
+        // is neither waited for behind the frame stores in flight nor alive anywhere else in the loop.  Likewise the next tile's gate.
+        const uint32_t gate_next = env_bits[min(t0 + (uint32_t)kMixRows + l32, a.T - 1u)];
+        uint32_t pace_seen;
+        const bool pace_now = pace_step(pace, t0 / kMixRows, lane, pace_seen);
+        // the envelope by eights, the second eight requested two samples into the first (behind the wait for the first: scalar loads
+        // return in any order, so a wait is for all of them) and so on
+        float8u e[kMixRows / 8];
+        float xin[8];
+        e[0] = uniform_load8(env_s + t0);
+#pragma unroll 32
+        for (int i = 0; i < kMixRows; i++) {
+            if ((i & 7) == 2 && i + 8 < kMixRows) e[(i >> 3) + 1] = uniform_load8(env_s + t0 + (uint32_t)((i & ~7) + 8));
+            if (decltype(kX)::value) {  // eight rows of the tile in flight per LDS round trip; a row is read before its output overwrites it
+                if ((i & 7) == 0) {
 #pragma unroll
-                for (int i0 = 0; i0 < kMixRows; i0 += 8) {
-                    float xin[8];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) xin[u] = mix_tile[(i0 + u) * kMixPitch + lane];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) sample_x(i0 + u, xin[u]);
+                    for (int u = 0; u < 8; u++) xin[u] = mix_tile[(i + u) * kMixPitch + lane];
                 }
-                if (pace_now) pace_apply(pace, pace_seen);
+                sample_x(i, xin[i & 7], e[i >> 3][i & 7], gated, true);
             } else {
-                for (int i = 0; i < n; i++) sample_x(i, mix_tile[i * kMixPitch + lane]);
+                sample(i, e[i >> 3][i & 7], gated, true);
+            }
+        }
+        // (the atomic's value is looked at whether a step was taken or not: a register that a vector-memory result may still be on its
+        // way to makes the compiler drain every frame store in flight where it next writes that register — in emit_flush, every tile)
+        const uint32_t seen = (uint32_t)__builtin_amdgcn_readfirstlane((int)pace_seen);
+        if (pace_now) pace_apply(pace, seen);
+        plain = all_pos(gate_next);
+        emit_flush<kOut>(em, mix_tile, t0, kMixRows, V);
+    };
+    // The launch's tiles: runs of plain tiles and runs of gated ones, each run a loop of its own around ONE copy of the samples, then the
+    // short last tile.  (One loop around both copies: behind the join of the two the compiler's wait counts no longer tell the pace
+    // atomic and the next tile's gate from the 32 frame stores issued after them, and every tile waits for all of its stores.  A run
+    // ends where the envelope changes class — twice per gate period — and there the counts are settled once, by hand.)
+    auto tiles = [&](auto kX) __attribute__((always_inline)) {
+        const uint32_t t_full = a.T & ~(uint32_t)(kMixRows - 1);
+        uint32_t t0 = 0;
+        // (exact mode's stepwise oscillator, hundreds of f64 instructions per sample, keeps the one gated copy: a second copy of it costs
+        // the statistics variant its fourth wave per SIMD, 100 -> 131 VGPRs, for one instruction per sample)
+        constexpr bool kTwo = !kExact || decltype(kX)::value;
+        while (t0 < t_full) {
+            if (kTwo && plain) {
+                do {
+                    full_tile(t0, kX, false);
+                    t0 += kMixRows;
+                } while (t0 < t_full && plain);
+            } else {
+                do {
+                    full_tile(t0, kX, true);
+                    t0 += kMixRows;
+                } while (t0 < t_full && !(kTwo && plain));
+            }
+            __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+        }
+        if (t0 < a.T) {
+            const int n = (int)(a.T - t0);
+            if (!pace.word) {
+                if (t0 >= prio1_at && t0 < prio1_at + kMixRows) __builtin_amdgcn_s_setprio(1);
+                if (t0 >= prio0_at && t0 < prio0_at + kMixRows) __builtin_amdgcn_s_setprio(0);
+            }
+            if (decltype(kX)::value) {
+                xsaw_tile(xo, mix_tile + lane, kMixPitch, n);
+                for (int i = 0; i < n; i++) sample_x(i, mix_tile[i * kMixPitch + lane], env_s[t0 + (uint32_t)i], true, false);
+            } else {
+                for (int i = 0; i < n; i++) sample(i, env_s[t0 + (uint32_t)i], true, false);
             }
             emit_flush<kOut>(em, mix_tile, t0, n, V);
-            continue;
         }
-        auto sample = [&](int i) {
-            const float env = env_s[t0 + (uint32_t)i];
-            if (kExact) {
-                float sine = 0.0f, square = 0.0f, saw = 0.0f;
-                osc_step(fa, sa, ka, 0.0f, 0.0f, sine, square, saw);
-                x = kOscAPort == OSC_OUT_SINE ? sine : (kOscAPort == OSC_OUT_SQUARE ? square : saw);
-            }
-            float lp, bp, hp;
-            vcf_run<!kExact>(sv, sv_fin, x, lp, bp, hp);
-            const float y = kVcfPort == VCF_OUT_LP ? lp : (kVcfPort == VCF_OUT_BP ? bp : hp);
-            if (kFixed) {
-                fpos_lo = fa_osc.lo;
-                fpos_hi = fa_osc.hi;
-                x = fosc_saw(fa_osc);  // sample t+1
-            } else if (!kExact) {
-                pos_a = ca.pos;
-                x = cosc_step<kOscAPort>(ca);  // sample t+1
-            }
-            // vca.rs:132: (negative || cv > 0.0) ? audio * cv : 0.0 — cv is wave-uniform here, so `cv > 0.0` is decided
-            // on the scalar unit from the bit pattern: positive, non-zero, not NaN  <=>  0 < bits <= 0x7f800000
-            const bool cv_pos = (uint32_t)(__float_as_int(env) - 1) < 0x7f800000u;
-            const float o = (negative || cv_pos) ? y * env : 0.0f;
-            emit_put<kOut>(em, mix_tile, o, i, V);
-        };
-        if (n == kMixRows) {  // constant trip count: unrollable (readlane is convergent, so a runtime count is not)
-            // pacing: the step's atomic before the tile's samples, its value looked at after them — in this block alone, so that the value
-            // is neither waited for behind the frame stores in flight nor alive anywhere else in the loop
-            uint32_t pace_seen;
-            const bool pace_now = pace_step(pace, t0 / kMixRows, lane, pace_seen);
-#pragma unroll 32
-            for (int i = 0; i < kMixRows; i++) sample(i);
-            if (pace_now) pace_apply(pace, pace_seen);
-        } else {
-            for (int i = 0; i < n; i++) sample(i);
-        }
-        emit_flush<kOut>(em, mix_tile, t0, n, V);
-    }
+    };
+    if (xs)
+        tiles(std::true_type{});
+    else
+        tiles(std::false_type{});
     if (!kExact) {
         sa.pos = pos_a;
         sa.sync_last = false;

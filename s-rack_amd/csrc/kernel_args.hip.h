@@ -42,6 +42,9 @@ struct KernelArgs {
     // render_voice_chain_track: this launch's slice of the pacing table (wave.hip.h, kPaceKeys words, cleared by the host), or null: the
     // voice waves keep the open-loop priority ramp
     uint32_t* pace;
+    // render_voice_chain_track: 1 = a full tile whose 32 envelope values are all > 0 runs the copy of the samples without the VCA's
+    // gate (fused.hip.h; same bits either way); 0 = every tile runs the gated copy (SRACK_TILE_PLAIN=0: tools/ and the tests' A/B)
+    uint32_t tile_plain;
 };
 
 struct ChainRoles {  // op indices of the fused voice chain (osc_l / adsr unused in the track variant)

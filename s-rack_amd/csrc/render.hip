@@ -67,6 +67,7 @@ struct Knobs {
                                       // three alternating rounds): config 3 11.52 / 11.54 / 11.57 ms per step all at once at the end, 11.62 / 11.67 / 11.69 aside;
                                       // cfg3_poly 16.40 against 16.43 — at the power cap a kernel that runs beside the voices is paid for in clock
     int pace = 1;                     // the flagship's voice waves pace themselves against their SIMD's other waves (wave.hip.h, notes/r10.md); 0: the open-loop priority ramp
+    int tile_plain = 1;               // the flagship's all-positive envelope tiles run without the VCA's gate (fused.hip.h, notes/r15.md); 0: every tile keeps it — same bits
     int tick = 2;                     // calls keep the control program running ahead across calls (TickSession below); 1: calls of one chunk only (round 3); 0: every call starts it afresh
 };
 static const Knobs& knobs()
@@ -94,6 +95,7 @@ static const Knobs& knobs()
         v.tick = (int)num("SRACK_TICK", 0, 2, 2);
         v.mix_aside = (int)num("SRACK_MIX_ASIDE", 0, 1, 0);
         v.pace = (int)num("SRACK_PACE", 0, 1, 1);
+        v.tile_plain = (int)num("SRACK_TILE_PLAIN", 0, 1, 1);
         return v;
     }();
     return k;
@@ -1391,6 +1393,7 @@ struct Segment {
             ka.lanes = lanes;
             ka.n0 = h.samples_rendered + t_off;
             ka.stats = fold ? nullptr : d_stats;  // (in-kernel statistics: the fused voice chains)
+            ka.tile_plain = (uint32_t)knobs().tile_plain;
             if (fold_rows) {
                 ka.frames = d->d_stat_frames;
                 ka.plane_stride = (uint64_t)fold_rows * V;

@@ -240,6 +240,21 @@ SRK_DEV void emit_put(E& e, float* mix_tile, float o, int i, uint32_t V)  // i =
     if constexpr ((kOut & kOutStats) != 0) stats_add(e.st, o);
 }
 
+// Unrolled 32 times, emit_put's row offset becomes 32 loop-invariant SGPRs (i * V * 4, hoisted out of the tile loop).  A kernel that
+// needs those registers calls this after each emit_put: the offset is then one running SGPR, advanced by one s_add per sample.
+// (An output mode without frames has no offset to pin.)
+template <int kOut>
+SRK_DEV void emit_row_pin(Emit& e)
+{
+    if constexpr ((kOut & ~kOutStats) != 2) asm("" : "+s"(e.soff));
+}
+
+// Eight consecutive floats of wave-uniform data through the scalar unit: one s_load_dwordx8 into SGPRs (dword alignment is all a
+// scalar load asks for — a tick session starts its tracks at any sample)
+typedef float float8u __attribute__((ext_vector_type(8)));
+typedef float8u float8u_dw __attribute__((aligned(4)));
+SRK_DEV float8u uniform_load8(const __attribute__((address_space(4))) float* p) { return *(const __attribute__((address_space(4))) float8u_dw*)p; }
+
 SRK_DEV void emit_rebase(Emit& e)  // point the descriptor at frame_row; a tile spans at most 32 rows = 32 * V * 4 bytes
 {
     e.rsrc = __builtin_amdgcn_make_buffer_rsrc(e.frame_row, 0, 0x7fffffff, 0x00020000);

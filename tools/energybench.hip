@@ -19,6 +19,7 @@ __global__ __launch_bounds__(64) void k(float* out, int iters, float seed)
     float a = seed + threadIdx.x, b = a * 1.0001f, c = a * 0.9999f, d = 0.5f, e = 0.25f, f = 0.125f, g = 1.5f, h = 2.5f;
     double p = a, q = b, r = c, s = d;
     unsigned u = threadIdx.x, v = 12345u, w = 777u, x = 99u;
+    unsigned s0 = (unsigned)iters, s1 = 3u;  // variant 11
     float* mine = out + (size_t)blockIdx.x * 64 + threadIdx.x;
     __shared__ float lds[64 * 4];
     for (int i = 0; i < iters; i++) {
@@ -46,9 +47,20 @@ __global__ __launch_bounds__(64) void k(float* out, int iters, float seed)
         } else if (kVariant == 10) {  // the same without the ds_write (the reference for 9)
             REP16(asm volatile("v_fma_f32 %1, %1, %2, %3\n v_fma_f32 %2, %2, %3, %1\n v_fma_f32 %3, %3, %1, %2" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));)
         } else if (kVariant == 11) {  // scalar ALU
-            unsigned s0 = i, s1 = 3;
-            REP16(asm volatile("s_add_u32 %0, %0, %1\n s_xor_b32 %1, %1, %0\n s_add_u32 %0, %0, %1\n s_xor_b32 %1, %1, %0" : "+s"(s0), "+s"(s1));)
-            u += s0;
+            // (s0 / s1 are carried across the iterations and end in the result; profiles/r04_energy.txt has a build of this variant that ran
+            // 0.0028 ms per launch — no loop at all)
+            REP16(asm volatile("s_add_u32 %0, %0, %1\n s_xor_b32 %1, %1, %0\n s_add_u32 %0, %0, %1\n s_xor_b32 %1, %1, %0" : "+s"(s0), "+s"(s1) : : "scc");)
+        } else if (kVariant == 18) {  // one s_load_dword per three v_fma (the flagship's envelope, a dword per sample; denser than the kernel's: x9)
+            unsigned sv;
+            REP16(asm volatile("s_load_dword %4, %5, 0x0\n v_fma_f32 %1, %1, %2, %3\n v_fma_f32 %2, %2, %3, %1\n v_fma_f32 %3, %3, %1, %2" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "=&s"(sv) : "s"(out) : "memory");)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        } else if (kVariant == 19) {  // the same 48 v_fma with one s_load_dwordx8 per eight groups of three (the envelope by eights)
+            typedef unsigned u8v __attribute__((ext_vector_type(8)));
+            u8v sv8;
+#define FMA3 "v_fma_f32 %1, %1, %2, %3\n v_fma_f32 %2, %2, %3, %1\n v_fma_f32 %3, %3, %1, %2\n "
+            asm volatile("s_load_dwordx8 %4, %5, 0x0\n " FMA3 FMA3 FMA3 FMA3 FMA3 FMA3 FMA3 FMA3 "s_load_dwordx8 %4, %5, 0x20\n " FMA3 FMA3 FMA3 FMA3 FMA3 FMA3 FMA3 FMA3 "s_waitcnt lgkmcnt(0)"
+                         : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "=&s"(sv8) : "s"(out) : "memory");
+#undef FMA3
         } else if (kVariant == 12) {  // v_fma_f32 with the constant operands in SGPRs (one VGPR source instead of three)
             float se = 0.25f;  // (one SGPR per instruction: the constant bus)
             REP16(asm volatile("v_fma_f32 %0, %0, %4, 0.5\n v_fma_f32 %1, %1, %4, 0.5\n v_fma_f32 %2, %2, %4, 0.5\n v_fma_f32 %3, %3, %4, 0.5" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "s"(se));)
@@ -67,7 +79,7 @@ __global__ __launch_bounds__(64) void k(float* out, int iters, float seed)
             a = pa.x + pa.y; c = pb.x + pb.y;
         }
     }
-    *mine = a + b + c + d + (float)(p + q + r + s) + (float)(u + v + x) + lds[threadIdx.x];
+    *mine = a + b + c + d + (float)(p + q + r + s) + (float)(u + v + x + s0 + s1) + lds[threadIdx.x];
 }
 
 template <int V>
@@ -88,7 +100,7 @@ static void run(float* out, double seconds)
     for (int j = 0; j < n; j++) hipLaunchKernelGGL(k<V>, dim3(4096), dim3(64), 0, 0, out, iters, 1.0f);
     hipDeviceSynchronize();
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    // wave-instructions of the class per launch: 4096 waves x iters x 64 (variants 9: 16 ds_write + 48 fma; 10: 48; 13: 1 nop; 15: 32 pk)
+    // wave-instructions of the class per launch: 4096 waves x iters x 64 (variants 9: 16 ds_write + 48 fma; 10: 48; 13: 1 nop; 15: 32 pk; 18: 16 s_load_dword + 48 fma; 19: 2 s_load_dwordx8 + 48 fma)
     printf("{\"variant\": %d, \"launches\": %d, \"seconds\": %.3f, \"ms_per_launch\": %.4f, \"waves\": 4096, \"iters\": %d}\n", V, n, dt, dt / n * 1e3, iters);
 }
 
@@ -99,7 +111,7 @@ int main(int argc, char** argv)
     float* out; hipMalloc(&out, 4096 * 64 * 4);
     switch (v) {
 #define C(n) case n: run<n>(out, sec); break;
-        C(0) C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16) C(17)
+        C(0) C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16) C(17) C(18) C(19)
     }
     return 0;
 }

@@ -1,6 +1,6 @@
 // buses.hpp — the mix table of a handle's voices (srack_voices_set_buses) and what the bus fold reads of it on the device.
 //
-// bus_mix[b][c][t] = sum over the voices of bus b of fl32(gain[v] * x[plane(c)][t][v]).  The fold (fused.hip.h: bus_fold_tiles,
+// bus_mix[b][c][t] = sum over the voices of bus b of fl32(gain[v] * x[plane(c)][t][v]).  The fold (folds.hip.h: bus_fold_tiles,
 // bus_fold_sum) streams a launch's frames once, 64 voices — one 256-byte piece of a frame row — per wave: a TILE.  Everything the
 // kernels need to know about the table is prepared here, on the host, once per srack_voices_set_buses, by a pure function:
 //   order    per tile, the lanes of its voices that are in a bus, sorted by bus (ties: ascending voice): the order they are added in

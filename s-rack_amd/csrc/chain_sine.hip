@@ -1,0 +1,6 @@
+// chain_sine.hip — the render_voice_chain and render_voice_chain_track kernels whose audio oscillator emits its sine port (chain_unit.hip.h).
+#include "chain_unit.hip.h"
+
+namespace srack {
+template void launch_chain<OSC_OUT_SINE>(uint32_t, bool, int, bool, const KernelArgs&, const ChainRoles&, const CtlWork&, dim3, hipStream_t);
+}

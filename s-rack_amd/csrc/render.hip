@@ -3,8 +3,10 @@
 //
 // Execution model: one voice per lane, 64 voices per wave, one wave per workgroup (no barriers between waves: voices
 // never interact).  A wave owns its voices for the whole render because every module is a recurrence in time (phase
-// accumulator, IIR state, envelope state).  The kernels live in interp.hip.h (generic tile interpreter) and
-// fused.hip.h (whole patch shapes in registers, mix-down); the per-sample module arithmetic in modules.hip.h.
+// accumulator, IIR state, envelope state).  The voice kernels are translation units of their own, one per kernel family — the tile
+// interpreter (interp.hip), whole patch shapes in registers (chain*.hip, seq.hip, fm_pair.hip, fm_block.hip) — reached through the
+// launch functions of launch.hpp: this file is the host side and sees none of them.  It keeps the small passes over what they wrote
+// (folds.hip.h: mix-down, statistics, bus folds; busfx.hip.h: the bus reverbs); the per-sample module arithmetic is in modules.hip.h.
 //
 // HBM layout (all voice-minor so that lane == voice gives 256 B contiguous per wave access):
 //   table   u32 [n_rows][V]           state rows, then per-voice parameter rows
@@ -24,13 +26,13 @@
 #include <vector>
 
 #include "busfx.hip.h"
-#include "fused.hip.h"
-#include "interp.hip.h"
+#include "folds.hip.h"
+#include "freeverb_params.hpp"
 #include "jit.hpp"
 #include "kernel_args.hip.h"
-#include "modules.hip.h"
-#include "freeverb_params.hpp"
+#include "launch.hpp"
 #include "runtime.hpp"
+#include "wave.hip.h"
 
 namespace srack {
 
@@ -509,82 +511,7 @@ static int grow(float*& p, size_t& have, size_t need)
     return SRACK_OK;
 }
 
-// ---- kernel launches (template parameters from runtime port flags and output modes) ----------------
-// f(std::integral_constant<int, O>) with the output mode as a compile-time constant: 3 frames + mix, 1 frames, 2 mix; 0 for anything else —
-// the instantiation that decides at run time (a render that asks for neither only advances the voice state).  Every kernel family takes
-// its output mode from here; one that has no instantiation of its own for a mode says so where it calls.
-template <class Fn>
-static auto with_out_mode(int out_mode, Fn&& f)
-{
-    switch (out_mode) {
-    case 3: return f(std::integral_constant<int, 3>{});
-    case 1: return f(std::integral_constant<int, 1>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    default: return f(std::integral_constant<int, 0>{});
-    }
-}
-
-// ... and f(std::integral_constant<uint32_t, P>) for the one of three output ports a flag word names (anything else: the last)
-template <uint32_t P0, uint32_t P1, uint32_t P2, class Fn>
-static void with_port(uint32_t port, Fn&& f)
-{
-    if (port == P0)
-        f(std::integral_constant<uint32_t, P0>{});
-    else if (port == P1)
-        f(std::integral_constant<uint32_t, P1>{});
-    else
-        f(std::integral_constant<uint32_t, P2>{});
-}
-template <class Fn>
-static void with_osc_port(uint32_t port, Fn&& f)
-{
-    with_port<OSC_OUT_SAW, OSC_OUT_SQUARE, OSC_OUT_SINE>(port, f);
-}
-
-template <uint32_t A, uint32_t F, bool E, int O>
-static void launch_fused4(bool track, const KernelArgs& ka, const ChainRoles& roles, const CtlWork& co, dim3 grid, hipStream_t st)
-{
-    if (track)
-        hipLaunchKernelGGL((render_voice_chain_track<A, F, E, O>), grid, dim3(64), 0, st, ka, roles, co);
-    else
-        hipLaunchKernelGGL((render_voice_chain<A, OSC_OUT_SQUARE, F, E, O>), grid, dim3(64), 0, st, ka, roles);
-}
-
-template <uint32_t A, uint32_t F>
-static void launch_fused3(bool exact, int out_mode, bool track, const KernelArgs& ka, const ChainRoles& roles, const CtlWork& co, dim3 grid, hipStream_t st)
-{
-    if ((out_mode & kOutStats) && exact)  // per-voice statistics (wave.hip.h): one instantiation per flavour, frames and mix decided at run time
-        launch_fused4<A, F, true, kOutStats>(track, ka, roles, co, grid, st);
-    else if (out_mode & kOutStats)
-        launch_fused4<A, F, false, kOutStats>(track, ka, roles, co, grid, st);
-    else if (exact && out_mode == 3 && track)  // frames + mix, the usual request, also gets the compile-time output mode in exact mode
-        hipLaunchKernelGGL((render_voice_chain_track<A, F, true, 3>), grid, dim3(64), 0, st, ka, roles, co);
-    else if (exact)  // otherwise one instantiation, output mode decided at run time
-        launch_fused4<A, F, true, 0>(track, ka, roles, co, grid, st);
-    else
-        with_out_mode(out_mode, [&](auto O) { launch_fused4<A, F, false, O>(track, ka, roles, co, grid, st); });
-}
-
-static void launch_fused(uint32_t osc_port, uint32_t vcf_port, bool exact, int out_mode, bool track, const KernelArgs& ka, const ChainRoles& roles,
-                         const CtlWork& co, dim3 grid, hipStream_t st)
-{
-    with_osc_port(osc_port, [&](auto A) {
-        with_port<VCF_OUT_LP, VCF_OUT_BP, VCF_OUT_HP>(vcf_port, [&](auto F) { launch_fused3<decltype(A)::value, F>(exact, out_mode, track, ka, roles, co, grid, st); });
-    });
-}
-
-static void launch_seq(uint32_t osc_port, int out_mode, const KernelArgs& ka, const SeqRoles& r, dim3 grid, hipStream_t st)
-{
-    with_osc_port(osc_port, [&](auto A) {
-        // (no instantiation for the mix alone: that request takes the one that decides at run time)
-        with_out_mode(out_mode == 2 ? 0 : out_mode, [&](auto O) {
-            if constexpr (O != 2) hipLaunchKernelGGL((render_voice_chain_seq<decltype(A)::value, O>), grid, dim3(64), 0, st, ka, r);
-        });
-    });
-}
-
-// The hand-written kernel a program takes (pick_kernel below).
-enum class Kernel { Interp, VoiceChain, VoiceChainTrack, SeqChain, FmPair, FmPairRing, FmPairSplit, FmPairBlock, FmPairBlockX, FmPairX };
+// The hand-written kernel a program takes (pick_kernel below; each family's launch functions: launch.hpp), by the name srack_render_info gives it.
 static const char* const kKernelName[] = {"render_interp", "render_voice_chain", "render_voice_chain_track", "render_voice_chain_seq", "render_fm_pair", "render_fm_pair_ring",
                                           "render_fm_pair" /* (on two waves) */, "render_fm_pair_block", "render_fm_pair_block_x", "render_fm_pair_x"};
 
@@ -605,69 +532,6 @@ static ChainRoles fm_pair_roles(const FlatProgram& P)
     roles.out = 6;
     roles.track = P.ops[0].aux;  // the ring's state row
     return roles;
-}
-
-static void launch_fm_pair(Kernel kernel, bool exact, int out_mode, const KernelArgs& ka, const ChainRoles& roles, dim3 grid, hipStream_t st)
-{
-    if (kernel == Kernel::FmPairSplit) {
-        hipLaunchKernelGGL((render_fm_pair_split<true, 0>), grid, dim3(128), 0, st, ka, roles);
-        return;
-    }
-    auto launch = [&](auto E, auto O) {
-        if (kernel == Kernel::FmPairRing)
-            hipLaunchKernelGGL((render_fm_pair_ring<E, O>), grid, dim3(64), 0, st, ka, roles);
-        else
-            hipLaunchKernelGGL((render_fm_pair<E, O>), grid, dim3(64), 0, st, ka, roles);
-    };
-    if (exact)  // one instantiation, output mode decided at run time
-        launch(std::true_type{}, std::integral_constant<int, 0>{});
-    else
-        with_out_mode(out_mode, [&](auto O) { launch(std::false_type{}, O); });
-}
-
-static void launch_fm_pair_x(int out_mode, const KernelArgs& ka, const ChainRoles& roles, dim3 grid, hipStream_t st)
-{
-    with_out_mode(out_mode, [&](auto O) { hipLaunchKernelGGL((render_fm_pair_x<O>), grid, dim3(128), 0, st, ka, roles); });
-}
-
-// The FM pair with a delay of 256 ... 1024 samples in default mode: time-parallel, 32 voices per 512-thread workgroup, ring in LDS.
-template <class K>
-static int launch_blk(K kernel, size_t lds, const KernelArgs& ka, const ChainRoles& roles, hipStream_t st)
-{
-    // more than 64 KB of dynamic LDS has to be asked for — per device (the attribute belongs to the current device's copy of the
-    // function) and from any thread: asked for before every launch, which costs nothing next to one
-    HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(kernel, dim3(ka.n_waves), dim3(kBlkVoices * kBlkSlices), lds, st, ka, roles);
-    return SRACK_OK;
-}
-
-static int launch_fm_block(bool x, int out_mode, const KernelArgs& ka, const ChainRoles& roles, hipStream_t st)
-{
-    const size_t B = (size_t)ka.prog.buffer_size;
-    return with_out_mode(out_mode, [&](auto O) {
-        if (x) return launch_blk(render_fm_pair_block_x<O>, fm_block_x_lds_bytes((uint32_t)B), ka, roles, st);
-        return launch_blk(render_fm_pair_block<O>, sizeof(float) * B * kBlkVoices + sizeof(double) * 2 * kBlkSlices * kBlkVoices + 16, ka, roles, st);
-    });
-}
-
-static size_t interp_lds_bytes(const DevProgram& H)
-{
-    return ((size_t)H.n_rows + 2 + (size_t)H.n_tracks + (size_t)H.n_slots * H.tile) * 256;  // + zero, trash and track rows
-}
-
-static void launch_interp(const FlatProgram& P, const KernelArgs& ka, hipStream_t st)
-{
-    const size_t lds = interp_lds_bytes(P.hdr);
-    if (knobs().debug_occ) {  // tools/: what the runtime says about resident workgroups per CU for this LDS size
-        int n = -1;
-        hipError_t e = (P.render_flags & SRACK_RENDER_EXACT_OSC) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, render_interp<true>, 64, lds)
-                                                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, render_interp<false>, 64, lds);
-        fprintf(stderr, "[srack] render_interp lds=%zu B/wave occupancy=%d workgroups/CU (%s) waves=%u\n", lds, n, hipGetErrorString(e), ka.n_waves);
-    }
-    if (P.render_flags & SRACK_RENDER_EXACT_OSC)
-        hipLaunchKernelGGL(render_interp<true>, dim3(ka.n_waves), dim3(64), lds, st, ka);
-    else
-        hipLaunchKernelGGL(render_interp<false>, dim3(ka.n_waves), dim3(64), lds, st, ka);
 }
 
 // Voices per wave.  A full wave (64) is right whenever there are enough voices to give every SIMD work.
@@ -800,18 +664,19 @@ static void launch_ctl(const FlatProgram& Cp, const KernelArgs& kc, hipStream_t 
     if (Cp.fused == FUSED_CTL_GATE_ENV) {
         CtlWork w{kc.ops, kc.table, kc.frames + (size_t)Cp.ops[2].aux * kc.plane_stride, kc.T,
                   Cp.ops[0].flags & (OSC_OUT_SINE | OSC_OUT_SQUARE | OSC_OUT_SAW | OSC_EXACT), nullptr, 0u};
-        hipLaunchKernelGGL(render_ctl_gate_env, dim3(1), dim3(64), 0, st, w);
+        launch_ctl_gate_env(w, st);
     } else if (Cp.fused == FUSED_FM_PAIR) {
         const bool exact = (Cp.render_flags & SRACK_RENDER_EXACT_OSC) != 0;
         launch_fm_pair(fm_pair_kernel(Cp.fused_variant, exact), exact, 1, kc, fm_pair_roles(Cp), dim3(1), st);
     } else {
-        launch_interp(Cp, kc, st);
+        launch_interp(Cp, kc, st, knobs().debug_occ);
     }
 }
 
 #ifdef SRK_WAVE_CENSUS
 // Tools-only build (make EXTRA=-DSRK_WAVE_CENSUS ...; tools/wave_census.py): while armed, every launch of render_voice_chain_track records
 // its waves (fused.hip.h) into the next n_waves + 1 slots of one device buffer (slot n_waves: the control block).  Not in the library's ABI.
+// Every port's unit has a record pointer of its own, which the launch sets from census_rec (launch.hpp): null unless census_arm armed it.
 static struct {
     uint32_t* d_rec = nullptr;
     uint32_t cap = 0, used = 0;
@@ -819,7 +684,10 @@ static struct {
     std::vector<uint32_t*> where;     // the pointer each launch was given (host copies stay alive until the next srack_census_begin)
 } g_census;
 
-static int census_arm(uint32_t n_slots, hipStream_t st)
+static uint32_t* const kCensusNone = nullptr;
+uint32_t* const* census_rec = &kCensusNone;
+
+static int census_arm(uint32_t n_slots)
 {
     uint32_t* p = nullptr;
     if (g_census.d_rec && g_census.used + n_slots <= g_census.cap && g_census.where.size() < g_census.where.capacity()) {
@@ -827,9 +695,10 @@ static int census_arm(uint32_t n_slots, hipStream_t st)
         g_census.used += n_slots;
         g_census.slots.push_back(n_slots);
     }
-    if (g_census.where.size() == g_census.where.capacity()) return SRACK_OK;  // not armed (or out of launch slots): the symbol stays null
+    census_rec = &kCensusNone;
+    if (g_census.where.size() == g_census.where.capacity()) return SRACK_OK;  // not armed (or out of launch slots): the launch records nothing
     g_census.where.push_back(p);
-    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(srk_census_rec), &g_census.where.back(), sizeof(p), 0, hipMemcpyHostToDevice, st));
+    census_rec = &g_census.where.back();
     return SRACK_OK;
 }
 
@@ -838,6 +707,7 @@ extern "C" int srack_census_begin(uint32_t max_slots, uint32_t max_launches)
     HIP_TRY(hipDeviceSynchronize());
     (void)hipFree(g_census.d_rec);
     g_census = {};
+    census_rec = &kCensusNone;
     HIP_TRY(hipMalloc(&g_census.d_rec, sizeof(uint32_t) * 8 * (size_t)max_slots));
     HIP_TRY(hipMemset(g_census.d_rec, 0, sizeof(uint32_t) * 8 * (size_t)max_slots));
     g_census.cap = max_slots;
@@ -850,8 +720,6 @@ extern "C" int srack_census_begin(uint32_t max_slots, uint32_t max_launches)
 extern "C" int srack_census_read(uint32_t* out, uint32_t max_slots, uint32_t* slots_per_launch, uint32_t max_launches)
 {
     HIP_TRY(hipDeviceSynchronize());
-    uint32_t* null_rec = nullptr;
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(srk_census_rec), &null_rec, sizeof(null_rec), 0, hipMemcpyHostToDevice));
     const uint32_t n = std::min<uint32_t>((uint32_t)g_census.slots.size(), max_launches);
     uint32_t words = 0;
     for (uint32_t i = 0; i < n; i++) {
@@ -1224,7 +1092,7 @@ struct Segment {
             tk.n0 = h.samples_rendered;
             tk.st = st;
             if (co_ctl) {
-                hipLaunchKernelGGL(render_ctl_gate_env, dim3(1), dim3(64), 0, st, tick_work(0));
+                launch_ctl_gate_env(tick_work(0), st);
                 HIP_TRY(hipGetLastError());
             } else {
                 if ((rc = tick_upload_slots(0)) != SRACK_OK) return rc;
@@ -1252,7 +1120,7 @@ struct Segment {
                 if ((rc = jit_launch(*special, kp, n_stages, st)) != SRACK_OK) return rc;
             }
         } else if (co_ctl) {  // chunk 0's track: the only control work that is not hidden (1024 samples, ~0.15 ms)
-            hipLaunchKernelGGL(render_ctl_gate_env, dim3(1), dim3(64), 0, st, ctl_work(chunks[0].first, chunks[0].second));
+            launch_ctl_gate_env(ctl_work(chunks[0].first, chunks[0].second), st);
             HIP_TRY(hipGetLastError());
         } else if (has_ctl) {
             if (!d->ctl_stream) {
@@ -1282,10 +1150,7 @@ struct Segment {
                 if ((rc = upload_stage_slots(d->ctl_stream)) != SRACK_OK) return rc;
                 for (uint32_t j = 0; j < n_launch; j++) {
                     const KernelArgs* slots = d->d_stage_slots + (size_t)j * n_stages;
-                    if (flags & SRACK_RENDER_EXACT_OSC)
-                        hipLaunchKernelGGL(render_interp_stages<true>, dim3(n_stages), dim3(64), lds, d->ctl_stream, slots);
-                    else
-                        hipLaunchKernelGGL(render_interp_stages<false>, dim3(n_stages), dim3(64), lds, d->ctl_stream, slots);
+                    launch_interp_stages((flags & SRACK_RENDER_EXACT_OSC) != 0, n_stages, lds, slots, d->ctl_stream);
                     HIP_TRY(hipGetLastError());
                     if (j >= max_lag) HIP_TRY(hipEventRecord(d->ev_chunk[j - max_lag], d->ctl_stream));
                 }
@@ -1427,7 +1292,7 @@ struct Segment {
                 switch (pick.kernel) {
                 case Kernel::VoiceChainTrack:
 #ifdef SRK_WAVE_CENSUS
-                    if ((rc = census_arm(n_waves + 1, st)) != SRACK_OK) return rc;
+                    if ((rc = census_arm(n_waves + 1)) != SRACK_OK) return rc;
 #endif
                     [[fallthrough]];
                 case Kernel::VoiceChain:
@@ -1437,12 +1302,12 @@ struct Segment {
                 case Kernel::FmPairX: launch_fm_pair_x(out_mode, ka, roles, dim3(n_waves), st); break;
                 case Kernel::FmPairBlock:
                 case Kernel::FmPairBlockX:
-                    if ((rc = launch_fm_block(pick.kernel == Kernel::FmPairBlockX, out_mode, ka, roles, st)) != SRACK_OK) return rc;
+                    HIP_TRY(launch_fm_block(pick.kernel == Kernel::FmPairBlockX, out_mode, ka, roles, st));
                     break;
                 case Kernel::FmPair:
                 case Kernel::FmPairRing:
                 case Kernel::FmPairSplit: launch_fm_pair(pick.kernel, exact, out_mode, ka, roles, dim3(n_waves), st); break;
-                case Kernel::Interp: launch_interp(P, ka, st); break;
+                case Kernel::Interp: launch_interp(P, ka, st, knobs().debug_occ); break;
                 }
             }
             HIP_TRY(hipGetLastError());

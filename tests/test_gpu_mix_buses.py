@@ -1,5 +1,5 @@
 """Mix buses (srack_voices_set_buses, srack_render_buses): bus_mix[b][c][t] = f32 sum over the voices of bus b of the f32 product
-gain[v] * x[plane(c)][t][v], by a two-pass fold over each launch's frames (fused.hip.h: bus_fold_tiles, bus_fold_sum).
+gain[v] * x[plane(c)][t][v], by a two-pass fold over each launch's frames (folds.hip.h: bus_fold_tiles, bus_fold_sum).
 
 References are NumPy f64 sums over FRAMES — the frames the same call returned, and once the oracle's.  The bound is the standard one
 for an f32 sum of n rounded products in any order, |got - ref| <= 1.02 n 2^-24 sum |gain x| + n 2^-149 (gamma_{n-1} (1 + u) + u with

@@ -1,5 +1,5 @@
 """Per-voice output statistics (srack_render_stats): in registers of the fused voice chains (wave.hip.h, EmitStats), folded from each
-launch's frames for every other kernel (fused.hip.h, stats_fold).
+launch's frames for every other kernel (folds.hip.h, stats_fold).
 
 The statistics must be what a sequential f64 loop over the frames gives, bit for bit, however the render is cut (launches, segments,
 calls, tick sessions) and whichever kernel renders, and asking for them must change no bit of frames, mix or voice state."""

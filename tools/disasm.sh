@@ -1,12 +1,14 @@
 #!/bin/bash
-# tools/disasm.sh [out.s] — the gfx950 code object inside s-rack_amd/libsrack_hip.so, disassembled (ISA counts quoted in DESIGN.md).
+# tools/disasm.sh [out.s] — the gfx950 code objects inside s-rack_amd/libsrack_hip.so (one per translation unit with device code),
+# disassembled one after the other (ISA counts quoted in DESIGN.md).  LIB=<path>: another library.
 # tools/disasm.sh out.s '<mangled-name regex>' additionally prints an instruction histogram per loop of that kernel.
 set -eu
 OUT=${1:-/tmp/srack_lib.s}
+LIB=${LIB:-s-rack_amd/libsrack_hip.so}
 T=$(mktemp -d)
-objcopy -O binary --only-section=.hip_fatbin s-rack_amd/libsrack_hip.so "$T/fat.bin"
-/opt/rocm/lib/llvm/bin/clang-offload-bundler --unbundle --type=o --input="$T/fat.bin" --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output="$T/lib.co"
-/opt/rocm/lib/llvm/bin/llvm-objdump -d "$T/lib.co" > "$OUT"
+cp "$LIB" "$T/lib.so"
+(cd "$T" && /opt/rocm/lib/llvm/bin/llvm-objdump --offloading lib.so > /dev/null)
+for co in "$T"/lib.so.*gfx950; do /opt/rocm/lib/llvm/bin/llvm-objdump -d "$co"; done > "$OUT"
 rm -rf "$T"
 [ $# -ge 2 ] || exit 0
 python3 - "$OUT" "$2" <<'PY'

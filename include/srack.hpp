@@ -197,6 +197,16 @@ public:
     {
         check(srack_buses_reverb(p_, n_samples, d_bus_mix, d_bus_fx, stream));
     }
+    // The master section: a gain per bus and channel (f32 [n_buses][2]; nullptr: 1.0f everywhere), the buses summed to one stereo pair in an
+    // order that depends on n_buses alone.  Not part of the program: restarts nothing, and the gains survive an edit of the patch.
+    void set_master(const float* gain = nullptr) { check(srack_buses_set_master(p_, gain)); }
+    uint32_t get_master(float* gain = nullptr, uint32_t cap = 0) const { return (uint32_t)check(srack_buses_get_master(p_, gain, cap)); }
+    // d_rows f32 [n_buses][row_channels][n_samples] -> d_master f32 [2][n_samples] (no overlap); d_master_stats f64 [2][SRACK_STAT_COUNT],
+    // added to, or null.  Asynchronous on `stream`.  A sharded host reduces the bus mixes first and takes the master on the root.
+    void master(uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_master, double* d_master_stats = nullptr, void* stream = nullptr)
+    {
+        check(srack_buses_master(p_, n_samples, d_rows, row_channels, d_master, d_master_stats, stream));
+    }
     // execute_batch plus d_bus_mix, f32 [n_buses][channels][n_samples] (written); d_frames, d_mix, d_stats may each be null
     void execute_batch_buses(uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags = 0, void* stream = nullptr)
     {

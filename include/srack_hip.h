@@ -497,6 +497,55 @@ int srack_buses_reset_reverb(srack_patch* p);
 int srack_buses_reverb_plan(const srack_patch* p, int* line_lengths, int* block);
 int srack_buses_reverb(srack_patch* p, uint32_t n_samples, const float* d_bus_mix, float* d_bus_fx, void* stream);
 
+/* ---- master section: a gain per bus and channel, one stereo sum over the buses, its statistics -------------------
+ * MonoMixerModule behind the effects (mixer.rs:106-119: output.fill(0.0); *dst += src * gain, one gain per input), generalised to
+ * N buses: a host with thousands of buses wants one stereo pair, not f32 [n_buses][2][T] to read back and add up itself.
+ *   master[c][t] = sum over the buses b of  fl32(gain[b][c] * rows[b][c][t]),   c = 0, 1
+ * Product and sum are IEEE f32, one rounding per operation, no fma.  ANY f32 gain is accepted, the reference's way: 0 * inf is NaN; a
+ * non-finite sample or gain makes that channel's sample non-finite and touches nothing else.
+ *
+ * The order of the additions is part of the ABI.  It depends on n_buses alone — never on n_samples, on how a render is cut into
+ * calls, or on what else the call is asked for:
+ *   run r    = ((+0.0f + p[64r]) + p[64r+1]) + ...   over its up to SRACK_MASTER_RUN buses, ascending   (p[b] the product of bus b)
+ *   block k  = +0.0f plus its up to SRACK_MASTER_BLOCK run sums, ascending
+ *   master   = +0.0f plus the up to 16 block sums, ascending
+ * Up to 64 buses that is MonoMixerModule's loop exactly; up to 65 it coincides with the plain sequential sum, from 66 on it does not.
+ *
+ * set_master: gain is host memory, f32 [n_buses][2] (channel 0, channel 1 of every bus), copied bit for bit; NULL = 1.0f everywhere.
+ * get_master copies up to cap buses (gain may be NULL) and returns n_buses, or 0 when no gains are set.  Before set_master the master
+ * runs with every gain 1.0f.
+ * The gains belong to the handle, NOT to the patch's program: setting or changing them, or running the master, does not re-flatten,
+ * restarts nothing, changes no bit of frames, mix, statistics, bus mixes, fx or voice state and not the kernel a patch renders with;
+ * they survive an edit that re-flattens the patch.  srack_voices_configure drops them; so does srack_voices_set_buses with another
+ * n_buses (the same n_buses keeps them).  Rack files carry nothing of this.
+ *
+ * The master call:
+ *   d_rows         : device, f32 [n_buses][row_channels][n_samples] — what srack_buses_reverb writes (row_channels = 2) or what
+ *                    srack_render_buses writes (row_channels = the patch's channels).  1 <= row_channels <= 8; channels 0 and 1 are
+ *                    used, channels beyond the second are ignored (the reverb's convention).  Any 4-byte aligned address; rows that
+ *                    are 16-byte aligned (the base is, and n_samples % 4 == 0) are read four samples at a time.
+ *   d_master       : device, f32 [2][n_samples], written; must not overlap d_rows (SRACK_ERR_INVALID).  With row_channels == 1,
+ *                    d_master[1] is +0.0f throughout and no product is taken for it.
+ *   d_master_stats : device, f64 [2][SRACK_STAT_COUNT], 8-byte aligned, or NULL.  The per-voice definitions of the statistics above,
+ *                    applied to the f32 master sample the call writes: NaN / +-inf adds 1 to NONFINITE and nothing else; otherwise
+ *                    SUM, SUM_SQ, PEAK_POS, PEAK_NEG and CLIPPED (|x| > 1) are updated as there.  The call adds to what the buffer
+ *                    holds; SUM and SUM_SQ are taken in sample order: bit for bit the sequential f64 loop, however the samples are
+ *                    cut into calls.  With row_channels == 1 channel 1's row is left untouched.
+ *   stream         : as for srack_render: asynchronous, and the library touches the stream only during the call.
+ * Errors, in this order: SRACK_ERR_INVALID for a null handle; SRACK_ERR_STATE before srack_voices_configure or before a mix table
+ * exists (all three calls); n_samples == 0 is SRACK_OK and touches nothing; SRACK_ERR_INVALID for a null d_rows or d_master,
+ * row_channels outside 1..8, a misaligned d_master_stats or an overlap.  A failed set_master leaves the earlier gains in place.
+ * The run sums pass through scratch of the handle's, f32 [runs][2][n_samples] (1/64 of the input), grown on demand: SRACK_ERR_NOMEM
+ * if that fails, the earlier state intact.  No floating-point atomics (csrc/master.hip.h).  A sharded host reduces the per-rank bus
+ * mixes first, reverberates on the root and takes the master there: a sum of per-rank masters has another association and other bits.
+ * srack_render_info says " master=<n_buses>[<runs> runs]" once a master call has run. */
+#define SRACK_MASTER_RUN   64   /* buses per run   (level 1) */
+#define SRACK_MASTER_BLOCK 64   /* runs per block  (level 2): 4096 buses; at most 16 blocks (level 3) */
+int srack_buses_set_master(srack_patch* p, const float* gain);
+int srack_buses_get_master(const srack_patch* p, float* gain, uint32_t cap);
+int srack_buses_master(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels,
+                       float* d_master, double* d_master_stats, void* stream);
+
 /* Optional: do everything a later srack_render(p, <= n_samples, ..., flags) would do on first use — flatten the graph,
  * upload the programs and the voice table, size the scratch buffers (mix partials when want_mix, control tracks) — so
  * that the first render costs what every render costs.  Renders nothing and leaves the voice state untouched. */

@@ -73,6 +73,9 @@ mod ffi {
         pub fn srack_buses_reset_reverb(p: *mut SrackPatch) -> c_int;
         pub fn srack_buses_reverb_plan(p: *const SrackPatch, line_lengths: *mut c_int, block: *mut c_int) -> c_int;
         pub fn srack_buses_reverb(p: *mut SrackPatch, n_samples: u32, d_bus_mix: *const f32, d_bus_fx: *mut f32, stream: *mut c_void) -> c_int;
+        pub fn srack_buses_set_master(p: *mut SrackPatch, gain: *const f32) -> c_int;
+        pub fn srack_buses_get_master(p: *const SrackPatch, gain: *mut f32, cap: u32) -> c_int;
+        pub fn srack_buses_master(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_master: *mut f32, d_master_stats: *mut f64, stream: *mut c_void) -> c_int;
         pub fn srack_device_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
         pub fn srack_device_free(d_ptr: *mut c_void) -> c_int;
         pub fn srack_device_to_host(h_dst: *mut c_void, d_src: *const c_void, bytes: usize, stream: *mut c_void) -> c_int;
@@ -411,6 +414,29 @@ impl Patch {
     /// reverberates on the root: the reverb of a sum is not, bit for bit, the sum of reverbs.
     pub fn bus_reverb(&mut self, n_samples: u32, bus_mix: &DeviceBuffer, bus_fx: &DeviceBuffer) -> Result<(), Error> {
         check(unsafe { ffi::srack_buses_reverb(self.raw, n_samples, bus_mix.as_f32() as *const f32, bus_fx.as_f32(), std::ptr::null_mut()) }).map(|_| ())
+    }
+    /// The master section's gains (`srack_buses_set_master`): `[n_buses][2]` f32, a gain per bus and channel, any f32; None: 1.0 everywhere.
+    /// Not part of the program: restarts nothing, and the gains survive an edit of the patch.
+    pub fn set_master(&mut self, gain: Option<&[f32]>) -> Result<(), Error> {
+        check(unsafe { ffi::srack_buses_set_master(self.raw, gain.map_or(std::ptr::null(), |x| x.as_ptr())) }).map(|_| ())
+    }
+    /// The gains set, `[n_buses][2]`; None when none are (the master then runs with 1.0 everywhere).
+    pub fn get_master(&self) -> Result<Option<Vec<f32>>, Error> {
+        let n = check(unsafe { ffi::srack_buses_get_master(self.raw, std::ptr::null_mut(), 0) })? as usize;
+        if n == 0 {
+            return Ok(None);
+        }
+        let mut g = vec![0f32; n * 2];
+        check(unsafe { ffi::srack_buses_get_master(self.raw, g.as_mut_ptr(), n as u32) })?;
+        Ok(Some(g))
+    }
+    /// The buses summed to one stereo pair (`srack_buses_master`): `rows` `[n_buses][row_channels][n_samples]` f32 in — what `bus_reverb`
+    /// (2 row channels) or `execute_batch_buses` (the patch's channels) wrote —, `master` `[2][n_samples]` f32 out, `stats`
+    /// `[2][STAT_COUNT]` f64 added to.  The order of the additions depends on `n_buses` alone: runs of 64 buses, blocks of 64 runs.  A sharded
+    /// host reduces the per-rank bus mixes first, reverberates on the root and takes the master there.
+    pub fn master(&mut self, n_samples: u32, rows: &DeviceBuffer, row_channels: u32, master: &DeviceBuffer, stats: Option<&DeviceBuffer>) -> Result<(), Error> {
+        let s = stats.map_or(std::ptr::null_mut(), |b| b.as_f64());
+        check(unsafe { ffi::srack_buses_master(self.raw, n_samples, rows.as_f32() as *const f32, row_channels, master.as_f32(), s, std::ptr::null_mut()) }).map(|_| ())
     }
 }
 

@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libsrack_hip.so")
 
 OK, ERR_INVALID, ERR_PORT, ERR_NO_OUTPUT, ERR_SELF_LOOP, ERR_STATE, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8
 MAX_BUSES, BUS_NONE = 65536, -1
+MASTER_RUN, MASTER_BLOCK = 64, 64  # buses per run, runs per block: the order srack_buses_master adds in
 FREEVERB_DEFAULTS = (0.5, 0.0, 1.0, 0.5, 0.5, 0.0)  # FreeverbModule's six parameters in field order: what set_bus_reverbs(None) gives every bus
 WAVE_OWN = -1
 SEQ_OWN, MAX_SEQUENCES = -1, 65536
@@ -34,6 +35,7 @@ ABI_SYMBOLS = [
     "srack_voices_configure", "srack_voices_set_field_f32", "srack_voices_set_field_f64", "srack_render_planes", "srack_render", "srack_render_stats", "srack_render_reserve",
     "srack_voices_set_buses", "srack_voices_get_buses", "srack_voices_bus_plan", "srack_render_buses",
     "srack_buses_set_reverb", "srack_buses_get_reverb", "srack_buses_reset_reverb", "srack_buses_reverb_plan", "srack_buses_reverb",
+    "srack_buses_set_master", "srack_buses_get_master", "srack_buses_master",
     "srack_patch_set_wave_bank", "srack_patch_get_wave_bank", "srack_patch_get_wave_bank_samples", "srack_voices_set_waves", "srack_voices_get_waves",
     "srack_patch_set_sequence_bank", "srack_patch_get_sequence_bank", "srack_voices_set_sequences", "srack_voices_get_sequences",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
@@ -111,6 +113,10 @@ def _load():
         L.srack_buses_reset_reverb.argtypes = [vp]
         L.srack_buses_reverb_plan.argtypes = [vp, ip, ip]
         L.srack_buses_reverb.argtypes = [vp, u32, vp, vp, vp]
+    if hasattr(L, "srack_buses_master"):
+        L.srack_buses_set_master.argtypes = [vp, fp]
+        L.srack_buses_get_master.argtypes = [vp, fp, u32]
+        L.srack_buses_master.argtypes = [vp, u32, vp, u32, vp, vp, vp]
     if hasattr(L, "srack_voices_set_waves"):  # (tools/ alternate older builds of the library under this binding)
         L.srack_patch_set_wave_bank.argtypes = [vp, i32, fp, ip, fp, u32]
         L.srack_patch_get_wave_bank.argtypes = [vp, i32, ip, fp, u32]
@@ -548,6 +554,60 @@ class Patch:
             return fx
         finally:
             for d in (d_in, d_out):
+                if d.value:
+                    lib.srack_device_free(d)
+
+    # ---- master section: a gain per bus and channel, the buses summed to one stereo pair ---------------
+    def set_master(self, gain=None):
+        """srack_buses_set_master: gain f32 [n_buses][2], any f32 (None: 1.0 everywhere).  Not part of the program: restarts nothing."""
+        g = None
+        if gain is not None:
+            n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+            g = np.ascontiguousarray(gain, dtype=np.float32)
+            assert g.shape == (n_buses, 2), g.shape
+        _check(lib.srack_buses_set_master(self.h, None if g is None else g.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def get_master(self):
+        """-> gain f32 [n_buses][2], or None when no gains are set"""
+        n = _check(lib.srack_buses_get_master(self.h, None, 0))
+        if n == 0:
+            return None
+        g = np.empty((n, 2), dtype=np.float32)
+        _check(lib.srack_buses_get_master(self.h, g.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return g
+
+    def master_raw(self, n_samples, d_rows, row_channels, d_master, d_master_stats=None, stream=None):
+        """Device pointers in; asynchronous on `stream` (srack_buses_master): d_rows f32 [n_buses][row_channels][n], d_master f32 [2][n],
+        d_master_stats f64 [2][STAT_COUNT] (added to) or None."""
+        _check(lib.srack_buses_master(self.h, n_samples, d_rows, row_channels, d_master, d_master_stats, stream))
+
+    def master(self, rows, stats=None):
+        """Convenience for tests: rows f32 [n_buses][row_channels][T] from the host through the master -> (master f32 [2][T], stats).
+        stats: f64 [2][STAT_COUNT] to continue from (a copy comes back), or None for no statistics."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
+        T = x.shape[2]
+        out = np.empty((2, T), dtype=np.float32)
+        st = None if stats is None else np.array(stats, dtype=np.float64).reshape(2, STAT_COUNT)
+        d_in, d_out, d_st = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        try:
+            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
+            _check(lib.srack_device_alloc(C.byref(d_out), max(4, out.nbytes)))
+            if x.nbytes:
+                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
+            if st is not None:
+                _check(lib.srack_device_alloc(C.byref(d_st), st.nbytes))
+                _check(lib.srack_device_from_host(d_st, st.ctypes.data_as(C.c_void_p), st.nbytes, None))
+            self.master_raw(T, d_in, x.shape[1], d_out, d_st if st is not None else None, None)
+            if out.nbytes:
+                _check(lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), d_out, out.nbytes, None))
+            if st is not None:
+                _check(lib.srack_device_to_host(st.ctypes.data_as(C.c_void_p), d_st, st.nbytes, None))
+            _check(lib.srack_device_sync(None))
+            return out, st
+        finally:
+            for d in (d_in, d_out, d_st):
                 if d.value:
                     lib.srack_device_free(d)
 

@@ -687,6 +687,7 @@ int srack_voices_configure(srack_patch* p, uint32_t n_voices)
         p->h.bus_plan = BusPlan();
         p->h.bus_revision++;
         device_busfx_drop(p->h);  // the reverbs sat behind that table
+        device_master_drop(p->h);  // ... and so did the master's gains
         return SRACK_OK;
     });
 }
@@ -758,7 +759,10 @@ int srack_voices_set_buses(srack_patch* p, uint32_t n_buses, const int* bus, con
         if (bus) std::copy(bus, bus + h.n_voices, b.begin());
         if (gain) std::copy(gain, gain + h.n_voices, g.begin());
         BusPlan plan = bus_plan_make(h.n_voices, n_buses, b.data());
-        if (n_buses != h.n_buses) device_busfx_drop(h);  // other buses: their reverbs go, parameters and state (the same count keeps both)
+        if (n_buses != h.n_buses) {  // other buses: their reverbs go, parameters and state, and the master's gains (the same count keeps all)
+            device_busfx_drop(h);
+            device_master_drop(h);
+        }
         h.n_buses = n_buses;
         h.bus = std::move(b);
         h.bus_gain = std::move(g);
@@ -957,6 +961,65 @@ int srack_buses_reverb(srack_patch* p, uint32_t n_samples, const float* d_bus_mi
     });
 }
 
+// ---- the master section ------------------------------------------------------------------------------------------
+int srack_buses_set_master(srack_patch* p, const float* gain)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_set_master");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        // (built aside: an allocation failure leaves the earlier gains in place)
+        std::vector<float> g((size_t)h.n_buses * 2, 1.0f);
+        if (gain) std::memcpy(g.data(), gain, sizeof(float) * g.size());  // (bit for bit: NaN payloads, signed zeros)
+        h.master.gain = std::move(g);
+        h.master.set = true;
+        device_master_gains_changed(h);
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_get_master(const srack_patch* p, float* gain, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_get_master");
+        if (rc != SRACK_OK) return rc;
+        const PatchHandle& h = p->h;
+        if (!h.master.set) return 0;
+        const size_t n = std::min<size_t>(cap, h.n_buses);
+        if (gain && n) std::memcpy(gain, h.master.gain.data(), sizeof(float) * 2 * n);
+        return (int)h.n_buses;
+    });
+}
+
+int srack_buses_master(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_master, double* d_master_stats, void* stream)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_master");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        if (n_samples == 0) return SRACK_OK;
+        if (!d_rows || !d_master) {
+            set_error("buses_master: d_rows and d_master must be given");
+            return SRACK_ERR_INVALID;
+        }
+        if (row_channels < 1 || row_channels > 8) {
+            set_error("buses_master: row_channels must be 1 .. 8");
+            return SRACK_ERR_INVALID;
+        }
+        if (((uintptr_t)d_master_stats & 7u) != 0) {
+            set_error("buses_master: d_master_stats must be 8-byte aligned");
+            return SRACK_ERR_INVALID;
+        }
+        const uintptr_t in0 = (uintptr_t)d_rows, out0 = (uintptr_t)d_master;
+        const uint64_t in_bytes = 4ull * h.n_buses * row_channels * n_samples, out_bytes = 4ull * 2 * n_samples;
+        if (in0 < out0 + out_bytes && out0 < in0 + in_bytes) {
+            set_error("buses_master: d_master overlaps d_rows");
+            return SRACK_ERR_INVALID;
+        }
+        return device_buses_master(h, n_samples, d_rows, row_channels, d_master, d_master_stats, stream);
+    });
+}
+
 int srack_render_reserve(srack_patch* p, uint32_t n_samples, int want_mix, uint32_t flags)
 {
     return guarded([&]() -> int {
@@ -998,6 +1061,7 @@ int srack_render_info(srack_patch* p, char* buf, size_t cap)
         // (the kernel's name stays LAST: hosts and tests read it with split("kernel="))
         s += device_bus_note(p->h);
         s += device_busfx_note(p->h);
+        s += device_master_note(p->h);
         s += device_waves_note(p->h);
         s += device_sequences_note(p->h);
         s += device_jit_note(p->h);

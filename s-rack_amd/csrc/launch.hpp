@@ -83,4 +83,7 @@ void launch_interp(const FlatProgram& P, const KernelArgs& ka, hipStream_t st, b
 // the control pipeline: one block per control unit, `slots` its argument blocks of this launch
 void launch_interp_stages(bool exact, uint32_t n_stages, size_t lds, const KernelArgs* slots, hipStream_t st);
 
+// ---- the master section (master.hip): run sums into a.runs, the tree over them into a.master, a.stats when given ----
+void launch_master(const MasterArgs& a, hipStream_t st);
+
 }  // namespace srack

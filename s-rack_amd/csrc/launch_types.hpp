@@ -21,4 +21,17 @@ struct CtlWork {
 // The time-parallel FM pairs' launch shape (fm_block.hip.h): pick_kernel needs it for the voices per workgroup and the shortest ring.
 constexpr int kBlkVoices = 32, kBlkSlices = 16, kBlkPer = 16, kBlkChunk = kBlkSlices * kBlkPer;  // 256 samples per chunk
 
+// One srack_buses_master call (master.hip.h).
+struct MasterArgs {
+    const float* rows;   // [n_buses][row_channels][n]
+    const float* gain;   // [n_buses][2]
+    float* runs;         // [n_runs][2][n]: the run sums (the handle's scratch)
+    float* master;       // [2][n]
+    double* stats;       // [2][SRACK_STAT_COUNT] or null
+    uint32_t n;          // samples
+    uint32_t n_buses;
+    uint32_t row_channels;
+    uint32_t used;       // min(row_channels, 2): the channels that are summed
+};
+
 }  // namespace srack

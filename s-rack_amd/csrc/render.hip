@@ -240,6 +240,7 @@ void device_release(DeviceState* d)
 PatchHandle::~PatchHandle()
 {
     device_busfx_drop(*this);
+    device_master_drop(*this);
     device_release(dev);
     device_release(dev_old);
 }
@@ -1621,6 +1622,96 @@ int device_buses_reverb(PatchHandle& h, uint32_t n_samples, const float* d_bus_m
 std::string device_busfx_note(const PatchHandle& h)
 {
     return h.busfx.ran ? " busfx=" + std::to_string(h.busfx.last_enabled) + "[block " + std::to_string(h.busfx.last_block) + "]" : std::string();
+}
+
+// ---- the master section (master.hip.h, launched through launch_master) -------------------------------------------------------------
+// Gains on the device, uploaded again after a change — behind a host-side wait for the last call's kernels, which may still be reading
+// them —, and the run sums' scratch, grown on demand (the old one freed behind the same wait).  A tick session of unchanged gains and
+// call lengths is the launches and one event per call.
+static void master_wait(Master& M)
+{
+    if (M.ev_done) (void)hipEventSynchronize((hipEvent_t)M.ev_done);
+}
+
+void device_master_gains_changed(PatchHandle& h) { h.master.gain_dirty = true; }
+
+void device_master_drop(PatchHandle& h)
+{
+    Master& M = h.master;
+    master_wait(M);
+    if (M.d_gain) (void)hipFree(M.d_gain);
+    if (M.d_runs) (void)hipFree(M.d_runs);
+    if (M.ev_done) (void)hipEventDestroy((hipEvent_t)M.ev_done);
+    M = Master();
+}
+
+int device_buses_master(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_master, double* d_master_stats, void* stream)
+{
+    Master& M = h.master;
+    const hipStream_t st = (hipStream_t)stream;
+    const uint32_t n_buses = h.n_buses;
+    const uint32_t n_runs = (n_buses + SRACK_MASTER_RUN - 1) / SRACK_MASTER_RUN;
+    if (!M.ev_done) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        M.ev_done = e;
+    } else {
+        HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)M.ev_done, 0));  // (calls may come on different streams: the scratch is one)
+    }
+    const size_t want = (size_t)n_runs * 2 * n_samples;
+    if (M.runs_floats < want) {  // (allocated first, swapped in on success: a failure leaves the earlier scratch)
+        void* p = nullptr;
+        if (hipMalloc(&p, sizeof(float) * want) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("buses_master: out of device memory for the run sums (" + std::to_string(sizeof(float) * want) + " bytes)");
+            return SRACK_ERR_NOMEM;
+        }
+        master_wait(M);
+        if (M.d_runs) (void)hipFree(M.d_runs);
+        M.d_runs = p;
+        M.runs_floats = want;
+    }
+    if (M.gain_dirty || !M.d_gain) {
+        if (M.gain_buses < n_buses) {
+            void* p = nullptr;
+            if (hipMalloc(&p, sizeof(float) * 2 * n_buses) != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("buses_master: out of device memory for the gains");
+                return SRACK_ERR_NOMEM;
+            }
+            master_wait(M);
+            if (M.d_gain) (void)hipFree(M.d_gain);
+            M.d_gain = p;
+            M.gain_buses = n_buses;
+        }
+        master_wait(M);
+        const std::vector<float> ones(M.set ? 0 : (size_t)2 * n_buses, 1.0f);
+        HIP_TRY(hipMemcpy(M.d_gain, M.set ? M.gain.data() : ones.data(), sizeof(float) * 2 * n_buses, hipMemcpyHostToDevice));
+        M.gain_dirty = false;
+    }
+    MasterArgs a;
+    a.rows = d_rows;
+    a.gain = (const float*)M.d_gain;
+    a.runs = (float*)M.d_runs;
+    a.master = d_master;
+    a.stats = d_master_stats;
+    a.n = n_samples;
+    a.n_buses = n_buses;
+    a.row_channels = row_channels;
+    a.used = row_channels < 2 ? row_channels : 2u;
+    launch_master(a, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord((hipEvent_t)M.ev_done, st));
+    M.last_buses = n_buses;
+    M.ran = true;
+    return SRACK_OK;
+}
+
+std::string device_master_note(const PatchHandle& h)
+{
+    if (!h.master.ran) return std::string();
+    const uint32_t n_runs = (h.master.last_buses + SRACK_MASTER_RUN - 1) / SRACK_MASTER_RUN;
+    return " master=" + std::to_string(h.master.last_buses) + "[" + std::to_string(n_runs) + " runs]";
 }
 
 const char* device_kernel_name(const PatchHandle& h) { return h.dev ? h.dev->kernel_name : ""; }

@@ -34,6 +34,22 @@ struct BusFx {
     bool ran = false;
 };
 
+// The master section (srack_buses_set_master / srack_buses_master): a gain per bus and channel, the buses summed to one stereo pair.
+// Like the reverbs it hangs off the handle: not the program's, not DeviceState's; dropped with the table.
+struct Master {
+    bool set = false;
+    std::vector<float> gain;        // [n_buses][2] as the host gave them; empty: 1.0f everywhere
+    // device side (render.hip); nothing of it exists before the first srack_buses_master
+    void* d_gain = nullptr;         // f32 [gain_buses][2]
+    size_t gain_buses = 0;
+    bool gain_dirty = true;
+    void* d_runs = nullptr;         // the run sums, f32 [n_runs][2][n_samples]: grown on demand
+    size_t runs_floats = 0;
+    void* ev_done = nullptr;        // hipEvent_t behind every call's kernels: the next call, and whoever frees or rewrites, waits for it
+    uint32_t last_buses = 0;        // srack_render_info, once a call has run
+    bool ran = false;
+};
+
 struct PatchHandle {
     Graph graph;
     uint32_t n_voices = 0;
@@ -69,6 +85,7 @@ struct PatchHandle {
     BusPlan bus_plan;
     uint64_t bus_revision = 0;
     BusFx busfx;                    // the bus reverbs; dropped with the table (srack_voices_configure, another n_buses)
+    Master master;                  // the master section; dropped with the table as well
     bool timing_armed = false;      // srack_render_kernel_ms has been called: renders bracket the dominant kernel with HIP events
 
     ~PatchHandle();
@@ -93,6 +110,11 @@ int device_buses_reverb(PatchHandle& h, uint32_t n_samples, const float* d_bus_m
 void device_busfx_free_bus(PatchHandle& h, uint32_t bus);  // the bus's state, once no call uses it any more
 void device_busfx_drop(PatchHandle& h);                    // parameters and state of every bus
 std::string device_busfx_note(const PatchHandle& h);  // " busfx=3[block 244]" once a call has run, else ""
+// The master section: one call's work enqueued on `stream` (uploading the gains when they changed, growing the scratch).
+int device_buses_master(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_master, double* d_master_stats, void* stream);
+void device_master_gains_changed(PatchHandle& h);  // the host's gains were replaced: the next call uploads them
+void device_master_drop(PatchHandle& h);           // gains, scratch and the note
+std::string device_master_note(const PatchHandle& h);  // " master=4096[64 runs]" once a call has run, else ""
 std::string device_bus_note(const PatchHandle& h);  // " buses=4096[fold]" when the last render filled bus mixes, else ""
 std::string device_waves_note(const PatchHandle& h);  // " waves=9[lds]" / " waves=9[global]" for a patch that renders with a wave assignment, else ""
 std::string device_sequences_note(const PatchHandle& h);  // " sequences=9[global]" for a patch that renders with a sequence assignment, else ""

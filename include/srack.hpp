@@ -207,6 +207,28 @@ public:
     {
         check(srack_buses_master(p_, n_samples, d_rows, row_channels, d_master, d_master_stats, stream));
     }
+    // The bus sends: send i adds gain[i][c] * rows[src[i]][c] to bus dst[i], every bus keeps its own row times through[b][c] (gain f32
+    // [n_sends][2], through f32 [n_buses][2]; nullptr: 1.0f everywhere).  n_sends == 0 removes them.  Not part of the program: restarts
+    // nothing, and the sends survive an edit of the patch.
+    void set_sends(uint32_t n_sends, const int* src, const int* dst, const float* gain = nullptr, const float* through = nullptr)
+    {
+        check(srack_buses_set_sends(p_, n_sends, src, dst, gain, through));
+    }
+    uint32_t get_sends(int* src = nullptr, int* dst = nullptr, float* gain = nullptr, uint32_t cap = 0, float* through = nullptr, uint32_t through_cap = 0) const
+    {
+        return (uint32_t)check(srack_buses_get_sends(p_, src, dst, gain, cap, through, through_cap));
+    }
+    // -> the number of runs; n_terms [n_buses] (through term included), order: the send indices grouped by destination ascending
+    uint32_t send_plan(int* n_terms = nullptr, uint32_t bus_cap = 0, int* order = nullptr, uint32_t order_cap = 0) const
+    {
+        return (uint32_t)check(srack_buses_send_plan(p_, n_terms, bus_cap, order, order_cap));
+    }
+    // d_rows f32 [n_buses][row_channels][n_samples] -> d_out of the same shape (no overlap): one level of routing, per destination the
+    // master's order of additions over its terms.  Asynchronous on `stream`.  A sharded host reduces the bus mixes first and sends on the root.
+    void send(uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_out, void* stream = nullptr)
+    {
+        check(srack_buses_send(p_, n_samples, d_rows, row_channels, d_out, stream));
+    }
     // execute_batch plus d_bus_mix, f32 [n_buses][channels][n_samples] (written); d_frames, d_mix, d_stats may each be null
     void execute_batch_buses(uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags = 0, void* stream = nullptr)
     {

@@ -546,6 +546,63 @@ int srack_buses_get_master(const srack_patch* p, float* gain, uint32_t cap);
 int srack_buses_master(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels,
                        float* d_master, double* d_master_stats, void* stream);
 
+/* ---- bus sends: aux sends from bus to bus, one gather-sum per destination bus ------------------------------------
+ * MonoMixerModule (mixer.rs:106-119: output.fill(0.0); *dst += src * gain) in front of every bus, with as many inputs as the bus has
+ * feeders: a host with thousands of group buses wants a handful of aux buses that carry the rooms, every group bus sending some of
+ * its signal there, and not f32 [n_buses][channels][T] to read back and mix itself.
+ * The sends are a list of n_sends triples (src[i], dst[i], gain[i][2]), and there is a through gain through[b][2] per bus.  For every
+ * destination bus d the terms are: term 0 = (d, through[d]); then the sends i with dst[i] == d, in ascending i — a stable grouping of
+ * the host's list, which need not be sorted.  Each term is
+ *   p_k = fl32(g_k[c] * rows[src_k][c][t]),   c = 0, 1
+ * and out[d][c][t] is the master section's three-level tree over p_0 .. p_{n-1}:
+ *   run r    = ((+0.0f + p[64r]) + p[64r+1]) + ...   over its up to SRACK_MASTER_RUN terms, ascending
+ *   block k  = +0.0f plus its up to SRACK_MASTER_BLOCK run sums, ascending
+ *   out      = +0.0f plus the up to 16 block sums, ascending
+ * Product and sum are IEEE f32, one rounding per operation, no fma.  The order of the additions is part of the ABI.  It depends on
+ * the send list alone — never on n_samples or on how the samples are cut into calls.  Up to 64 terms it is MonoMixerModule's loop
+ * exactly; a bus with no sends is +0.0f + p_0: its row times the through gain, -0.0 becoming +0.0.  (A run sum is never -0.0, so a
+ * level with a single addend changes no bit.)
+ * Sends read the input rows only, never the output: one call is one level of routing, a chain of sends is two calls.  src == dst is
+ * allowed (a second gain on the bus's own row), so are duplicate pairs, and ANY f32 gain, the reference's way: 0 * inf is NaN; a
+ * non-finite sample or gain reaches the destinations it is sent to and no others.
+ * Limits: n_sends <= SRACK_MAX_SENDS; a destination has at most 65536 terms, the through term included — the tree's capacity.
+ *
+ * set_sends: src, dst (int [n_sends]), gain (f32 [n_sends][2], NULL = 1.0f) and through (f32 [n_buses][2], NULL = 1.0f) are host
+ * memory, the gains copied bit for bit.  n_sends == 0 removes the sends (the pointers may be NULL, through is ignored).
+ * SRACK_ERR_INVALID — the earlier sends staying in place — for n_sends > SRACK_MAX_SENDS, a null src or dst with n_sends > 0, an index
+ * outside [0, n_buses), a destination with more than 65535 sends.
+ * get_sends copies up to cap sends and up to through_cap buses (any pointer may be NULL) and returns n_sends, or 0 when none are set.
+ * send_plan: how the list is laid out — n_terms[b] the terms of bus b (through term included; up to bus_cap buses), order the send
+ * indices grouped by destination ascending, a destination's in the order they are added (up to order_cap) — and returns the number
+ * of runs, the sum over the buses of ceil(n_terms / SRACK_MASTER_RUN); 0 when no sends are set.
+ * The sends belong to the handle, NOT to the patch's program, exactly as the master's gains: setting, changing or running them does
+ * not re-flatten, restarts nothing, changes no bit of frames, mix, statistics, bus mixes, fx, master or voice state and not the kernel
+ * a patch renders with; they survive an edit that re-flattens the patch.  srack_voices_configure drops them; so does
+ * srack_voices_set_buses with another n_buses (the same n_buses keeps them).  Rack files carry nothing of this.
+ *
+ * The send call:
+ *   d_rows : device, f32 [n_buses][row_channels][n_samples] — what srack_render_buses writes.  1 <= row_channels <= 8; channels 0
+ *            and 1 are mixed, channels beyond the second are neither read nor written.  Any 4-byte aligned address; rows that are
+ *            16-byte aligned (both bases are, and n_samples % 4 == 0) are read four samples at a time.
+ *   d_out  : device, the same shape, written — every bus's row, a bus without sends included; srack_buses_reverb (row_channels = the
+ *            patch's channels) and srack_buses_master take it.  Must not overlap d_rows (SRACK_ERR_INVALID).
+ *   stream : as for srack_render: asynchronous, and the library touches the stream only during the call.
+ * Errors, in this order: SRACK_ERR_INVALID for a null handle; SRACK_ERR_STATE before srack_voices_configure or before a mix table
+ * exists (all four calls); SRACK_ERR_STATE for the send call before set_sends; n_samples == 0 is SRACK_OK and touches nothing;
+ * SRACK_ERR_INVALID for a null d_rows or d_out, row_channels outside 1..8 or an overlap.
+ * The run sums of the destinations of more than one run pass through scratch of the handle's, grown on demand: SRACK_ERR_NOMEM if that
+ * fails, the earlier state intact.  No floating-point atomics, every output float is written once (csrc/sends.hip.h).  A sharded host
+ * reduces the per-rank bus mixes first (srack_dist_reduce_mix) and sends on the root: a sum of per-rank sends has another association
+ * and other bits.  srack_render_info says " sends=<n_sends>[<runs> runs]" behind " buses=" once a send call has run. */
+#define SRACK_MAX_SENDS 1048576
+int srack_buses_set_sends(srack_patch* p, uint32_t n_sends, const int* src, const int* dst,
+                          const float* gain, const float* through);
+int srack_buses_get_sends(const srack_patch* p, int* src, int* dst, float* gain, uint32_t cap,
+                          float* through, uint32_t through_cap);
+int srack_buses_send_plan(const srack_patch* p, int* n_terms, uint32_t bus_cap, int* order, uint32_t order_cap);
+int srack_buses_send(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels,
+                     float* d_out, void* stream);
+
 /* Optional: do everything a later srack_render(p, <= n_samples, ..., flags) would do on first use — flatten the graph,
  * upload the programs and the voice table, size the scratch buffers (mix partials when want_mix, control tracks) — so
  * that the first render costs what every render costs.  Renders nothing and leaves the voice state untouched. */

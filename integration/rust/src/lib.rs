@@ -76,6 +76,10 @@ mod ffi {
         pub fn srack_buses_set_master(p: *mut SrackPatch, gain: *const f32) -> c_int;
         pub fn srack_buses_get_master(p: *const SrackPatch, gain: *mut f32, cap: u32) -> c_int;
         pub fn srack_buses_master(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_master: *mut f32, d_master_stats: *mut f64, stream: *mut c_void) -> c_int;
+        pub fn srack_buses_set_sends(p: *mut SrackPatch, n_sends: u32, src: *const c_int, dst: *const c_int, gain: *const f32, through: *const f32) -> c_int;
+        pub fn srack_buses_get_sends(p: *const SrackPatch, src: *mut c_int, dst: *mut c_int, gain: *mut f32, cap: u32, through: *mut f32, through_cap: u32) -> c_int;
+        pub fn srack_buses_send_plan(p: *const SrackPatch, n_terms: *mut c_int, bus_cap: u32, order: *mut c_int, order_cap: u32) -> c_int;
+        pub fn srack_buses_send(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_out: *mut f32, stream: *mut c_void) -> c_int;
         pub fn srack_device_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
         pub fn srack_device_free(d_ptr: *mut c_void) -> c_int;
         pub fn srack_device_to_host(h_dst: *mut c_void, d_src: *const c_void, bytes: usize, stream: *mut c_void) -> c_int;
@@ -437,6 +441,48 @@ impl Patch {
     pub fn master(&mut self, n_samples: u32, rows: &DeviceBuffer, row_channels: u32, master: &DeviceBuffer, stats: Option<&DeviceBuffer>) -> Result<(), Error> {
         let s = stats.map_or(std::ptr::null_mut(), |b| b.as_f64());
         check(unsafe { ffi::srack_buses_master(self.raw, n_samples, rows.as_f32() as *const f32, row_channels, master.as_f32(), s, std::ptr::null_mut()) }).map(|_| ())
+    }
+    /// The bus sends (`srack_buses_set_sends`): send `i` adds `gain[i][c] * rows[src[i]][c]` to bus `dst[i]`, and every bus keeps its own
+    /// row times `through[b][c]` — `gain` `[n_sends][2]`, `through` `[n_buses][2]`, any f32; None: 1.0 everywhere.  An empty list removes
+    /// the sends.  Not part of the program: restarts nothing, and the sends survive an edit of the patch.
+    pub fn set_sends(&mut self, src: &[i32], dst: &[i32], gain: Option<&[f32]>, through: Option<&[f32]>) -> Result<(), Error> {
+        assert_eq!(src.len(), dst.len());
+        assert!(gain.map_or(true, |g| g.len() == 2 * src.len()));
+        check(unsafe {
+            ffi::srack_buses_set_sends(self.raw, src.len() as u32, src.as_ptr(), dst.as_ptr(), gain.map_or(std::ptr::null(), |x| x.as_ptr()),
+                                       through.map_or(std::ptr::null(), |x| x.as_ptr()))
+        })
+        .map(|_| ())
+    }
+    /// The sends set: `(src, dst, gain [n_sends][2], through [n_buses][2])`; None when none are.
+    pub fn get_sends(&self) -> Result<Option<(Vec<i32>, Vec<i32>, Vec<f32>, Vec<f32>)>, Error> {
+        let n = check(unsafe { ffi::srack_buses_get_sends(self.raw, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), 0, std::ptr::null_mut(), 0) })? as usize;
+        if n == 0 {
+            return Ok(None);
+        }
+        let nb = check(unsafe { ffi::srack_voices_get_buses(self.raw, std::ptr::null_mut(), std::ptr::null_mut(), 0) })? as usize;
+        let (mut s, mut d, mut g, mut t) = (vec![0i32; n], vec![0i32; n], vec![0f32; n * 2], vec![0f32; nb * 2]);
+        check(unsafe { ffi::srack_buses_get_sends(self.raw, s.as_mut_ptr(), d.as_mut_ptr(), g.as_mut_ptr(), n as u32, t.as_mut_ptr(), nb as u32) })?;
+        Ok(Some((s, d, g, t)))
+    }
+    /// How the list is laid out (`srack_buses_send_plan`): the terms of every bus (through term included), the send indices grouped by
+    /// destination ascending, and the number of runs; None when no sends are set.
+    pub fn send_plan(&self) -> Result<Option<(Vec<i32>, Vec<i32>, u32)>, Error> {
+        let n = check(unsafe { ffi::srack_buses_get_sends(self.raw, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), 0, std::ptr::null_mut(), 0) })? as usize;
+        if n == 0 {
+            return Ok(None);
+        }
+        let nb = check(unsafe { ffi::srack_voices_get_buses(self.raw, std::ptr::null_mut(), std::ptr::null_mut(), 0) })? as usize;
+        let (mut terms, mut order) = (vec![0i32; nb], vec![0i32; n]);
+        let runs = check(unsafe { ffi::srack_buses_send_plan(self.raw, terms.as_mut_ptr(), nb as u32, order.as_mut_ptr(), n as u32) })?;
+        Ok(Some((terms, order, runs as u32)))
+    }
+    /// One level of routing (`srack_buses_send`): `rows` `[n_buses][row_channels][n_samples]` f32 in — what `execute_batch_buses` wrote —,
+    /// `out` of the same shape written (channels 0 and 1; no overlap), ready for `bus_reverb` and `master`.  Per destination the master's
+    /// order of additions over its terms, a function of the send list alone.  A sharded host reduces the per-rank bus mixes first and
+    /// sends on the root.
+    pub fn send(&mut self, n_samples: u32, rows: &DeviceBuffer, row_channels: u32, out: &DeviceBuffer) -> Result<(), Error> {
+        check(unsafe { ffi::srack_buses_send(self.raw, n_samples, rows.as_f32() as *const f32, row_channels, out.as_f32(), std::ptr::null_mut()) }).map(|_| ())
     }
 }
 

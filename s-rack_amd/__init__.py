@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libsrack_hip.so")
 OK, ERR_INVALID, ERR_PORT, ERR_NO_OUTPUT, ERR_SELF_LOOP, ERR_STATE, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8
 MAX_BUSES, BUS_NONE = 65536, -1
 MASTER_RUN, MASTER_BLOCK = 64, 64  # buses per run, runs per block: the order srack_buses_master adds in
+MAX_SENDS = 1048576  # srack_buses_set_sends: the longest send list
 FREEVERB_DEFAULTS = (0.5, 0.0, 1.0, 0.5, 0.5, 0.0)  # FreeverbModule's six parameters in field order: what set_bus_reverbs(None) gives every bus
 WAVE_OWN = -1
 SEQ_OWN, MAX_SEQUENCES = -1, 65536
@@ -36,6 +37,7 @@ ABI_SYMBOLS = [
     "srack_voices_set_buses", "srack_voices_get_buses", "srack_voices_bus_plan", "srack_render_buses",
     "srack_buses_set_reverb", "srack_buses_get_reverb", "srack_buses_reset_reverb", "srack_buses_reverb_plan", "srack_buses_reverb",
     "srack_buses_set_master", "srack_buses_get_master", "srack_buses_master",
+    "srack_buses_set_sends", "srack_buses_get_sends", "srack_buses_send_plan", "srack_buses_send",
     "srack_patch_set_wave_bank", "srack_patch_get_wave_bank", "srack_patch_get_wave_bank_samples", "srack_voices_set_waves", "srack_voices_get_waves",
     "srack_patch_set_sequence_bank", "srack_patch_get_sequence_bank", "srack_voices_set_sequences", "srack_voices_get_sequences",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
@@ -117,6 +119,11 @@ def _load():
         L.srack_buses_set_master.argtypes = [vp, fp]
         L.srack_buses_get_master.argtypes = [vp, fp, u32]
         L.srack_buses_master.argtypes = [vp, u32, vp, u32, vp, vp, vp]
+    if hasattr(L, "srack_buses_send"):
+        L.srack_buses_set_sends.argtypes = [vp, u32, ip, ip, fp, fp]
+        L.srack_buses_get_sends.argtypes = [vp, ip, ip, fp, u32, fp, u32]
+        L.srack_buses_send_plan.argtypes = [vp, ip, u32, ip, u32]
+        L.srack_buses_send.argtypes = [vp, u32, vp, u32, vp, vp]
     if hasattr(L, "srack_voices_set_waves"):  # (tools/ alternate older builds of the library under this binding)
         L.srack_patch_set_wave_bank.argtypes = [vp, i32, fp, ip, fp, u32]
         L.srack_patch_get_wave_bank.argtypes = [vp, i32, ip, fp, u32]
@@ -608,6 +615,76 @@ class Patch:
             return out, st
         finally:
             for d in (d_in, d_out, d_st):
+                if d.value:
+                    lib.srack_device_free(d)
+
+    # ---- bus sends: aux sends from bus to bus, a gather-sum per destination bus -------------------------
+    def set_sends(self, src, dst, gain=None, through=None):
+        """srack_buses_set_sends: src, dst int [n_sends], gain f32 [n_sends][2] (None: 1.0), through f32 [n_buses][2] (None: 1.0); any
+        f32.  An empty list removes the sends.  Not part of the program: restarts nothing."""
+        s, d = np.ascontiguousarray(src, dtype=np.intc), np.ascontiguousarray(dst, dtype=np.intc)
+        assert s.ndim == 1 and s.shape == d.shape, (s.shape, d.shape)
+        g = t = None
+        if gain is not None:
+            g = np.ascontiguousarray(gain, dtype=np.float32)
+            assert g.shape == (len(s), 2), g.shape
+        if through is not None:
+            n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+            t = np.ascontiguousarray(through, dtype=np.float32)
+            assert t.shape == (n_buses, 2), t.shape
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        _check(lib.srack_buses_set_sends(self.h, len(s), s.ctypes.data_as(ip), d.ctypes.data_as(ip), None if g is None else g.ctypes.data_as(fp),
+                                         None if t is None else t.ctypes.data_as(fp)))
+
+    def get_sends(self):
+        """-> (src int32 [n_sends], dst int32 [n_sends], gain f32 [n_sends][2], through f32 [n_buses][2]), or None when no sends are set"""
+        n = _check(lib.srack_buses_get_sends(self.h, None, None, None, 0, None, 0))
+        if n == 0:
+            return None
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        s, d = np.empty(n, dtype=np.intc), np.empty(n, dtype=np.intc)
+        g, t = np.empty((n, 2), dtype=np.float32), np.empty((n_buses, 2), dtype=np.float32)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        _check(lib.srack_buses_get_sends(self.h, s.ctypes.data_as(ip), d.ctypes.data_as(ip), g.ctypes.data_as(fp), n, t.ctypes.data_as(fp), n_buses))
+        return s, d, g, t
+
+    def send_plan(self):
+        """How the list is laid out (srack_buses_send_plan) -> (n_terms int32 [n_buses], through term included; order: the send indices
+        grouped by destination ascending; the number of runs), or None when no sends are set"""
+        n = _check(lib.srack_buses_get_sends(self.h, None, None, None, 0, None, 0))
+        if n == 0:
+            return None
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        nt, order = np.zeros(n_buses, dtype=np.intc), np.zeros(n, dtype=np.intc)
+        ip = C.POINTER(C.c_int)
+        runs = _check(lib.srack_buses_send_plan(self.h, nt.ctypes.data_as(ip), n_buses, order.ctypes.data_as(ip), n))
+        return nt, order, runs
+
+    def send_raw(self, n_samples, d_rows, row_channels, d_out, stream=None):
+        """Device pointers in; asynchronous on `stream` (srack_buses_send): d_rows and d_out f32 [n_buses][row_channels][n]."""
+        _check(lib.srack_buses_send(self.h, n_samples, d_rows, row_channels, d_out, stream))
+
+    def send(self, rows):
+        """Convenience for tests: rows f32 [n_buses][row_channels][T] from the host through the sends -> f32 of the same shape
+        (channels beyond the second are not written: they come back as zeros, which is what the output buffer is filled with)."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
+        out = np.zeros_like(x)
+        d_in, d_out = C.c_void_p(), C.c_void_p()
+        try:
+            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
+            _check(lib.srack_device_alloc(C.byref(d_out), max(4, out.nbytes)))
+            if x.nbytes:
+                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
+                _check(lib.srack_device_from_host(d_out, out.ctypes.data_as(C.c_void_p), out.nbytes, None))
+            self.send_raw(x.shape[2], d_in, x.shape[1], d_out, None)
+            if out.nbytes:
+                _check(lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), d_out, out.nbytes, None))
+            _check(lib.srack_device_sync(None))
+            return out
+        finally:
+            for d in (d_in, d_out):
                 if d.value:
                     lib.srack_device_free(d)
 

@@ -688,6 +688,7 @@ int srack_voices_configure(srack_patch* p, uint32_t n_voices)
         p->h.bus_revision++;
         device_busfx_drop(p->h);  // the reverbs sat behind that table
         device_master_drop(p->h);  // ... and so did the master's gains
+        device_sends_drop(p->h);   // ... and the sends between its buses
         return SRACK_OK;
     });
 }
@@ -759,9 +760,10 @@ int srack_voices_set_buses(srack_patch* p, uint32_t n_buses, const int* bus, con
         if (bus) std::copy(bus, bus + h.n_voices, b.begin());
         if (gain) std::copy(gain, gain + h.n_voices, g.begin());
         BusPlan plan = bus_plan_make(h.n_voices, n_buses, b.data());
-        if (n_buses != h.n_buses) {  // other buses: their reverbs go, parameters and state, and the master's gains (the same count keeps all)
+        if (n_buses != h.n_buses) {  // other buses: their reverbs go, parameters and state, the master's gains and the sends (the same count keeps all)
             device_busfx_drop(h);
             device_master_drop(h);
+            device_sends_drop(h);
         }
         h.n_buses = n_buses;
         h.bus = std::move(b);
@@ -1020,6 +1022,164 @@ int srack_buses_master(srack_patch* p, uint32_t n_samples, const float* d_rows, 
     });
 }
 
+// ---- the bus sends -------------------------------------------------------------------------------------------------
+// The host's list laid out for the kernels (sends.hip.h): a stable grouping by destination, the terms in CSR order with every
+// destination's through term first, one run per SRACK_MASTER_RUN terms.  A destination of one run is summed straight into its row; the
+// runs of any other get scratch rows, side by side, and an entry in the table of the tree kernel.
+static void sends_plan_make(Sends& S, uint32_t n_buses)
+{
+    const size_t n_sends = S.src.size();
+    S.n_terms.assign(n_buses, 1);
+    for (size_t i = 0; i < n_sends; i++) S.n_terms[S.dst[i]]++;
+    std::vector<size_t> first(n_buses + 1, 0);  // a destination's first term
+    for (uint32_t d = 0; d < n_buses; d++) first[d + 1] = first[d] + (size_t)S.n_terms[d];
+    S.term_src.assign(n_buses + n_sends, 0);
+    S.term_gain.assign((n_buses + n_sends) * 2, 0.0f);
+    S.order.assign(n_sends, 0);
+    std::vector<size_t> fill(n_buses);
+    for (uint32_t d = 0; d < n_buses; d++) {
+        S.term_src[first[d]] = d;
+        std::memcpy(&S.term_gain[first[d] * 2], &S.through[(size_t)d * 2], sizeof(float) * 2);
+        fill[d] = first[d] + 1;
+    }
+    for (size_t i = 0; i < n_sends; i++) {  // (ascending i within a destination: stable)
+        const size_t at = fill[S.dst[i]]++;
+        S.term_src[at] = (uint32_t)S.src[i];
+        std::memcpy(&S.term_gain[at * 2], &S.gain[i * 2], sizeof(float) * 2);
+        S.order[at - (size_t)S.dst[i] - 1] = (int32_t)i;  // (d + 1 through terms lie in front of destination d's sends)
+    }
+    S.runs.clear();
+    S.multi.clear();
+    S.scratch_rows = 0;
+    S.max_blocks = 0;
+    for (uint32_t d = 0; d < n_buses; d++) {
+        const uint32_t n = (uint32_t)S.n_terms[d], n_runs = (n + SRACK_MASTER_RUN - 1) / SRACK_MASTER_RUN;
+        if (n_runs > 1) {
+            const uint32_t m[4] = {d, S.scratch_rows, n_runs, 0u};
+            S.multi.insert(S.multi.end(), m, m + 4);
+            S.max_blocks = std::max(S.max_blocks, (n_runs + SRACK_MASTER_BLOCK - 1) / SRACK_MASTER_BLOCK);
+        }
+        for (uint32_t r = 0; r < n_runs; r++) {
+            const uint32_t run[4] = {d, (uint32_t)first[d] + r * SRACK_MASTER_RUN, std::min<uint32_t>(SRACK_MASTER_RUN, n - r * SRACK_MASTER_RUN),
+                                     n_runs > 1 ? S.scratch_rows + r : 0xFFFFFFFFu};
+            S.runs.insert(S.runs.end(), run, run + 4);
+        }
+        if (n_runs > 1) S.scratch_rows += n_runs;
+    }
+}
+
+int srack_buses_set_sends(srack_patch* p, uint32_t n_sends, const int* src, const int* dst, const float* gain, const float* through)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_set_sends");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        if (n_sends > SRACK_MAX_SENDS) {
+            set_error("buses_set_sends: n_sends must be at most " + std::to_string(SRACK_MAX_SENDS));
+            return SRACK_ERR_INVALID;
+        }
+        if (n_sends == 0) {  // no sends: none set
+            device_sends_drop(h);
+            return SRACK_OK;
+        }
+        if (!src || !dst) {
+            set_error("buses_set_sends: src and dst must be given");
+            return SRACK_ERR_INVALID;
+        }
+        std::vector<uint32_t> feeders(h.n_buses, 0);
+        for (uint32_t i = 0; i < n_sends; i++) {
+            if (src[i] < 0 || (uint32_t)src[i] >= h.n_buses || dst[i] < 0 || (uint32_t)dst[i] >= h.n_buses) {
+                set_error("buses_set_sends: send " + std::to_string(i) + " goes from bus " + std::to_string(src[i]) + " to bus " + std::to_string(dst[i]) + " of " +
+                          std::to_string(h.n_buses));
+                return SRACK_ERR_INVALID;
+            }
+            if (++feeders[dst[i]] > 65535u) {  // (with the through term: the tree's 16 blocks of 64 runs of 64 terms)
+                set_error("buses_set_sends: bus " + std::to_string(dst[i]) + " is the destination of more than 65535 sends");
+                return SRACK_ERR_INVALID;
+            }
+        }
+        // (built aside and committed at the end: a failure above or an allocation failure here leaves the earlier sends in place)
+        Sends S;
+        S.src.assign(src, src + n_sends);
+        S.dst.assign(dst, dst + n_sends);
+        S.gain.assign((size_t)n_sends * 2, 1.0f);
+        S.through.assign((size_t)h.n_buses * 2, 1.0f);
+        if (gain) std::memcpy(S.gain.data(), gain, sizeof(float) * S.gain.size());  // (bit for bit: NaN payloads, signed zeros)
+        if (through) std::memcpy(S.through.data(), through, sizeof(float) * S.through.size());
+        sends_plan_make(S, h.n_buses);
+        Sends& T = h.sends;  // the device side stays: tables (uploaded again by the next call), scratch, event and note
+        T.src = std::move(S.src), T.dst = std::move(S.dst), T.gain = std::move(S.gain), T.through = std::move(S.through);
+        T.n_terms = std::move(S.n_terms), T.order = std::move(S.order), T.term_src = std::move(S.term_src), T.term_gain = std::move(S.term_gain);
+        T.runs = std::move(S.runs), T.multi = std::move(S.multi);
+        T.scratch_rows = S.scratch_rows;
+        T.max_blocks = S.max_blocks;
+        T.set = true;
+        device_sends_changed(h);
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_get_sends(const srack_patch* p, int* src, int* dst, float* gain, uint32_t cap, float* through, uint32_t through_cap)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_get_sends");
+        if (rc != SRACK_OK) return rc;
+        const PatchHandle& h = p->h;
+        const Sends& S = h.sends;
+        if (!S.set) return 0;
+        const size_t n = std::min<size_t>(cap, S.src.size()), nb = std::min<size_t>(through_cap, h.n_buses);
+        if (src && n) std::memcpy(src, S.src.data(), sizeof(int) * n);
+        if (dst && n) std::memcpy(dst, S.dst.data(), sizeof(int) * n);
+        if (gain && n) std::memcpy(gain, S.gain.data(), sizeof(float) * 2 * n);
+        if (through && nb) std::memcpy(through, S.through.data(), sizeof(float) * 2 * nb);
+        return (int)S.src.size();
+    });
+}
+
+int srack_buses_send_plan(const srack_patch* p, int* n_terms, uint32_t bus_cap, int* order, uint32_t order_cap)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_send_plan");
+        if (rc != SRACK_OK) return rc;
+        const PatchHandle& h = p->h;
+        const Sends& S = h.sends;
+        if (!S.set) return 0;
+        const size_t nb = std::min<size_t>(bus_cap, h.n_buses), n = std::min<size_t>(order_cap, S.order.size());
+        if (n_terms && nb) std::memcpy(n_terms, S.n_terms.data(), sizeof(int) * nb);
+        if (order && n) std::memcpy(order, S.order.data(), sizeof(int) * n);
+        return (int)(S.runs.size() / 4);
+    });
+}
+
+int srack_buses_send(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_out, void* stream)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_send");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        if (!h.sends.set) {
+            set_error("buses_send: no sends set: call srack_buses_set_sends first");
+            return SRACK_ERR_STATE;
+        }
+        if (n_samples == 0) return SRACK_OK;
+        if (!d_rows || !d_out) {
+            set_error("buses_send: d_rows and d_out must be given");
+            return SRACK_ERR_INVALID;
+        }
+        if (row_channels < 1 || row_channels > 8) {
+            set_error("buses_send: row_channels must be 1 .. 8");
+            return SRACK_ERR_INVALID;
+        }
+        const uintptr_t in0 = (uintptr_t)d_rows, out0 = (uintptr_t)d_out;
+        const uint64_t bytes = 4ull * h.n_buses * row_channels * n_samples;
+        if (in0 < out0 + bytes && out0 < in0 + bytes) {
+            set_error("buses_send: d_out overlaps d_rows");
+            return SRACK_ERR_INVALID;
+        }
+        return device_buses_send(h, n_samples, d_rows, row_channels, d_out, stream);
+    });
+}
+
 int srack_render_reserve(srack_patch* p, uint32_t n_samples, int want_mix, uint32_t flags)
 {
     return guarded([&]() -> int {
@@ -1060,6 +1220,7 @@ int srack_render_info(srack_patch* p, char* buf, size_t cap)
         const char* k = device_kernel_name(p->h);
         // (the kernel's name stays LAST: hosts and tests read it with split("kernel="))
         s += device_bus_note(p->h);
+        s += device_sends_note(p->h);
         s += device_busfx_note(p->h);
         s += device_master_note(p->h);
         s += device_waves_note(p->h);

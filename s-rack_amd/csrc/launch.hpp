@@ -86,4 +86,7 @@ void launch_interp_stages(bool exact, uint32_t n_stages, size_t lds, const Kerne
 // ---- the master section (master.hip): run sums into a.runs, the tree over them into a.master, a.stats when given ----
 void launch_master(const MasterArgs& a, hipStream_t st);
 
+// ---- the bus sends (sends.hip): every destination's run sums, into a.out or a.scratch, and the tree over the scratch rows into a.out ----
+void launch_sends(const SendArgs& a, hipStream_t st);
+
 }  // namespace srack

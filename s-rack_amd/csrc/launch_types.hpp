@@ -34,4 +34,34 @@ struct MasterArgs {
     uint32_t used;       // min(row_channels, 2): the channels that are summed
 };
 
+// One srack_buses_send call (sends.hip.h).  The tables are made on the host when the sends are set (capi.cpp, sends_plan_make).
+struct SendRun {
+    uint32_t dst;        // the destination bus
+    uint32_t first;      // its first term in the term table ...
+    uint32_t count;      // ... and how many it has: 1 .. SRACK_MASTER_RUN
+    int32_t srow;        // the scratch row the run sum goes to; < 0: the destination has this run only, the sum is its row of out
+};
+struct SendMulti {       // a destination of more than one run
+    uint32_t dst;
+    uint32_t first_row;  // its first scratch row
+    uint32_t n_runs;
+    uint32_t pad;
+};
+static_assert(sizeof(SendRun) == 16 && sizeof(SendMulti) == 16, "the host keeps both tables as four 32-bit words per entry (runtime.hpp)");
+struct SendArgs {
+    const float* rows;          // [n_buses][row_channels][n]
+    float* out;                 // [n_buses][row_channels][n]
+    float* scratch;             // [scratch rows][2][n]: the run sums of the destinations of several runs (the handle's)
+    const uint32_t* term_src;   // [n_buses + n_sends] the terms in CSR order, a destination's through term first: source bus ...
+    const float* term_gain;     // ... and gain pair [n_buses + n_sends][2]
+    const SendRun* runs;        // [n_runs]
+    const SendMulti* multi;     // [n_multi]
+    uint32_t n;                 // samples
+    uint32_t row_channels;
+    uint32_t used;              // min(row_channels, 2): the channels that are mixed
+    uint32_t n_runs;
+    uint32_t n_multi;
+    uint32_t max_blocks;        // the most blocks (of SRACK_MASTER_BLOCK runs) any destination has: send_tree's waves
+};
+
 }  // namespace srack

@@ -241,6 +241,7 @@ PatchHandle::~PatchHandle()
 {
     device_busfx_drop(*this);
     device_master_drop(*this);
+    device_sends_drop(*this);
     device_release(dev);
     device_release(dev_old);
 }
@@ -1712,6 +1713,106 @@ std::string device_master_note(const PatchHandle& h)
     if (!h.master.ran) return std::string();
     const uint32_t n_runs = (h.master.last_buses + SRACK_MASTER_RUN - 1) / SRACK_MASTER_RUN;
     return " master=" + std::to_string(h.master.last_buses) + "[" + std::to_string(n_runs) + " runs]";
+}
+
+// ---- the bus sends (sends.hip.h, launched through launch_sends) ----------------------------------------------------------------------
+// The tables of the plan on the device in one allocation, uploaded again after a change — behind a host-side wait for the last call's
+// kernels, which may still be reading them —, and the scratch for the run sums of the destinations of several runs, grown on demand
+// (the old one freed behind the same wait).  A tick session of an unchanged list and call lengths is the launches and one event per call.
+static void sends_wait(Sends& S)
+{
+    if (S.ev_done) (void)hipEventSynchronize((hipEvent_t)S.ev_done);
+}
+
+void device_sends_changed(PatchHandle& h) { h.sends.tab_dirty = true; }
+
+void device_sends_drop(PatchHandle& h)
+{
+    Sends& S = h.sends;
+    sends_wait(S);
+    if (S.d_tab) (void)hipFree(S.d_tab);
+    if (S.d_scratch) (void)hipFree(S.d_scratch);
+    if (S.ev_done) (void)hipEventDestroy((hipEvent_t)S.ev_done);
+    S = Sends();
+}
+
+int device_buses_send(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_out, void* stream)
+{
+    Sends& S = h.sends;
+    const hipStream_t st = (hipStream_t)stream;
+    if (!S.ev_done) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        S.ev_done = e;
+    } else {
+        HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)S.ev_done, 0));  // (calls may come on different streams: the scratch is one)
+    }
+    const size_t want = (size_t)S.scratch_rows * 2 * n_samples;
+    if (S.scratch_floats < want) {  // (allocated first, swapped in on success: a failure leaves the earlier scratch)
+        void* p = nullptr;
+        if (hipMalloc(&p, sizeof(float) * want) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("buses_send: out of device memory for the run sums (" + std::to_string(sizeof(float) * want) + " bytes)");
+            return SRACK_ERR_NOMEM;
+        }
+        sends_wait(S);
+        if (S.d_scratch) (void)hipFree(S.d_scratch);
+        S.d_scratch = p;
+        S.scratch_floats = want;
+    }
+    // the tables side by side, each from a 16-byte boundary
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t at_src = 0, at_gain = up16(at_src + sizeof(uint32_t) * S.term_src.size());
+    const size_t at_runs = up16(at_gain + sizeof(float) * S.term_gain.size()), at_multi = up16(at_runs + sizeof(uint32_t) * S.runs.size());
+    const size_t bytes = up16(at_multi + sizeof(uint32_t) * S.multi.size()) + 16;
+    if (S.tab_dirty || !S.d_tab) {
+        if (S.tab_bytes < bytes) {
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("buses_send: out of device memory for the send tables (" + std::to_string(bytes) + " bytes)");
+                return SRACK_ERR_NOMEM;
+            }
+            sends_wait(S);
+            if (S.d_tab) (void)hipFree(S.d_tab);
+            S.d_tab = p;
+            S.tab_bytes = bytes;
+        }
+        sends_wait(S);
+        char* tab = (char*)S.d_tab;
+        HIP_TRY(hipMemcpy(tab + at_src, S.term_src.data(), sizeof(uint32_t) * S.term_src.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(tab + at_gain, S.term_gain.data(), sizeof(float) * S.term_gain.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(tab + at_runs, S.runs.data(), sizeof(uint32_t) * S.runs.size(), hipMemcpyHostToDevice));
+        if (!S.multi.empty()) HIP_TRY(hipMemcpy(tab + at_multi, S.multi.data(), sizeof(uint32_t) * S.multi.size(), hipMemcpyHostToDevice));
+        S.tab_dirty = false;
+    }
+    const char* tab = (const char*)S.d_tab;
+    SendArgs a;
+    a.rows = d_rows;
+    a.out = d_out;
+    a.scratch = (float*)S.d_scratch;
+    a.term_src = (const uint32_t*)(tab + at_src);
+    a.term_gain = (const float*)(tab + at_gain);
+    a.runs = (const SendRun*)(tab + at_runs);
+    a.multi = (const SendMulti*)(tab + at_multi);
+    a.n = n_samples;
+    a.row_channels = row_channels;
+    a.used = row_channels < 2 ? row_channels : 2u;
+    a.n_runs = (uint32_t)(S.runs.size() / 4);
+    a.n_multi = (uint32_t)(S.multi.size() / 4);
+    a.max_blocks = S.max_blocks;
+    launch_sends(a, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord((hipEvent_t)S.ev_done, st));
+    S.last_sends = (uint32_t)S.src.size();
+    S.last_runs = a.n_runs;
+    S.ran = true;
+    return SRACK_OK;
+}
+
+std::string device_sends_note(const PatchHandle& h)
+{
+    return h.sends.ran ? " sends=" + std::to_string(h.sends.last_sends) + "[" + std::to_string(h.sends.last_runs) + " runs]" : std::string();
 }
 
 const char* device_kernel_name(const PatchHandle& h) { return h.dev ? h.dev->kernel_name : ""; }

@@ -50,6 +50,33 @@ struct Master {
     bool ran = false;
 };
 
+// The bus sends (srack_buses_set_sends / srack_buses_send): aux sends from bus to bus, a gather-sum per destination bus.  Like the
+// master's gains they hang off the handle: not the program's, not DeviceState's; dropped with the table.
+struct Sends {
+    bool set = false;
+    std::vector<int32_t> src, dst;  // [n_sends] as the host gave them
+    std::vector<float> gain;        // [n_sends][2]
+    std::vector<float> through;     // [n_buses][2]
+    // the plan, made when the sends are set (capi.cpp, sends_plan_make)
+    std::vector<int32_t> n_terms;   // [n_buses] through term included
+    std::vector<int32_t> order;     // [n_sends] send indices grouped by destination ascending, stable
+    std::vector<uint32_t> term_src; // [n_buses + n_sends] the terms in that order, each destination's through term first
+    std::vector<float> term_gain;   // [n_buses + n_sends][2]
+    std::vector<uint32_t> runs;     // SendRun [n_runs] (launch_types.hpp), four words each
+    std::vector<uint32_t> multi;    // SendMulti [n_multi], four words each
+    uint32_t scratch_rows = 0;      // the runs of the destinations that have several
+    uint32_t max_blocks = 0;
+    // device side (render.hip); nothing of it exists before the first srack_buses_send
+    void* d_tab = nullptr;          // term_src | term_gain | runs | multi, each 16-byte aligned
+    size_t tab_bytes = 0;
+    bool tab_dirty = true;
+    void* d_scratch = nullptr;      // f32 [scratch_rows][2][n_samples]: grown on demand
+    size_t scratch_floats = 0;
+    void* ev_done = nullptr;        // hipEvent_t behind every call's kernels: the next call, and whoever frees or rewrites, waits for it
+    uint32_t last_sends = 0, last_runs = 0;  // srack_render_info, once a call has run
+    bool ran = false;
+};
+
 struct PatchHandle {
     Graph graph;
     uint32_t n_voices = 0;
@@ -86,6 +113,7 @@ struct PatchHandle {
     uint64_t bus_revision = 0;
     BusFx busfx;                    // the bus reverbs; dropped with the table (srack_voices_configure, another n_buses)
     Master master;                  // the master section; dropped with the table as well
+    Sends sends;                    // the bus sends; dropped with the table as well
     bool timing_armed = false;      // srack_render_kernel_ms has been called: renders bracket the dominant kernel with HIP events
 
     ~PatchHandle();
@@ -115,6 +143,11 @@ int device_buses_master(PatchHandle& h, uint32_t n_samples, const float* d_rows,
 void device_master_gains_changed(PatchHandle& h);  // the host's gains were replaced: the next call uploads them
 void device_master_drop(PatchHandle& h);           // gains, scratch and the note
 std::string device_master_note(const PatchHandle& h);  // " master=4096[64 runs]" once a call has run, else ""
+// The bus sends: one call's work enqueued on `stream` (uploading the tables when they changed, growing the scratch).
+int device_buses_send(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_out, void* stream);
+void device_sends_changed(PatchHandle& h);  // the host's list was replaced: the next call uploads the tables
+void device_sends_drop(PatchHandle& h);     // list, tables, scratch and the note
+std::string device_sends_note(const PatchHandle& h);  // " sends=4092[4156 runs]" once a call has run, else ""
 std::string device_bus_note(const PatchHandle& h);  // " buses=4096[fold]" when the last render filled bus mixes, else ""
 std::string device_waves_note(const PatchHandle& h);  // " waves=9[lds]" / " waves=9[global]" for a patch that renders with a wave assignment, else ""
 std::string device_sequences_note(const PatchHandle& h);  // " sequences=9[global]" for a patch that renders with a sequence assignment, else ""

@@ -229,6 +229,23 @@ public:
     {
         check(srack_buses_send(p_, n_samples, d_rows, row_channels, d_out, stream));
     }
+    // A Moog ladder per mix bus, behind the mixer: params f32 [n_buses][SRACK_BUS_FILTER_NPARAMS] = frequency, resonance, CV amount (any f32;
+    // nullptr: the module's defaults), port [n_buses] SRACK_VCF_OUT_* (nullptr: lowpass), enabled [n_buses] (nullptr: every bus).  Calling
+    // set_bus_filter again is the slider: parameters change, state stays.  Not part of the program: restarts nothing, survives an edit.
+    void set_bus_filter(const float* params = nullptr, const int* port = nullptr, const int* enabled = nullptr) { check(srack_buses_set_filter(p_, params, port, enabled)); }
+    uint32_t get_bus_filter(float* params = nullptr, int* port = nullptr, int* enabled = nullptr, uint32_t cap = 0) const
+    {
+        return (uint32_t)check(srack_buses_get_filter(p_, params, port, enabled, cap));
+    }
+    void reset_bus_filter() { check(srack_buses_reset_filter(p_)); }  // every state to zero; the parameters stay
+    // state f32 [n_buses][2][SRACK_BUS_FILTER_NSTATE] (host), behind a wait for the last filter call; a disabled bus reads as zeros
+    uint32_t bus_filter_state(float* state = nullptr, uint32_t cap = 0) { return (uint32_t)check(srack_buses_filter_state(p_, state, cap)); }
+    // d_rows f32 [n_buses][row_channels][n_samples] -> d_out of the same shape: d_rows itself (in place) or disjoint; d_cv f32
+    // [n_buses][n_samples] or null (the CV port unconnected).  Asynchronous on `stream`.  A sharded host reduces the bus mixes first.
+    void bus_filter(uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream = nullptr)
+    {
+        check(srack_buses_filter(p_, n_samples, d_rows, row_channels, d_cv, d_out, stream));
+    }
     // execute_batch plus d_bus_mix, f32 [n_buses][channels][n_samples] (written); d_frames, d_mix, d_stats may each be null
     void execute_batch_buses(uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags = 0, void* stream = nullptr)
     {

@@ -603,6 +603,60 @@ int srack_buses_send_plan(const srack_patch* p, int* n_terms, uint32_t bus_cap, 
 int srack_buses_send(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels,
                      float* d_out, void* stream);
 
+/* ---- the bus filters: a Moog ladder per mix bus, behind the mixer ---------------------------------------------------
+ * The one processor a console strip has besides level, sends and a room: a filter on the bus.  Channel c (0 or 1) of an enabled bus b
+ * is one MoogFilterModule (filter.rs:182-221 with InternalMoogFilterState::calc and clamp_buffers, filter.rs:58-92): its three
+ * sliders are the bus's params, its Audio input d_rows[b][c][t], its CV input d_cv[b][t]; it is ticked once per sample and writes the
+ * chosen port to d_out[b][c][t].  The two channels of a bus are two modules with the same sliders and the same CV, each with its own
+ * state.  A ladder on the sum is not the sum of ladders (the cubic and the clamps are non-linear), so this is not what a filter in
+ * every voice gives.  Every operation is IEEE f32, one rounding each, in the reference's order: no fma, the clamps the literal
+ * min-then-max (a NaN state clamps to +1.0, the reference's way); the coefficients are recomputed only when the clamped
+ * (frequency, res) differs from the pair they were computed for — the reference's quirk included that a fresh filter at frequency 0
+ * and resonance 0 never computes them.  State starts at all zeros (Default).  ANY f32 parameter is accepted, as the reference accepts
+ * any; a non-finite sample, CV or parameter affects that bus's rows and no other.
+ *
+ * params: f32 [n_buses][SRACK_BUS_FILTER_NPARAMS] = FREQ, RES, EXP_AMT (SRACK_VCF_FREQ .. SRACK_VCF_EXP_AMT); NULL = the module's defaults 0.2f, 0.5f, 0.5f
+ * port:   int [n_buses], SRACK_VCF_OUT_LOWPASS / _BANDPASS / _HIGHPASS: which of the module's three outputs the bus takes; NULL = lowpass
+ * enabled: int [n_buses], zero = no filter on that bus; NULL = every bus
+ * All three are host memory.  A port outside 0..2 is SRACK_ERR_INVALID and leaves the earlier setting in place.
+ * Lifecycle (the reverbs' rules): calling set_filter again is the slider — parameters change, state stays.  A bus enabled later
+ * starts from zeros; disabling a bus drops its state.  reset_filter zeroes every state and keeps the parameters.  get_filter copies up
+ * to cap buses (any pointer may be NULL) and returns n_buses, or 0 when no filters are set.  filter_state waits for the last filter
+ * call and copies up to cap buses of state — per bus and channel the ten values SRACK_VCF_ST_F .. SRACK_VCF_ST_RES, a disabled bus as
+ * zeros — and returns n_buses.  The state lives on the device between calls: the result cannot depend on how the samples are cut
+ * into calls.
+ * The filters belong to the handle, NOT to the patch's program, exactly as the reverbs: setting, changing or running them does not
+ * re-flatten, restarts nothing, changes no bit of frames, mix, statistics, bus mixes, sends, fx, master or voice state and not the
+ * kernel a patch renders with; they survive an edit that re-flattens the patch.  srack_voices_configure drops them; so does
+ * srack_voices_set_buses with another n_buses (the same n_buses keeps them).  Rack files carry nothing of this.
+ *
+ * The filter call:
+ *   d_rows : device, f32 [n_buses][row_channels][n_samples] — what srack_render_buses or srack_buses_send writes.
+ *            1 <= row_channels <= 8; channels 0 and 1 are filtered, channels beyond the second are neither read nor written.
+ *   d_cv   : device, f32 [n_buses][n_samples], one CV per bus, shared by its channels; NULL = the CV port is unconnected:
+ *            cv = 0.0f, the arithmetic freq + 0.0f * exp_amt still carried out, as the reference does.
+ *   d_out  : device, the shape of d_rows, written: d_rows itself (in place) or disjoint from it; a partial overlap is
+ *            SRACK_ERR_INVALID, and so is d_cv overlapping d_out.  A disabled bus's channels 0 and 1 are copied bit for bit (-0.0
+ *            stays -0.0); in place they are left alone.  A disabled bus costs no state.
+ *   Any 4-byte aligned address is accepted for all three.
+ *   stream : as for srack_render: asynchronous, and the library touches the stream only during the call.
+ * Errors, in this order: SRACK_ERR_INVALID for a null handle; SRACK_ERR_STATE before srack_voices_configure or before a mix table
+ * exists (all five calls); SRACK_ERR_STATE for srack_buses_filter, reset_filter and filter_state before set_filter; n_samples == 0 is
+ * SRACK_OK and touches nothing; SRACK_ERR_INVALID for a null d_rows or d_out, row_channels outside 1..8 or an overlap as above;
+ * SRACK_ERR_NOMEM if the state cannot be allocated, the earlier state intact.
+ * The kernel takes a lane per (enabled bus, channel) row — the ladder is serial in time — and one wave per workgroup; tiles of 64 rows
+ * x 64 samples pass through LDS so that memory is touched in whole lines (csrc/busvcf.hip.h).  Until every SIMD has a wave (32 768
+ * stereo buses) the call's time is set by one row's dependency chain, not by the number of buses.  srack_render_info says
+ * " busvcf=<enabled buses>[<waves> waves]" between " sends=" and " busfx=" once a filter call has run. */
+#define SRACK_BUS_FILTER_NPARAMS 3
+#define SRACK_BUS_FILTER_NSTATE  10   /* SRACK_VCF_ST_F .. SRACK_VCF_ST_RES, index = field - SRACK_VCF_ST_F */
+int srack_buses_set_filter(srack_patch* p, const float* params, const int* port, const int* enabled);
+int srack_buses_get_filter(const srack_patch* p, float* params, int* port, int* enabled, uint32_t cap);
+int srack_buses_reset_filter(srack_patch* p);
+int srack_buses_filter_state(srack_patch* p, float* state /* host, f32 [n_buses][2][SRACK_BUS_FILTER_NSTATE] */, uint32_t cap);
+int srack_buses_filter(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels,
+                       const float* d_cv, float* d_out, void* stream);
+
 /* Optional: do everything a later srack_render(p, <= n_samples, ..., flags) would do on first use — flatten the graph,
  * upload the programs and the voice table, size the scratch buffers (mix partials when want_mix, control tracks) — so
  * that the first render costs what every render costs.  Renders nothing and leaves the voice state untouched. */

@@ -80,6 +80,11 @@ mod ffi {
         pub fn srack_buses_get_sends(p: *const SrackPatch, src: *mut c_int, dst: *mut c_int, gain: *mut f32, cap: u32, through: *mut f32, through_cap: u32) -> c_int;
         pub fn srack_buses_send_plan(p: *const SrackPatch, n_terms: *mut c_int, bus_cap: u32, order: *mut c_int, order_cap: u32) -> c_int;
         pub fn srack_buses_send(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_out: *mut f32, stream: *mut c_void) -> c_int;
+        pub fn srack_buses_set_filter(p: *mut SrackPatch, params: *const f32, port: *const c_int, enabled: *const c_int) -> c_int;
+        pub fn srack_buses_get_filter(p: *const SrackPatch, params: *mut f32, port: *mut c_int, enabled: *mut c_int, cap: u32) -> c_int;
+        pub fn srack_buses_reset_filter(p: *mut SrackPatch) -> c_int;
+        pub fn srack_buses_filter_state(p: *mut SrackPatch, state: *mut f32, cap: u32) -> c_int;
+        pub fn srack_buses_filter(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_cv: *const f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
         pub fn srack_device_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
         pub fn srack_device_free(d_ptr: *mut c_void) -> c_int;
         pub fn srack_device_to_host(h_dst: *mut c_void, d_src: *const c_void, bytes: usize, stream: *mut c_void) -> c_int;
@@ -483,6 +488,47 @@ impl Patch {
     /// sends on the root.
     pub fn send(&mut self, n_samples: u32, rows: &DeviceBuffer, row_channels: u32, out: &DeviceBuffer) -> Result<(), Error> {
         check(unsafe { ffi::srack_buses_send(self.raw, n_samples, rows.as_f32() as *const f32, row_channels, out.as_f32(), std::ptr::null_mut()) }).map(|_| ())
+    }
+    /// A Moog ladder per mix bus, behind the mixer (`srack_buses_set_filter`): `params` is `[n_buses][3]` f32 — frequency, resonance, CV
+    /// amount, any f32; None: the module's defaults 0.2, 0.5, 0.5 —, `port` `[n_buses]` 0 lowpass, 1 bandpass, 2 highpass (None: lowpass),
+    /// `enabled` `[n_buses]` (None: every bus).  Calling it again is the slider: parameters change, state stays.  Not part of the
+    /// program: restarts nothing, and the filters carry on across an edit of the patch.
+    pub fn set_bus_filter(&mut self, params: Option<&[f32]>, port: Option<&[i32]>, enabled: Option<&[i32]>) -> Result<(), Error> {
+        let a = params.map_or(std::ptr::null(), |x| x.as_ptr());
+        let o = port.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        let e = enabled.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        check(unsafe { ffi::srack_buses_set_filter(self.raw, a, o, e) }).map(|_| ())
+    }
+    /// `(params [n_buses][3], port [n_buses], enabled [n_buses])` of the filters set; None when none are.
+    pub fn get_bus_filter(&self) -> Result<Option<(Vec<f32>, Vec<i32>, Vec<i32>)>, Error> {
+        let n = check(unsafe { ffi::srack_buses_get_filter(self.raw, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), 0) })? as usize;
+        if n == 0 {
+            return Ok(None);
+        }
+        let (mut a, mut o, mut e) = (vec![0f32; n * 3], vec![0 as c_int; n], vec![0 as c_int; n]);
+        check(unsafe { ffi::srack_buses_get_filter(self.raw, a.as_mut_ptr(), o.as_mut_ptr(), e.as_mut_ptr(), n as u32) })?;
+        Ok(Some((a, o, e)))
+    }
+    /// Every filter's state to zero; the parameters stay.
+    pub fn reset_bus_filter(&mut self) -> Result<(), Error> {
+        check(unsafe { ffi::srack_buses_reset_filter(self.raw) }).map(|_| ())
+    }
+    /// The filters' state behind the last call, `[n_buses][2][10]` f32: f, p, q, b0 .. b4 and the (frequency, resonance) the coefficients
+    /// were computed for, per bus and channel; a disabled bus reads as zeros.
+    pub fn bus_filter_state(&mut self) -> Result<Vec<f32>, Error> {
+        let n = check(unsafe { ffi::srack_buses_filter_state(self.raw, std::ptr::null_mut(), 0) })? as usize;
+        let mut st = vec![0f32; n * 2 * 10];
+        check(unsafe { ffi::srack_buses_filter_state(self.raw, st.as_mut_ptr(), n as u32) })?;
+        Ok(st)
+    }
+    /// The bus rows through their filters (`srack_buses_filter`): `rows` `[n_buses][row_channels][n_samples]` f32 in, `cv`
+    /// `[n_buses][n_samples]` f32 (None: the CV port unconnected), `out` of the shape of `rows` written — None: in place.  Channels 0 and 1
+    /// are filtered; a disabled bus passes bit for bit.  A sharded host reduces the per-rank bus mixes first and filters on the root:
+    /// a ladder on a sum is not the sum of ladders.
+    pub fn bus_filter(&mut self, n_samples: u32, rows: &DeviceBuffer, row_channels: u32, cv: Option<&DeviceBuffer>, out: Option<&DeviceBuffer>) -> Result<(), Error> {
+        let c = cv.map_or(std::ptr::null(), |b| b.as_f32() as *const f32);
+        let o = out.map_or(rows.as_f32(), |b| b.as_f32());
+        check(unsafe { ffi::srack_buses_filter(self.raw, n_samples, rows.as_f32() as *const f32, row_channels, c, o, std::ptr::null_mut()) }).map(|_| ())
     }
 }
 

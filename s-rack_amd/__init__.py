@@ -20,6 +20,8 @@ OK, ERR_INVALID, ERR_PORT, ERR_NO_OUTPUT, ERR_SELF_LOOP, ERR_STATE, ERR_UNSUPPOR
 MAX_BUSES, BUS_NONE = 65536, -1
 MASTER_RUN, MASTER_BLOCK = 64, 64  # buses per run, runs per block: the order srack_buses_master adds in
 MAX_SENDS = 1048576  # srack_buses_set_sends: the longest send list
+BUS_FILTER_NPARAMS, BUS_FILTER_NSTATE = 3, 10  # srack_buses_set_filter: FREQ, RES, EXP_AMT per bus; srack_buses_filter_state: VCF_ST_F .. VCF_ST_RES per bus and channel
+BUS_FILTER_DEFAULTS = (0.2, 0.5, 0.5)  # MoogFilterModule's three sliders: what set_bus_filter(None) gives every bus
 FREEVERB_DEFAULTS = (0.5, 0.0, 1.0, 0.5, 0.5, 0.0)  # FreeverbModule's six parameters in field order: what set_bus_reverbs(None) gives every bus
 WAVE_OWN = -1
 SEQ_OWN, MAX_SEQUENCES = -1, 65536
@@ -38,6 +40,7 @@ ABI_SYMBOLS = [
     "srack_buses_set_reverb", "srack_buses_get_reverb", "srack_buses_reset_reverb", "srack_buses_reverb_plan", "srack_buses_reverb",
     "srack_buses_set_master", "srack_buses_get_master", "srack_buses_master",
     "srack_buses_set_sends", "srack_buses_get_sends", "srack_buses_send_plan", "srack_buses_send",
+    "srack_buses_set_filter", "srack_buses_get_filter", "srack_buses_reset_filter", "srack_buses_filter_state", "srack_buses_filter",
     "srack_patch_set_wave_bank", "srack_patch_get_wave_bank", "srack_patch_get_wave_bank_samples", "srack_voices_set_waves", "srack_voices_get_waves",
     "srack_patch_set_sequence_bank", "srack_patch_get_sequence_bank", "srack_voices_set_sequences", "srack_voices_get_sequences",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
@@ -124,6 +127,12 @@ def _load():
         L.srack_buses_get_sends.argtypes = [vp, ip, ip, fp, u32, fp, u32]
         L.srack_buses_send_plan.argtypes = [vp, ip, u32, ip, u32]
         L.srack_buses_send.argtypes = [vp, u32, vp, u32, vp, vp]
+    if hasattr(L, "srack_buses_filter"):
+        L.srack_buses_set_filter.argtypes = [vp, fp, ip, ip]
+        L.srack_buses_get_filter.argtypes = [vp, fp, ip, ip, u32]
+        L.srack_buses_reset_filter.argtypes = [vp]
+        L.srack_buses_filter_state.argtypes = [vp, fp, u32]
+        L.srack_buses_filter.argtypes = [vp, u32, vp, u32, vp, vp, vp]
     if hasattr(L, "srack_voices_set_waves"):  # (tools/ alternate older builds of the library under this binding)
         L.srack_patch_set_wave_bank.argtypes = [vp, i32, fp, ip, fp, u32]
         L.srack_patch_get_wave_bank.argtypes = [vp, i32, ip, fp, u32]
@@ -685,6 +694,89 @@ class Patch:
             return out
         finally:
             for d in (d_in, d_out):
+                if d.value:
+                    lib.srack_device_free(d)
+
+    # ---- bus filters: a Moog ladder per mix bus, behind the mixer -----------------------------------------
+    def set_bus_filter(self, params=None, port=None, enabled=None):
+        """srack_buses_set_filter: params f32 [n_buses][3] = FREQ, RES, EXP_AMT, any f32 (None: the module's defaults), port int [n_buses]
+        VCF_OUT_* (None: lowpass), enabled [n_buses] (None: every bus).  Calling it again is the slider: parameters change, state stays.
+        Not part of the program: restarts nothing."""
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        a = po = e = None
+        if params is not None:
+            a = np.ascontiguousarray(params, dtype=np.float32)
+            assert a.shape == (n_buses, BUS_FILTER_NPARAMS), a.shape
+        if port is not None:
+            po = np.ascontiguousarray(port, dtype=np.intc)
+            assert po.shape == (n_buses,), po.shape
+        if enabled is not None:
+            e = np.ascontiguousarray(np.asarray(enabled) != 0, dtype=np.intc)
+            assert e.shape == (n_buses,), e.shape
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        _check(lib.srack_buses_set_filter(self.h, None if a is None else a.ctypes.data_as(fp), None if po is None else po.ctypes.data_as(ip),
+                                          None if e is None else e.ctypes.data_as(ip)))
+
+    def get_bus_filter(self):
+        """-> (n_buses, params f32 [n_buses][3], port int32 [n_buses], enabled int32 [n_buses]); (0, None, None, None) when no filters are set"""
+        n = _check(lib.srack_buses_get_filter(self.h, None, None, None, 0))
+        if n == 0:
+            return 0, None, None, None
+        a, po, e = np.empty((n, BUS_FILTER_NPARAMS), dtype=np.float32), np.empty(n, dtype=np.intc), np.empty(n, dtype=np.intc)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        _check(lib.srack_buses_get_filter(self.h, a.ctypes.data_as(fp), po.ctypes.data_as(ip), e.ctypes.data_as(ip), n))
+        return n, a, po, e
+
+    def reset_bus_filter(self):
+        """Every filter's state to zero; the parameters stay (srack_buses_reset_filter)."""
+        _check(lib.srack_buses_reset_filter(self.h))
+
+    def bus_filter_state(self):
+        """-> f32 [n_buses][2][BUS_FILTER_NSTATE]: VCF_ST_F .. VCF_ST_RES per bus and channel behind the last filter call, a disabled bus as
+        zeros (srack_buses_filter_state)"""
+        n = _check(lib.srack_buses_filter_state(self.h, None, 0))
+        st = np.zeros((n, 2, BUS_FILTER_NSTATE), dtype=np.float32)
+        _check(lib.srack_buses_filter_state(self.h, st.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return st
+
+    def bus_filter_raw(self, n_samples, d_rows, row_channels, d_cv, d_out, stream=None):
+        """Device pointers in; asynchronous on `stream` (srack_buses_filter): d_rows and d_out f32 [n_buses][row_channels][n] (d_out may be
+        d_rows), d_cv f32 [n_buses][n] or None."""
+        _check(lib.srack_buses_filter(self.h, n_samples, d_rows, row_channels, d_cv, d_out, stream))
+
+    def bus_filter(self, rows, cv=None, in_place=False):
+        """Convenience for tests: rows f32 [n_buses][row_channels][T] (and cv f32 [n_buses][T]) from the host through the filters -> f32 of
+        the shape of rows.  Out of place the output buffer starts as zeros, which is what channels beyond the second come back as; in
+        place they come back as they went in."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
+        c = None
+        if cv is not None:
+            c = np.ascontiguousarray(cv, dtype=np.float32)
+            assert c.shape == (n_buses, x.shape[2]), c.shape
+        out = np.zeros_like(x)
+        d_in, d_out, d_cv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        try:
+            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
+            if not in_place:
+                _check(lib.srack_device_alloc(C.byref(d_out), max(4, out.nbytes)))
+            if c is not None:
+                _check(lib.srack_device_alloc(C.byref(d_cv), max(4, c.nbytes)))
+            if x.nbytes:
+                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
+                if not in_place:
+                    _check(lib.srack_device_from_host(d_out, out.ctypes.data_as(C.c_void_p), out.nbytes, None))
+                if c is not None:
+                    _check(lib.srack_device_from_host(d_cv, c.ctypes.data_as(C.c_void_p), c.nbytes, None))
+            to = d_in if in_place else d_out
+            self.bus_filter_raw(x.shape[2], d_in, x.shape[1], d_cv if c is not None else None, to, None)
+            if out.nbytes:
+                _check(lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), to, out.nbytes, None))
+            _check(lib.srack_device_sync(None))
+            return out
+        finally:
+            for d in (d_in, d_out, d_cv):
                 if d.value:
                     lib.srack_device_free(d)
 

@@ -689,6 +689,7 @@ int srack_voices_configure(srack_patch* p, uint32_t n_voices)
         device_busfx_drop(p->h);  // the reverbs sat behind that table
         device_master_drop(p->h);  // ... and so did the master's gains
         device_sends_drop(p->h);   // ... and the sends between its buses
+        device_busvcf_drop(p->h);  // ... and the filters on them
         return SRACK_OK;
     });
 }
@@ -764,6 +765,7 @@ int srack_voices_set_buses(srack_patch* p, uint32_t n_buses, const int* bus, con
             device_busfx_drop(h);
             device_master_drop(h);
             device_sends_drop(h);
+            device_busvcf_drop(h);
         }
         h.n_buses = n_buses;
         h.bus = std::move(b);
@@ -1180,6 +1182,117 @@ int srack_buses_send(srack_patch* p, uint32_t n_samples, const float* d_rows, ui
     });
 }
 
+// ---- the bus filters -----------------------------------------------------------------------------------------------
+static const float kBusVcfDefaults[SRACK_BUS_FILTER_NPARAMS] = {0.2f, 0.5f, 0.5f};  // MoogFilterModule::new: freq, res, exp_amt
+
+static int busvcf_need_set(const srack_patch* p, const char* who)
+{
+    if (p->h.busvcf.set) return SRACK_OK;
+    set_error(std::string(who) + ": no filters set: call srack_buses_set_filter first");
+    return SRACK_ERR_STATE;
+}
+
+int srack_buses_set_filter(srack_patch* p, const float* params, const int* port, const int* enabled)
+{
+    return guarded([&]() -> int {
+        int rc = busfx_preamble(p, "buses_set_filter");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        BusVcf& F = h.busvcf;
+        const size_t n = h.n_buses;
+        for (size_t b = 0; port && b < n; b++)
+            if (port[b] < SRACK_VCF_OUT_LOWPASS || port[b] > SRACK_VCF_OUT_HIGHPASS) {
+                set_error("buses_set_filter: bus " + std::to_string(b) + " asks for port " + std::to_string(port[b]) + ": a filter has outputs 0 .. 2");
+                return SRACK_ERR_INVALID;
+            }
+        // (built aside: a failure leaves the earlier setting in place)
+        std::vector<float> par(n * SRACK_BUS_FILTER_NPARAMS);
+        std::vector<int32_t> po(n, SRACK_VCF_OUT_LOWPASS);
+        std::vector<uint8_t> en(n, 1);
+        for (size_t b = 0; b < n; b++) {
+            for (int f = 0; f < SRACK_BUS_FILTER_NPARAMS; f++) par[b * SRACK_BUS_FILTER_NPARAMS + f] = kBusVcfDefaults[f];
+            if (port) po[b] = port[b];
+            if (enabled) en[b] = enabled[b] != 0;
+        }
+        if (params) std::memcpy(par.data(), params, sizeof(float) * par.size());  // bit for bit
+        if ((rc = device_busvcf_enable(h, en)) != SRACK_OK) return rc;  // the state follows its buses: a bus enabled now starts from zeros, a disabled one drops its state
+        F.params = std::move(par);
+        F.port = std::move(po);
+        F.enabled = std::move(en);
+        F.set = true;
+        device_busvcf_changed(h);  // the sliders: the table is made again, the state stays
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_get_filter(const srack_patch* p, float* params, int* port, int* enabled, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_get_filter");
+        if (rc != SRACK_OK) return rc;
+        const PatchHandle& h = p->h;
+        const BusVcf& F = h.busvcf;
+        if (!F.set) return 0;
+        const size_t n = std::min<size_t>(cap, h.n_buses);
+        if (params && n) std::memcpy(params, F.params.data(), sizeof(float) * n * SRACK_BUS_FILTER_NPARAMS);
+        for (size_t b = 0; port && b < n; b++) port[b] = F.port[b];
+        for (size_t b = 0; enabled && b < n; b++) enabled[b] = F.enabled[b];
+        return (int)h.n_buses;
+    });
+}
+
+int srack_buses_reset_filter(srack_patch* p)
+{
+    return guarded([&]() -> int {
+        int rc = busfx_preamble(p, "buses_reset_filter");
+        if (rc != SRACK_OK) return rc;
+        if ((rc = busvcf_need_set(p, "buses_reset_filter")) != SRACK_OK) return rc;
+        device_busvcf_reset(p->h);
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_filter_state(srack_patch* p, float* state, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        int rc = busfx_preamble(p, "buses_filter_state");
+        if (rc != SRACK_OK) return rc;
+        if ((rc = busvcf_need_set(p, "buses_filter_state")) != SRACK_OK) return rc;
+        if (state && cap && (rc = device_busvcf_state(p->h, state, cap)) != SRACK_OK) return rc;
+        return (int)p->h.n_buses;
+    });
+}
+
+int srack_buses_filter(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream)
+{
+    return guarded([&]() -> int {
+        int rc = busfx_preamble(p, "buses_filter");
+        if (rc != SRACK_OK) return rc;
+        if ((rc = busvcf_need_set(p, "buses_filter")) != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        if (n_samples == 0) return SRACK_OK;
+        if (!d_rows || !d_out) {
+            set_error("buses_filter: d_rows and d_out must be given");
+            return SRACK_ERR_INVALID;
+        }
+        if (row_channels < 1 || row_channels > 8) {
+            set_error("buses_filter: row_channels must be 1 .. 8");
+            return SRACK_ERR_INVALID;
+        }
+        const uintptr_t in0 = (uintptr_t)d_rows, out0 = (uintptr_t)d_out, cv0 = (uintptr_t)d_cv;
+        const uint64_t bytes = 4ull * h.n_buses * row_channels * n_samples, cv_bytes = 4ull * h.n_buses * n_samples;
+        if (in0 != out0 && in0 < out0 + bytes && out0 < in0 + bytes) {
+            set_error("buses_filter: d_out overlaps d_rows in part: it must be d_rows itself or disjoint from it");
+            return SRACK_ERR_INVALID;
+        }
+        if (d_cv && cv0 < out0 + bytes && out0 < cv0 + cv_bytes) {
+            set_error("buses_filter: d_cv overlaps d_out");
+            return SRACK_ERR_INVALID;
+        }
+        return device_buses_filter(h, n_samples, d_rows, row_channels, d_cv, d_out, stream);
+    });
+}
+
 int srack_render_reserve(srack_patch* p, uint32_t n_samples, int want_mix, uint32_t flags)
 {
     return guarded([&]() -> int {
@@ -1221,6 +1334,7 @@ int srack_render_info(srack_patch* p, char* buf, size_t cap)
         // (the kernel's name stays LAST: hosts and tests read it with split("kernel="))
         s += device_bus_note(p->h);
         s += device_sends_note(p->h);
+        s += device_busvcf_note(p->h);
         s += device_busfx_note(p->h);
         s += device_master_note(p->h);
         s += device_waves_note(p->h);

@@ -89,4 +89,7 @@ void launch_master(const MasterArgs& a, hipStream_t st);
 // ---- the bus sends (sends.hip): every destination's run sums, into a.out or a.scratch, and the tree over the scratch rows into a.out ----
 void launch_sends(const SendArgs& a, hipStream_t st);
 
+// ---- the bus filters (busvcf.hip): a lane per row of a.tab, a wave per workgroup; the disabled buses' rows copied when a.out is not a.rows ----
+void launch_bus_filter(const BusVcfArgs& a, hipStream_t st);
+
 }  // namespace srack

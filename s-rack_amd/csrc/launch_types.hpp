@@ -64,4 +64,29 @@ struct SendArgs {
     uint32_t max_blocks;        // the most blocks (of SRACK_MASTER_BLOCK runs) any destination has: send_tree's waves
 };
 
+// One srack_buses_filter call (busvcf.hip.h).  The row table is made on the host (render.hip, device_buses_filter): the (enabled bus,
+// used channel) pairs compacted, 64 to a wave.
+struct BusVcfRow {
+    uint32_t row;        // the row of rows / out: bus * row_channels + channel
+    uint32_t bus;        // its row of cv
+    uint32_t slot;       // where its state lives: 2 * (the bus's place among the enabled ones) + channel
+    uint32_t port;       // SRACK_VCF_OUT_*
+    float freq, res, exp_amt;  // the bus's sliders, as given
+    uint32_t pad;
+};
+static_assert(sizeof(BusVcfRow) == 32, "the host uploads the table as it stands");
+constexpr int kBusVcfFields = 10;  // SRACK_BUS_FILTER_NSTATE: f, p, q, b0 .. b4, freq, res
+struct BusVcfArgs {
+    const float* rows;          // [n_buses][row_channels][n]
+    const float* cv;            // [n_buses][n] or null
+    float* out;                 // [n_buses][row_channels][n]; may be rows itself
+    float* state;               // [slots / 64][kBusVcfFields][64]: a wave's 64 slots side by side per field
+    const BusVcfRow* tab;       // [n_rows]
+    const uint32_t* copy_rows;  // [n_copy] rows of the disabled buses' used channels, copied when out is not rows
+    uint32_t n;                 // samples
+    uint32_t n_rows;
+    uint32_t n_copy;
+    uint32_t used;              // min(row_channels, 2): table entries that share a bus, and a row of cv
+};
+
 }  // namespace srack

@@ -242,6 +242,7 @@ PatchHandle::~PatchHandle()
     device_busfx_drop(*this);
     device_master_drop(*this);
     device_sends_drop(*this);
+    device_busvcf_drop(*this);
     device_release(dev);
     device_release(dev_old);
 }
@@ -1813,6 +1814,214 @@ int device_buses_send(PatchHandle& h, uint32_t n_samples, const float* d_rows, u
 std::string device_sends_note(const PatchHandle& h)
 {
     return h.sends.ran ? " sends=" + std::to_string(h.sends.last_sends) + "[" + std::to_string(h.sends.last_runs) + " runs]" : std::string();
+}
+
+// ---- the bus filters (busvcf.hip.h, launched through launch_bus_filter) -----------------------------------------------------------------
+// One lane per (enabled bus, used channel) row.  The row table — where each row lies, its state slot, its bus's sliders and port, and
+// the rows of the disabled buses, which an out-of-place call copies — is made again after a change of the setting or of row_channels,
+// behind a host-side wait for the last call's kernels, which may still be reading it.  The state is one allocation, zeroed on the
+// call's stream when it is fresh; after a change of the enabled set it comes up from the host in its new layout (BusVcf::pending).  A
+// tick session of unchanged filters is the launch and one event per call.
+static void busvcf_wait(BusVcf& F)
+{
+    if (F.ev_done) (void)hipEventSynchronize((hipEvent_t)F.ev_done);
+}
+
+static uint32_t busvcf_enabled(const std::vector<uint8_t>& en)
+{
+    uint32_t n = 0;
+    for (uint8_t e : en) n += e != 0;
+    return n;
+}
+
+// The state as it stands, f32 [slots][kBusVcfFields] in the order of F.enabled; `have` false: there is none, every filter is at zero.
+static int busvcf_fetch(BusVcf& F, std::vector<float>& out, bool& have)
+{
+    have = false;
+    if (!F.pending.empty()) {
+        out = F.pending;
+        have = true;
+        return SRACK_OK;
+    }
+    if (!F.d_state || F.fresh) return SRACK_OK;
+    const size_t slots = (size_t)2 * busvcf_enabled(F.enabled);
+    if (slots == 0) return SRACK_OK;
+    busvcf_wait(F);
+    std::vector<float> raw((slots + 63) / 64 * (kBusVcfFields * 64));
+    HIP_TRY(hipMemcpy(raw.data(), F.d_state, sizeof(float) * raw.size(), hipMemcpyDeviceToHost));
+    out.resize(slots * kBusVcfFields);
+    for (size_t sl = 0; sl < slots; sl++)
+        for (int f = 0; f < kBusVcfFields; f++) out[sl * kBusVcfFields + f] = raw[(sl >> 6) * (kBusVcfFields * 64) + (size_t)f * 64 + (sl & 63)];
+    have = true;
+    return SRACK_OK;
+}
+
+void device_busvcf_changed(PatchHandle& h) { h.busvcf.tab_dirty = true; }
+
+void device_busvcf_reset(PatchHandle& h)
+{
+    h.busvcf.pending.clear();
+    h.busvcf.fresh = true;  // zeroed on the next call's stream, before its kernel
+}
+
+int device_busvcf_enable(PatchHandle& h, const std::vector<uint8_t>& enabled)
+{
+    BusVcf& F = h.busvcf;
+    if (!F.set || enabled == F.enabled) return SRACK_OK;
+    std::vector<float> old;
+    bool have = false;
+    const int rc = busvcf_fetch(F, old, have);
+    if (rc != SRACK_OK) return rc;
+    if (!have) return SRACK_OK;  // all zeros, in any layout
+    std::vector<float> now((size_t)2 * busvcf_enabled(enabled) * kBusVcfFields, 0.0f);
+    size_t from = 0, to = 0;
+    for (size_t b = 0; b < enabled.size(); b++) {  // a bus that stays enabled keeps its state; one enabled now starts from zeros; a disabled one drops it
+        if (F.enabled[b] && enabled[b]) std::copy(old.begin() + from, old.begin() + from + 2 * kBusVcfFields, now.begin() + to);
+        if (F.enabled[b]) from += 2 * kBusVcfFields;
+        if (enabled[b]) to += 2 * kBusVcfFields;
+    }
+    F.pending = std::move(now);
+    if (F.pending.empty()) F.fresh = true;
+    return SRACK_OK;
+}
+
+int device_busvcf_state(PatchHandle& h, float* state, uint32_t cap)
+{
+    BusVcf& F = h.busvcf;
+    const size_t n = std::min<size_t>(cap, h.n_buses);
+    std::vector<float> cur;
+    bool have = false;
+    const int rc = busvcf_fetch(F, cur, have);
+    if (rc != SRACK_OK) return rc;
+    std::fill(state, state + n * 2 * kBusVcfFields, 0.0f);
+    size_t from = 0;
+    for (size_t b = 0; have && b < n; b++) {
+        if (!F.enabled[b]) continue;
+        std::copy(cur.begin() + from, cur.begin() + from + 2 * kBusVcfFields, state + b * 2 * kBusVcfFields);
+        from += 2 * kBusVcfFields;
+    }
+    return SRACK_OK;
+}
+
+void device_busvcf_drop(PatchHandle& h)
+{
+    BusVcf& F = h.busvcf;
+    busvcf_wait(F);
+    if (F.d_state) (void)hipFree(F.d_state);
+    if (F.d_tab) (void)hipFree(F.d_tab);
+    if (F.ev_done) (void)hipEventDestroy((hipEvent_t)F.ev_done);
+    F = BusVcf();
+}
+
+int device_buses_filter(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream)
+{
+    BusVcf& F = h.busvcf;
+    const hipStream_t st = (hipStream_t)stream;
+    const uint32_t n_buses = h.n_buses, used = row_channels < 2 ? row_channels : 2u;
+    const uint32_t n_enabled = busvcf_enabled(F.enabled);
+    if (!F.ev_done) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        F.ev_done = e;
+    } else {
+        HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)F.ev_done, 0));  // (calls may come on different streams: the state is one)
+    }
+    // the state: two slots per enabled bus, whole waves of 64
+    const size_t need = ((size_t)2 * n_enabled + 63) / 64 * 64;
+    const size_t state_bytes = sizeof(float) * kBusVcfFields * need;
+    if (F.state_slots < need) {  // (allocated first, swapped in on success: a failure leaves the earlier state, which then is `pending` or nothing)
+        void* p = nullptr;
+        if (hipMalloc(&p, state_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("buses_filter: out of device memory for the filters' state (" + std::to_string(state_bytes) + " bytes)");
+            return SRACK_ERR_NOMEM;
+        }
+        busvcf_wait(F);
+        if (F.d_state) (void)hipFree(F.d_state);
+        F.d_state = p;
+        F.state_slots = need;
+        if (F.pending.empty()) F.fresh = true;
+    }
+    if (!F.pending.empty()) {
+        std::vector<float> raw((size_t)kBusVcfFields * need, 0.0f);
+        const size_t slots = F.pending.size() / kBusVcfFields;
+        for (size_t sl = 0; sl < slots; sl++)
+            for (int f = 0; f < kBusVcfFields; f++) raw[(sl >> 6) * (kBusVcfFields * 64) + (size_t)f * 64 + (sl & 63)] = F.pending[sl * kBusVcfFields + f];
+        busvcf_wait(F);
+        HIP_TRY(hipMemcpy(F.d_state, raw.data(), sizeof(float) * raw.size(), hipMemcpyHostToDevice));
+        F.pending.clear();
+        F.fresh = false;
+    } else if (F.fresh && need) {  // InternalMoogFilterState::default(): all zeros
+        HIP_TRY(hipMemsetAsync(F.d_state, 0, state_bytes, st));
+        F.fresh = false;
+    }
+    if (F.tab_dirty || !F.d_tab || F.tab_row_channels != row_channels) {
+        std::vector<BusVcfRow> rows;
+        std::vector<uint32_t> copy;
+        uint32_t k = 0;
+        for (uint32_t b = 0; b < n_buses; b++) {
+            for (uint32_t c = 0; c < used; c++) {
+                if (!F.enabled[b]) {
+                    copy.push_back(b * row_channels + c);
+                    continue;
+                }
+                BusVcfRow r;
+                r.row = b * row_channels + c;
+                r.bus = b;
+                r.slot = 2 * k + c;
+                r.port = (uint32_t)F.port[b];
+                r.freq = F.params[(size_t)b * SRACK_BUS_FILTER_NPARAMS + SRACK_VCF_FREQ];
+                r.res = F.params[(size_t)b * SRACK_BUS_FILTER_NPARAMS + SRACK_VCF_RES];
+                r.exp_amt = F.params[(size_t)b * SRACK_BUS_FILTER_NPARAMS + SRACK_VCF_EXP_AMT];
+                r.pad = 0;
+                rows.push_back(r);
+            }
+            k += F.enabled[b] != 0;
+        }
+        const size_t at_copy = sizeof(BusVcfRow) * rows.size(), bytes = at_copy + sizeof(uint32_t) * copy.size() + 16;
+        if (F.tab_bytes < bytes) {
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("buses_filter: out of device memory for the table of the rows (" + std::to_string(bytes) + " bytes)");
+                return SRACK_ERR_NOMEM;
+            }
+            busvcf_wait(F);
+            if (F.d_tab) (void)hipFree(F.d_tab);
+            F.d_tab = p;
+            F.tab_bytes = bytes;
+        }
+        busvcf_wait(F);
+        if (!rows.empty()) HIP_TRY(hipMemcpy(F.d_tab, rows.data(), at_copy, hipMemcpyHostToDevice));
+        if (!copy.empty()) HIP_TRY(hipMemcpy((char*)F.d_tab + at_copy, copy.data(), sizeof(uint32_t) * copy.size(), hipMemcpyHostToDevice));
+        F.n_rows = (uint32_t)rows.size();
+        F.n_copy = (uint32_t)copy.size();
+        F.tab_row_channels = row_channels;
+        F.tab_dirty = false;
+    }
+    BusVcfArgs a;
+    a.rows = d_rows;
+    a.cv = d_cv;
+    a.out = d_out;
+    a.state = (float*)F.d_state;
+    a.tab = (const BusVcfRow*)F.d_tab;
+    a.copy_rows = (const uint32_t*)((const char*)F.d_tab + sizeof(BusVcfRow) * F.n_rows);
+    a.n = n_samples;
+    a.n_rows = F.n_rows;
+    a.n_copy = F.n_copy;
+    a.used = used;
+    launch_bus_filter(a, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord((hipEvent_t)F.ev_done, st));
+    F.last_enabled = n_enabled;
+    F.last_waves = (F.n_rows + 63) / 64;
+    F.ran = true;
+    return SRACK_OK;
+}
+
+std::string device_busvcf_note(const PatchHandle& h)
+{
+    return h.busvcf.ran ? " busvcf=" + std::to_string(h.busvcf.last_enabled) + "[" + std::to_string(h.busvcf.last_waves) + " waves]" : std::string();
 }
 
 const char* device_kernel_name(const PatchHandle& h) { return h.dev ? h.dev->kernel_name : ""; }

@@ -77,6 +77,31 @@ struct Sends {
     bool ran = false;
 };
 
+// The bus filters (srack_buses_set_filter / srack_buses_filter): a Moog ladder per enabled bus and channel, behind the mixer.  Like the
+// reverbs they hang off the handle: not the program's, not DeviceState's; dropped with the table.
+// The state of (enabled bus, channel) sits in slot 2 * (the bus's place among the enabled ones) + channel, on the device between calls
+// as f32 [slots / 64][SRACK_BUS_FILTER_NSTATE][64] (busvcf.hip.h).  Whenever the enabled set changes the slots move: the state comes to
+// the host, is laid out anew (`pending`) and goes up again before the next call's kernel.
+struct BusVcf {
+    bool set = false;
+    std::vector<float> params;      // [n_buses][SRACK_BUS_FILTER_NPARAMS], as the host gave them
+    std::vector<int32_t> port;      // [n_buses]
+    std::vector<uint8_t> enabled;   // [n_buses]
+    // device side (render.hip); nothing of it exists before the first srack_buses_filter
+    void* d_state = nullptr;        // f32 [state_slots / 64][10][64]
+    size_t state_slots = 0;         // a multiple of 64
+    bool fresh = true;              // the state is to be zeroed before the next call uses it (nothing ran yet, or reset_filter)
+    std::vector<float> pending;     // [slots][10] the state in the layout of `enabled`, to be uploaded before the next call; empty: none
+    void* d_tab = nullptr;          // BusVcfRow [n_rows], then u32 [n_copy]: the rows of the disabled buses
+    size_t tab_bytes = 0;
+    bool tab_dirty = true;          // parameters, ports or the enabled set changed ...
+    uint32_t tab_row_channels = 0;  // ... or a call comes with another row_channels than the table was made for
+    uint32_t n_rows = 0, n_copy = 0;
+    void* ev_done = nullptr;        // hipEvent_t behind every call's kernels: the next call, and whoever frees or rewrites, waits for it
+    uint32_t last_enabled = 0, last_waves = 0;  // srack_render_info, once a call has run
+    bool ran = false;
+};
+
 struct PatchHandle {
     Graph graph;
     uint32_t n_voices = 0;
@@ -114,6 +139,7 @@ struct PatchHandle {
     BusFx busfx;                    // the bus reverbs; dropped with the table (srack_voices_configure, another n_buses)
     Master master;                  // the master section; dropped with the table as well
     Sends sends;                    // the bus sends; dropped with the table as well
+    BusVcf busvcf;                  // the bus filters; dropped with the table as well
     bool timing_armed = false;      // srack_render_kernel_ms has been called: renders bracket the dominant kernel with HIP events
 
     ~PatchHandle();
@@ -148,6 +174,14 @@ int device_buses_send(PatchHandle& h, uint32_t n_samples, const float* d_rows, u
 void device_sends_changed(PatchHandle& h);  // the host's list was replaced: the next call uploads the tables
 void device_sends_drop(PatchHandle& h);     // list, tables, scratch and the note
 std::string device_sends_note(const PatchHandle& h);  // " sends=4092[4156 runs]" once a call has run, else ""
+// The bus filters: one call's work enqueued on `stream` (allocating, zeroing and uploading what is missing); state handling without a call.
+int device_buses_filter(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream);
+int device_busvcf_enable(PatchHandle& h, const std::vector<uint8_t>& enabled);  // the enabled set is about to become this: the state moves to its new slots
+int device_busvcf_state(PatchHandle& h, float* state, uint32_t cap);            // host, f32 [cap][2][10] as the C ABI hands it out, behind a wait for the last call
+void device_busvcf_changed(PatchHandle& h);  // parameters, ports or the enabled set were replaced: the next call makes the table anew
+void device_busvcf_reset(PatchHandle& h);    // every state to zero, before the next call uses it
+void device_busvcf_drop(PatchHandle& h);     // parameters, state, table and the note
+std::string device_busvcf_note(const PatchHandle& h);  // " busvcf=48[2 waves]" once a call has run, else ""
 std::string device_bus_note(const PatchHandle& h);  // " buses=4096[fold]" when the last render filled bus mixes, else ""
 std::string device_waves_note(const PatchHandle& h);  // " waves=9[lds]" / " waves=9[global]" for a patch that renders with a wave assignment, else ""
 std::string device_sequences_note(const PatchHandle& h);  // " sequences=9[global]" for a patch that renders with a sequence assignment, else ""

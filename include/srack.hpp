@@ -246,6 +246,23 @@ public:
     {
         check(srack_buses_filter(p_, n_samples, d_rows, row_channels, d_cv, d_out, stream));
     }
+    // An ADSR and a VCA per mix bus, behind the mixer: params f32 [n_buses][SRACK_BUS_VCA_NPARAMS] = attack, decay, sustain, release (any f32;
+    // nullptr: the module's defaults), mode [n_buses] SRACK_BUS_VCA_* (nullptr: every bus GATE), negative [n_buses] (nullptr: false).  Calling
+    // set_bus_vca again is the slider: sliders change, state stays; a bus that becomes GATE starts fresh.  Not part of the program.
+    void set_bus_vca(const float* params = nullptr, const int* mode = nullptr, const int* negative = nullptr) { check(srack_buses_set_vca(p_, params, mode, negative)); }
+    uint32_t get_bus_vca(float* params = nullptr, int* mode = nullptr, int* negative = nullptr, uint32_t cap = 0) const
+    {
+        return (uint32_t)check(srack_buses_get_vca(p_, params, mode, negative, cap));
+    }
+    void reset_bus_vca() { check(srack_buses_reset_vca(p_)); }  // every state fresh; the setting stays
+    // state f32 [n_buses][SRACK_BUS_VCA_NSTATE] (host), behind a wait for the last call; a bus that is not GATE reads as the fresh state
+    uint32_t bus_vca_state(float* state = nullptr, uint32_t cap = 0) { return (uint32_t)check(srack_buses_vca_state(p_, state, cap)); }
+    // d_rows f32 [n_buses][row_channels][n_samples] -> d_out of the same shape: d_rows itself (in place) or disjoint; d_ctl f32
+    // [n_buses][n_samples], the gate or CV per bus, or null (unconnected); d_env of d_ctl's shape, written, or null.  Asynchronous on `stream`.
+    void bus_vca(uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_ctl, float* d_out, float* d_env = nullptr, void* stream = nullptr)
+    {
+        check(srack_buses_vca(p_, n_samples, d_rows, row_channels, d_ctl, d_out, d_env, stream));
+    }
     // execute_batch plus d_bus_mix, f32 [n_buses][channels][n_samples] (written); d_frames, d_mix, d_stats may each be null
     void execute_batch_buses(uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags = 0, void* stream = nullptr)
     {

@@ -657,6 +657,66 @@ int srack_buses_filter_state(srack_patch* p, float* state /* host, f32 [n_buses]
 int srack_buses_filter(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels,
                        const float* d_cv, float* d_out, void* stream);
 
+/* ---- the bus VCAs: an ADSR and a VCA per mix bus, behind the mixer, driven by a gate or CV row ------------------------------------
+ * What moves a strip's level in time.  Every bus has one control row d_ctl[b][t] and a mode:
+ *   SRACK_BUS_VCA_GATE  the row is the Gate input of one ADSRModule (adsr.rs:134-217) with the sliders params[b]; the envelope is the
+ *                       CV of one VCAModule (vca.rs:117-148) per channel c in {0, 1}: Audio input d_rows[b][c][t], flag negative[b],
+ *                       output d_out[b][c][t] — the pair every patch of the reference ends in (patch P1 wires exactly that).
+ *   SRACK_BUS_VCA_CV    no ADSR and no state: the row is the VCAs' CV itself (automation).
+ *   SRACK_BUS_VCA_OFF   the bus passes.
+ * Every operation is IEEE f32, one rounding each, in the reference's order, no fma: the envelope is adsr.rs's literal sequence
+ * (a_sec = 0 gives an increment of +inf: Attack lasts one sample; a NaN gate is neither high nor low), the VCA is
+ * negative || cv > 0 ? audio * cv : +0.0f.  The ADSR's sample rate is the f32 a fresh ADSR module of this patch carries
+ * (SRACK_ADSR_SAMPLE_RATE).  ANY f32 slider is accepted; a non-finite sample, control value or slider affects that bus's rows and no
+ * other.  Fresh state is NOT all zeros: phase 0, mode SRACK_ADSR_MODE_NONE, r_val 0, from_a_val 0, TransitionDetector.last TRUE.
+ *
+ * params:   f32 [n_buses][SRACK_BUS_VCA_NPARAMS] = A_SEC, D_SEC, S_VAL, R_SEC (SRACK_ADSR_A_SEC .. SRACK_ADSR_R_SEC); NULL = the module's
+ *           defaults 0, 0.5, 0.25, 0.5
+ * mode:     int [n_buses], SRACK_BUS_VCA_*; NULL = every bus GATE
+ * negative: int [n_buses], non-zero = the VCAs' `negative` flag; NULL = false
+ * All three are host memory.  A mode outside 0..2 is SRACK_ERR_INVALID and leaves the earlier setting in place.
+ * Lifecycle (the filters' rules): calling set_vca again is the slider — sliders, flags change, state stays.  A bus that becomes GATE
+ * starts fresh; a bus that leaves GATE drops its state.  reset_vca makes every state fresh and keeps the setting.  get_vca copies up to
+ * cap buses (any pointer may be NULL) and returns n_buses, or 0 when no VCAs are set.  vca_state waits for the last call and copies
+ * up to cap buses of state — per bus the six values SRACK_ADSR_PHASE .. SRACK_ADSR_GATE_LAST as f32: mode and last as their small
+ * integers, the sample-rate slot the f32 rate; a bus that is not GATE reads as the fresh state (0, 4, 0, 0, rate, 1) — and returns
+ * n_buses.  The state lives on the device between calls: the result cannot depend on how the samples are cut into calls.
+ * The VCAs belong to the handle, NOT to the patch's program, exactly as the filters: setting, changing or running them does not
+ * re-flatten, restarts nothing, changes no bit of frames, mix, statistics, bus mixes, sends, filters, fx, master or voice state;
+ * they survive an edit that re-flattens the patch.  srack_voices_configure drops them; so does srack_voices_set_buses with another
+ * n_buses (the same n_buses keeps them).  Rack files carry nothing of this.
+ *
+ * The call:
+ *   d_rows : device, f32 [n_buses][row_channels][n_samples] — what srack_render_buses, srack_buses_send or srack_buses_filter writes.
+ *            1 <= row_channels <= 8; channels 0 and 1 are processed, channels beyond the second are neither read nor written.
+ *   d_ctl  : device, f32 [n_buses][n_samples], or NULL = the control port is unconnected: a GATE bus runs its ADSR with no gate
+ *            (gate_in_buf is None: Sustain falls to Release, mode None stays None), a CV bus writes +0.0f (output.fill(0.0)).
+ *   d_out  : device, the shape of d_rows, written: d_rows itself (in place) or disjoint from it.  An OFF bus's channels 0 and 1 are
+ *            copied as 32-bit words (-0.0 stays -0.0, a NaN keeps its payload); in place they are left alone.
+ *   d_env  : device, f32 [n_buses][n_samples], written, or NULL: a GATE bus's envelope, a CV bus's control row word for word (+0.0
+ *            when d_ctl is NULL), +0.0 for an OFF bus — e.g. to sweep the bus filters with the same gate through
+ *            srack_buses_filter's d_cv.  What d_out gets does not depend on whether d_env is given.
+ *   d_env and d_ctl must not overlap d_out or each other, d_env must not overlap d_rows; those, and a partial overlap of d_rows and
+ *   d_out, are SRACK_ERR_INVALID.  Any 4-byte aligned address is accepted for all four.
+ *   stream : as for srack_render: asynchronous, and the library touches the stream only during the call.
+ * Errors, in this order: SRACK_ERR_INVALID for a null handle; SRACK_ERR_STATE before srack_voices_configure or before a mix table
+ * exists (all five calls); SRACK_ERR_STATE for srack_buses_vca, reset_vca and vca_state before set_vca; n_samples == 0 is SRACK_OK
+ * and touches nothing; SRACK_ERR_INVALID for a null d_rows or d_out, row_channels outside 1..8 or an overlap as above;
+ * SRACK_ERR_NOMEM if state and table cannot be allocated.
+ * The kernel takes a workgroup of eight waves per 64 buses: the envelopes — serial in time — a lane per bus on the first wave, a tile
+ * of 64 buses x 64 control samples turned through LDS; the VCAs elementwise on all eight waves, lanes on time (csrc/busvca.hip.h).  A
+ * workgroup without a GATE bus is a plain streaming pass.  srack_render_info says " busvca=<buses not OFF>[<GATE buses> gated]"
+ * between " busvcf=" and " busfx=" once a call has run. */
+#define SRACK_BUS_VCA_NPARAMS 4   /* SRACK_ADSR_A_SEC .. SRACK_ADSR_R_SEC */
+#define SRACK_BUS_VCA_NSTATE  6   /* SRACK_ADSR_PHASE .. SRACK_ADSR_GATE_LAST, index = field - SRACK_ADSR_PHASE */
+enum { SRACK_BUS_VCA_OFF = 0, SRACK_BUS_VCA_CV = 1, SRACK_BUS_VCA_GATE = 2 };
+int srack_buses_set_vca(srack_patch* p, const float* params, const int* mode, const int* negative);
+int srack_buses_get_vca(const srack_patch* p, float* params, int* mode, int* negative, uint32_t cap);
+int srack_buses_reset_vca(srack_patch* p);
+int srack_buses_vca_state(srack_patch* p, float* state /* host, f32 [n_buses][SRACK_BUS_VCA_NSTATE] */, uint32_t cap);
+int srack_buses_vca(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels,
+                    const float* d_ctl, float* d_out, float* d_env, void* stream);
+
 /* Optional: do everything a later srack_render(p, <= n_samples, ..., flags) would do on first use — flatten the graph,
  * upload the programs and the voice table, size the scratch buffers (mix partials when want_mix, control tracks) — so
  * that the first render costs what every render costs.  Renders nothing and leaves the voice state untouched. */

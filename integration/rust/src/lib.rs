@@ -85,6 +85,11 @@ mod ffi {
         pub fn srack_buses_reset_filter(p: *mut SrackPatch) -> c_int;
         pub fn srack_buses_filter_state(p: *mut SrackPatch, state: *mut f32, cap: u32) -> c_int;
         pub fn srack_buses_filter(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_cv: *const f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
+        pub fn srack_buses_set_vca(p: *mut SrackPatch, params: *const f32, mode: *const c_int, negative: *const c_int) -> c_int;
+        pub fn srack_buses_get_vca(p: *const SrackPatch, params: *mut f32, mode: *mut c_int, negative: *mut c_int, cap: u32) -> c_int;
+        pub fn srack_buses_reset_vca(p: *mut SrackPatch) -> c_int;
+        pub fn srack_buses_vca_state(p: *mut SrackPatch, state: *mut f32, cap: u32) -> c_int;
+        pub fn srack_buses_vca(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_ctl: *const f32, d_out: *mut f32, d_env: *mut f32, stream: *mut c_void) -> c_int;
         pub fn srack_device_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
         pub fn srack_device_free(d_ptr: *mut c_void) -> c_int;
         pub fn srack_device_to_host(h_dst: *mut c_void, d_src: *const c_void, bytes: usize, stream: *mut c_void) -> c_int;
@@ -529,6 +534,49 @@ impl Patch {
         let c = cv.map_or(std::ptr::null(), |b| b.as_f32() as *const f32);
         let o = out.map_or(rows.as_f32(), |b| b.as_f32());
         check(unsafe { ffi::srack_buses_filter(self.raw, n_samples, rows.as_f32() as *const f32, row_channels, c, o, std::ptr::null_mut()) }).map(|_| ())
+    }
+    /// An ADSR and a VCA per mix bus, behind the mixer (`srack_buses_set_vca`): `params` is `[n_buses][4]` f32 — attack, decay (seconds),
+    /// sustain level, release (seconds), any f32; None: the module's defaults 0, 0.5, 0.25, 0.5 —, `mode` `[n_buses]` 0 off, 1 the control
+    /// row is the VCA's CV, 2 it is the envelope's gate (None: every bus gated), `negative` `[n_buses]` the VCAs' flag (None: false).
+    /// Calling it again is the slider: sliders change, state stays; a bus that becomes gated starts fresh.  Not part of the program:
+    /// restarts nothing, and the envelopes carry on across an edit of the patch.
+    pub fn set_bus_vca(&mut self, params: Option<&[f32]>, mode: Option<&[i32]>, negative: Option<&[i32]>) -> Result<(), Error> {
+        let a = params.map_or(std::ptr::null(), |x| x.as_ptr());
+        let m = mode.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        let g = negative.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        check(unsafe { ffi::srack_buses_set_vca(self.raw, a, m, g) }).map(|_| ())
+    }
+    /// `(params [n_buses][4], mode [n_buses], negative [n_buses])` of the VCAs set; None when none are.
+    pub fn get_bus_vca(&self) -> Result<Option<(Vec<f32>, Vec<i32>, Vec<i32>)>, Error> {
+        let n = check(unsafe { ffi::srack_buses_get_vca(self.raw, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), 0) })? as usize;
+        if n == 0 {
+            return Ok(None);
+        }
+        let (mut a, mut m, mut g) = (vec![0f32; n * 4], vec![0 as c_int; n], vec![0 as c_int; n]);
+        check(unsafe { ffi::srack_buses_get_vca(self.raw, a.as_mut_ptr(), m.as_mut_ptr(), g.as_mut_ptr(), n as u32) })?;
+        Ok(Some((a, m, g)))
+    }
+    /// Every envelope's state fresh (mode None, the gate detector armed as at `new()`); the setting stays.
+    pub fn reset_bus_vca(&mut self) -> Result<(), Error> {
+        check(unsafe { ffi::srack_buses_reset_vca(self.raw) }).map(|_| ())
+    }
+    /// The envelopes' state behind the last call, `[n_buses][6]` f32: phase, mode, r_val, from_a_val, the f32 sample rate, gate_last; a
+    /// bus that is not gated reads as the fresh state (0, 4, 0, 0, rate, 1).
+    pub fn bus_vca_state(&mut self) -> Result<Vec<f32>, Error> {
+        let n = check(unsafe { ffi::srack_buses_vca_state(self.raw, std::ptr::null_mut(), 0) })? as usize;
+        let mut st = vec![0f32; n * 6];
+        check(unsafe { ffi::srack_buses_vca_state(self.raw, st.as_mut_ptr(), n as u32) })?;
+        Ok(st)
+    }
+    /// The bus rows through their VCAs (`srack_buses_vca`): `rows` `[n_buses][row_channels][n_samples]` f32 in, `ctl`
+    /// `[n_buses][n_samples]` f32 the gate or CV per bus (None: the control port unconnected), `out` of the shape of `rows` written — None:
+    /// in place —, `env` `[n_buses][n_samples]` written when given: the envelopes, e.g. as the `cv` of `bus_filter`.  Channels 0 and 1 are
+    /// processed; a bus that is off passes word for word.
+    pub fn bus_vca(&mut self, n_samples: u32, rows: &DeviceBuffer, row_channels: u32, ctl: Option<&DeviceBuffer>, out: Option<&DeviceBuffer>, env: Option<&DeviceBuffer>) -> Result<(), Error> {
+        let c = ctl.map_or(std::ptr::null(), |b| b.as_f32() as *const f32);
+        let o = out.map_or(rows.as_f32(), |b| b.as_f32());
+        let e = env.map_or(std::ptr::null_mut(), |b| b.as_f32());
+        check(unsafe { ffi::srack_buses_vca(self.raw, n_samples, rows.as_f32() as *const f32, row_channels, c, o, e, std::ptr::null_mut()) }).map(|_| ())
     }
 }
 

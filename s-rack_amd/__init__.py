@@ -22,6 +22,10 @@ MASTER_RUN, MASTER_BLOCK = 64, 64  # buses per run, runs per block: the order sr
 MAX_SENDS = 1048576  # srack_buses_set_sends: the longest send list
 BUS_FILTER_NPARAMS, BUS_FILTER_NSTATE = 3, 10  # srack_buses_set_filter: FREQ, RES, EXP_AMT per bus; srack_buses_filter_state: VCF_ST_F .. VCF_ST_RES per bus and channel
 BUS_FILTER_DEFAULTS = (0.2, 0.5, 0.5)  # MoogFilterModule's three sliders: what set_bus_filter(None) gives every bus
+BUS_VCA_NPARAMS, BUS_VCA_NSTATE = 4, 6  # srack_buses_set_vca: ADSR_A_SEC .. ADSR_R_SEC per bus; srack_buses_vca_state: ADSR_PHASE .. ADSR_GATE_LAST per bus
+BUS_VCA_OFF, BUS_VCA_CV, BUS_VCA_GATE = 0, 1, 2  # a bus's mode: it passes; its control row is the VCAs' CV; it is the gate of the bus's ADSR
+BUS_VCA_DEFAULTS = (0.0, 0.5, 0.25, 0.5)  # ADSRModule's four sliders: what set_bus_vca(None) gives every bus
+ADSR_MODE_ATTACK, ADSR_MODE_DECAY, ADSR_MODE_SUSTAIN, ADSR_MODE_RELEASE, ADSR_MODE_NONE = 0, 1, 2, 3, 4  # the values of ADSR_MODE
 FREEVERB_DEFAULTS = (0.5, 0.0, 1.0, 0.5, 0.5, 0.0)  # FreeverbModule's six parameters in field order: what set_bus_reverbs(None) gives every bus
 WAVE_OWN = -1
 SEQ_OWN, MAX_SEQUENCES = -1, 65536
@@ -41,6 +45,7 @@ ABI_SYMBOLS = [
     "srack_buses_set_master", "srack_buses_get_master", "srack_buses_master",
     "srack_buses_set_sends", "srack_buses_get_sends", "srack_buses_send_plan", "srack_buses_send",
     "srack_buses_set_filter", "srack_buses_get_filter", "srack_buses_reset_filter", "srack_buses_filter_state", "srack_buses_filter",
+    "srack_buses_set_vca", "srack_buses_get_vca", "srack_buses_reset_vca", "srack_buses_vca_state", "srack_buses_vca",
     "srack_patch_set_wave_bank", "srack_patch_get_wave_bank", "srack_patch_get_wave_bank_samples", "srack_voices_set_waves", "srack_voices_get_waves",
     "srack_patch_set_sequence_bank", "srack_patch_get_sequence_bank", "srack_voices_set_sequences", "srack_voices_get_sequences",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
@@ -133,6 +138,12 @@ def _load():
         L.srack_buses_reset_filter.argtypes = [vp]
         L.srack_buses_filter_state.argtypes = [vp, fp, u32]
         L.srack_buses_filter.argtypes = [vp, u32, vp, u32, vp, vp, vp]
+    if hasattr(L, "srack_buses_vca"):
+        L.srack_buses_set_vca.argtypes = [vp, fp, ip, ip]
+        L.srack_buses_get_vca.argtypes = [vp, fp, ip, ip, u32]
+        L.srack_buses_reset_vca.argtypes = [vp]
+        L.srack_buses_vca_state.argtypes = [vp, fp, u32]
+        L.srack_buses_vca.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
     if hasattr(L, "srack_voices_set_waves"):  # (tools/ alternate older builds of the library under this binding)
         L.srack_patch_set_wave_bank.argtypes = [vp, i32, fp, ip, fp, u32]
         L.srack_patch_get_wave_bank.argtypes = [vp, i32, ip, fp, u32]
@@ -777,6 +788,96 @@ class Patch:
             return out
         finally:
             for d in (d_in, d_out, d_cv):
+                if d.value:
+                    lib.srack_device_free(d)
+
+    # ---- bus VCAs: an ADSR and a VCA per mix bus, behind the mixer ------------------------------------------
+    def set_bus_vca(self, params=None, mode=None, negative=None):
+        """srack_buses_set_vca: params f32 [n_buses][4] = A_SEC, D_SEC, S_VAL, R_SEC, any f32 (None: the module's defaults), mode int
+        [n_buses] BUS_VCA_OFF / _CV / _GATE (None: every bus GATE), negative [n_buses] (None: false).  Calling it again is the slider:
+        sliders change, state stays; a bus that becomes GATE starts fresh.  Not part of the program: restarts nothing."""
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        a = mo = ng = None
+        if params is not None:
+            a = np.ascontiguousarray(params, dtype=np.float32)
+            assert a.shape == (n_buses, BUS_VCA_NPARAMS), a.shape
+        if mode is not None:
+            mo = np.ascontiguousarray(mode, dtype=np.intc)
+            assert mo.shape == (n_buses,), mo.shape
+        if negative is not None:
+            ng = np.ascontiguousarray(np.asarray(negative) != 0, dtype=np.intc)
+            assert ng.shape == (n_buses,), ng.shape
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        _check(lib.srack_buses_set_vca(self.h, None if a is None else a.ctypes.data_as(fp), None if mo is None else mo.ctypes.data_as(ip),
+                                       None if ng is None else ng.ctypes.data_as(ip)))
+
+    def get_bus_vca(self):
+        """-> (n_buses, params f32 [n_buses][4], mode int32 [n_buses], negative int32 [n_buses]); (0, None, None, None) when no VCAs are set"""
+        n = _check(lib.srack_buses_get_vca(self.h, None, None, None, 0))
+        if n == 0:
+            return 0, None, None, None
+        a, mo, ng = np.empty((n, BUS_VCA_NPARAMS), dtype=np.float32), np.empty(n, dtype=np.intc), np.empty(n, dtype=np.intc)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        _check(lib.srack_buses_get_vca(self.h, a.ctypes.data_as(fp), mo.ctypes.data_as(ip), ng.ctypes.data_as(ip), n))
+        return n, a, mo, ng
+
+    def reset_bus_vca(self):
+        """Every envelope's state fresh; the setting stays (srack_buses_reset_vca)."""
+        _check(lib.srack_buses_reset_vca(self.h))
+
+    def bus_vca_state(self):
+        """-> f32 [n_buses][BUS_VCA_NSTATE]: ADSR_PHASE .. ADSR_GATE_LAST per bus behind the last call, a bus that is not GATE as the fresh
+        state (0, 4, 0, 0, rate, 1) (srack_buses_vca_state)"""
+        n = _check(lib.srack_buses_vca_state(self.h, None, 0))
+        st = np.zeros((n, BUS_VCA_NSTATE), dtype=np.float32)
+        _check(lib.srack_buses_vca_state(self.h, st.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return st
+
+    def bus_vca_raw(self, n_samples, d_rows, row_channels, d_ctl, d_out, d_env=None, stream=None):
+        """Device pointers in; asynchronous on `stream` (srack_buses_vca): d_rows and d_out f32 [n_buses][row_channels][n] (d_out may be
+        d_rows), d_ctl and d_env f32 [n_buses][n] or None."""
+        _check(lib.srack_buses_vca(self.h, n_samples, d_rows, row_channels, d_ctl, d_out, d_env, stream))
+
+    def bus_vca(self, rows, ctl=None, in_place=False, want_env=False):
+        """Convenience for tests: rows f32 [n_buses][row_channels][T] (and ctl f32 [n_buses][T]) from the host through the VCAs -> f32 of
+        the shape of rows, or (that, env f32 [n_buses][T]) when want_env.  Out of place the output buffer starts as zeros, which is what
+        channels beyond the second come back as; in place they come back as they went in."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
+        c = None
+        if ctl is not None:
+            c = np.ascontiguousarray(ctl, dtype=np.float32)
+            assert c.shape == (n_buses, x.shape[2]), c.shape
+        out = np.zeros_like(x)
+        env = np.zeros((n_buses, x.shape[2]), dtype=np.float32)
+        d_in, d_out, d_ctl, d_env = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        try:
+            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
+            if not in_place:
+                _check(lib.srack_device_alloc(C.byref(d_out), max(4, out.nbytes)))
+            if c is not None:
+                _check(lib.srack_device_alloc(C.byref(d_ctl), max(4, c.nbytes)))
+            if want_env:
+                _check(lib.srack_device_alloc(C.byref(d_env), max(4, env.nbytes)))
+            if x.nbytes:
+                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
+                if not in_place:
+                    _check(lib.srack_device_from_host(d_out, out.ctypes.data_as(C.c_void_p), out.nbytes, None))
+                if c is not None:
+                    _check(lib.srack_device_from_host(d_ctl, c.ctypes.data_as(C.c_void_p), c.nbytes, None))
+                if want_env:
+                    _check(lib.srack_device_from_host(d_env, env.ctypes.data_as(C.c_void_p), env.nbytes, None))
+            to = d_in if in_place else d_out
+            self.bus_vca_raw(x.shape[2], d_in, x.shape[1], d_ctl if c is not None else None, to, d_env if want_env else None, None)
+            if out.nbytes:
+                _check(lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), to, out.nbytes, None))
+                if want_env:
+                    _check(lib.srack_device_to_host(env.ctypes.data_as(C.c_void_p), d_env, env.nbytes, None))
+            _check(lib.srack_device_sync(None))
+            return (out, env) if want_env else out
+        finally:
+            for d in (d_in, d_out, d_ctl, d_env):
                 if d.value:
                     lib.srack_device_free(d)
 

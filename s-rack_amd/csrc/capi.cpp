@@ -690,6 +690,7 @@ int srack_voices_configure(srack_patch* p, uint32_t n_voices)
         device_master_drop(p->h);  // ... and so did the master's gains
         device_sends_drop(p->h);   // ... and the sends between its buses
         device_busvcf_drop(p->h);  // ... and the filters on them
+        device_busvca_drop(p->h);  // ... and their VCAs
         return SRACK_OK;
     });
 }
@@ -766,6 +767,7 @@ int srack_voices_set_buses(srack_patch* p, uint32_t n_buses, const int* bus, con
             device_master_drop(h);
             device_sends_drop(h);
             device_busvcf_drop(h);
+            device_busvca_drop(h);
         }
         h.n_buses = n_buses;
         h.bus = std::move(b);
@@ -1293,6 +1295,128 @@ int srack_buses_filter(srack_patch* p, uint32_t n_samples, const float* d_rows, 
     });
 }
 
+// ---- the bus VCAs ----------------------------------------------------------------------------------------------------
+static const float kBusVcaDefaults[SRACK_BUS_VCA_NPARAMS] = {0.0f, 0.5f, 0.25f, 0.5f};  // ADSRModule::new: a_sec, d_sec, s_val, r_sec
+
+static int busvca_need_set(const srack_patch* p, const char* who)
+{
+    if (p->h.busvca.set) return SRACK_OK;
+    set_error(std::string(who) + ": no VCAs set: call srack_buses_set_vca first");
+    return SRACK_ERR_STATE;
+}
+
+int srack_buses_set_vca(srack_patch* p, const float* params, const int* mode, const int* negative)
+{
+    return guarded([&]() -> int {
+        int rc = busfx_preamble(p, "buses_set_vca");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        BusVca& F = h.busvca;
+        const size_t n = h.n_buses;
+        for (size_t b = 0; mode && b < n; b++)
+            if (mode[b] < SRACK_BUS_VCA_OFF || mode[b] > SRACK_BUS_VCA_GATE) {
+                set_error("buses_set_vca: bus " + std::to_string(b) + " asks for mode " + std::to_string(mode[b]) + ": a bus VCA is off (0), CV (1) or gate (2)");
+                return SRACK_ERR_INVALID;
+            }
+        // (built aside: a failure leaves the earlier setting in place)
+        std::vector<float> par(n * SRACK_BUS_VCA_NPARAMS);
+        std::vector<int32_t> mo(n, SRACK_BUS_VCA_GATE);
+        std::vector<uint8_t> neg(n, 0);
+        for (size_t b = 0; b < n; b++) {
+            for (int f = 0; f < SRACK_BUS_VCA_NPARAMS; f++) par[b * SRACK_BUS_VCA_NPARAMS + f] = kBusVcaDefaults[f];
+            if (mode) mo[b] = mode[b];
+            if (negative) neg[b] = negative[b] != 0;
+        }
+        if (params) std::memcpy(par.data(), params, sizeof(float) * par.size());  // bit for bit
+        if ((rc = device_busvca_modes(h, mo)) != SRACK_OK) return rc;  // a bus that becomes GATE starts fresh, one that leaves GATE drops its state
+        F.params = std::move(par);
+        F.mode = std::move(mo);
+        F.negative = std::move(neg);
+        F.rate = h.graph.adsr_sample_rate();
+        F.set = true;
+        device_busvca_changed(h);  // the sliders: the table goes up again, the state stays
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_get_vca(const srack_patch* p, float* params, int* mode, int* negative, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        const int rc = busfx_preamble(p, "buses_get_vca");
+        if (rc != SRACK_OK) return rc;
+        const PatchHandle& h = p->h;
+        const BusVca& F = h.busvca;
+        if (!F.set) return 0;
+        const size_t n = std::min<size_t>(cap, h.n_buses);
+        if (params && n) std::memcpy(params, F.params.data(), sizeof(float) * n * SRACK_BUS_VCA_NPARAMS);
+        for (size_t b = 0; mode && b < n; b++) mode[b] = F.mode[b];
+        for (size_t b = 0; negative && b < n; b++) negative[b] = F.negative[b];
+        return (int)h.n_buses;
+    });
+}
+
+int srack_buses_reset_vca(srack_patch* p)
+{
+    return guarded([&]() -> int {
+        int rc = busfx_preamble(p, "buses_reset_vca");
+        if (rc != SRACK_OK) return rc;
+        if ((rc = busvca_need_set(p, "buses_reset_vca")) != SRACK_OK) return rc;
+        device_busvca_reset(p->h);
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_vca_state(srack_patch* p, float* state, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        int rc = busfx_preamble(p, "buses_vca_state");
+        if (rc != SRACK_OK) return rc;
+        if ((rc = busvca_need_set(p, "buses_vca_state")) != SRACK_OK) return rc;
+        if (state && cap && (rc = device_busvca_state(p->h, state, cap)) != SRACK_OK) return rc;
+        return (int)p->h.n_buses;
+    });
+}
+
+int srack_buses_vca(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_ctl, float* d_out, float* d_env,
+                    void* stream)
+{
+    return guarded([&]() -> int {
+        int rc = busfx_preamble(p, "buses_vca");
+        if (rc != SRACK_OK) return rc;
+        if ((rc = busvca_need_set(p, "buses_vca")) != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        if (n_samples == 0) return SRACK_OK;
+        if (!d_rows || !d_out) {
+            set_error("buses_vca: d_rows and d_out must be given");
+            return SRACK_ERR_INVALID;
+        }
+        if (row_channels < 1 || row_channels > 8) {
+            set_error("buses_vca: row_channels must be 1 .. 8");
+            return SRACK_ERR_INVALID;
+        }
+        const uintptr_t in0 = (uintptr_t)d_rows, out0 = (uintptr_t)d_out, ctl0 = (uintptr_t)d_ctl, env0 = (uintptr_t)d_env;
+        const uint64_t bytes = 4ull * h.n_buses * row_channels * n_samples, row_bytes = 4ull * h.n_buses * n_samples;
+        auto meet = [](uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) { return a < b + nb && b < a + na; };
+        if (in0 != out0 && meet(in0, bytes, out0, bytes)) {
+            set_error("buses_vca: d_out overlaps d_rows in part: it must be d_rows itself or disjoint from it");
+            return SRACK_ERR_INVALID;
+        }
+        if (d_ctl && meet(ctl0, row_bytes, out0, bytes)) {
+            set_error("buses_vca: d_ctl overlaps d_out");
+            return SRACK_ERR_INVALID;
+        }
+        if (d_env && (meet(env0, row_bytes, out0, bytes) || meet(env0, row_bytes, in0, bytes))) {
+            set_error(std::string("buses_vca: d_env overlaps ") + (meet(env0, row_bytes, out0, bytes) ? "d_out" : "d_rows"));
+            return SRACK_ERR_INVALID;
+        }
+        if (d_env && d_ctl && meet(env0, row_bytes, ctl0, row_bytes)) {
+            set_error("buses_vca: d_env overlaps d_ctl");
+            return SRACK_ERR_INVALID;
+        }
+        return device_buses_vca(h, n_samples, d_rows, row_channels, d_ctl, d_out, d_env, stream);
+    });
+}
+
 int srack_render_reserve(srack_patch* p, uint32_t n_samples, int want_mix, uint32_t flags)
 {
     return guarded([&]() -> int {
@@ -1335,6 +1459,7 @@ int srack_render_info(srack_patch* p, char* buf, size_t cap)
         s += device_bus_note(p->h);
         s += device_sends_note(p->h);
         s += device_busvcf_note(p->h);
+        s += device_busvca_note(p->h);
         s += device_busfx_note(p->h);
         s += device_master_note(p->h);
         s += device_waves_note(p->h);

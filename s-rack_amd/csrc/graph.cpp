@@ -139,7 +139,7 @@ int Graph::add_module(int type)
         m.fields[SRACK_ADSR_S_VAL] = 0.25;
         m.fields[SRACK_ADSR_R_SEC] = 0.5;
         m.fields[SRACK_ADSR_MODE] = SRACK_ADSR_MODE_NONE;
-        m.fields[SRACK_ADSR_SAMPLE_RATE] = (double)(float)cfg.sample_rate;
+        m.fields[SRACK_ADSR_SAMPLE_RATE] = (double)adsr_sample_rate();
         m.fields[SRACK_ADSR_GATE_LAST] = 1.0;
         break;
     case SRACK_MOD_VCA:  // vca.rs:18-26

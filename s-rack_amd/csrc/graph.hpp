@@ -88,6 +88,9 @@ public:
     uint64_t revision = 0;  // bumped by every structural or field edit
 
     int add_module(int type);  // returns index or SRACK_ERR_*
+    // the f32 copy of the sample rate an ADSRModule takes at new() (adsr.rs:47): what add_module gives SRACK_ADSR_SAMPLE_RATE, and what
+    // the bus VCAs' envelopes run at
+    float adsr_sample_rate() const { return (float)cfg.sample_rate; }
     int num_fields(int module) const;
     int set_field(int module, int field, double value);
     int get_field(int module, int field, double* value) const;

@@ -92,4 +92,7 @@ void launch_sends(const SendArgs& a, hipStream_t st);
 // ---- the bus filters (busvcf.hip): a lane per row of a.tab, a wave per workgroup; the disabled buses' rows copied when a.out is not a.rows ----
 void launch_bus_filter(const BusVcfArgs& a, hipStream_t st);
 
+// ---- the bus VCAs (busvca.hip): a workgroup of eight waves per 64 buses of a.tab, the envelopes on its first wave ----
+void launch_bus_vca(const BusVcaArgs& a, hipStream_t st);
+
 }  // namespace srack

@@ -89,4 +89,28 @@ struct BusVcfArgs {
     uint32_t used;              // min(row_channels, 2): table entries that share a bus, and a row of cv
 };
 
+// One srack_buses_vca call (busvca.hip.h).  The table has an entry per bus, in bus order: nothing is compacted, a workgroup takes 64
+// buses as they lie.
+struct BusVcaBus {
+    float a_sec, d_sec, s_val, r_sec;  // the bus's ADSR sliders, as given
+    uint32_t mode;                     // SRACK_BUS_VCA_OFF / _CV / _GATE
+    uint32_t negative;                 // the VCAs' flag
+    uint32_t pad[2];
+};
+static_assert(sizeof(BusVcaBus) == 32, "the host uploads the table as it stands");
+constexpr int kBusVcaFields = 6;  // SRACK_BUS_VCA_NSTATE: phase, mode, r_val, from_a_val, sample rate, gate_last
+struct BusVcaArgs {
+    const float* rows;          // [n_buses][row_channels][n]
+    const float* ctl;           // [n_buses][n] or null
+    float* out;                 // [n_buses][row_channels][n]; may be rows itself
+    float* env;                 // [n_buses][n] or null
+    float* state;               // [kBusVcaFields][n_buses], every value an f32 as the C ABI hands it out
+    const BusVcaBus* tab;       // [n_buses]
+    float rate;                 // the f32 sample rate a fresh ADSRModule of the patch carries
+    uint32_t n;                 // samples
+    uint32_t n_buses;
+    uint32_t row_channels;
+    uint32_t used;              // min(row_channels, 2): the channels that are processed
+};
+
 }  // namespace srack

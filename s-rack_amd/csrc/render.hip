@@ -243,6 +243,7 @@ PatchHandle::~PatchHandle()
     device_master_drop(*this);
     device_sends_drop(*this);
     device_busvcf_drop(*this);
+    device_busvca_drop(*this);
     device_release(dev);
     device_release(dev_old);
 }
@@ -2022,6 +2023,170 @@ int device_buses_filter(PatchHandle& h, uint32_t n_samples, const float* d_rows,
 std::string device_busvcf_note(const PatchHandle& h)
 {
     return h.busvcf.ran ? " busvcf=" + std::to_string(h.busvcf.last_enabled) + "[" + std::to_string(h.busvcf.last_waves) + " waves]" : std::string();
+}
+
+// ---- the bus VCAs (busvca.hip.h, launched through launch_bus_vca) -------------------------------------------------------------------------
+// A table entry and six state values per bus, in bus order: nothing is compacted, so a change of modes moves nothing.  The table goes
+// up again after a change of the setting, the state after a change of the set of GATE buses or a reset — both behind a host-side wait
+// for the last call's kernel, which may still be using them.  A tick session of unchanged VCAs is the launch and one event per call.
+static void busvca_wait(BusVca& F)
+{
+    if (F.ev_done) (void)hipEventSynchronize((hipEvent_t)F.ev_done);
+}
+
+// ADSRModule::new's state, f32 [6][n]: phase 0, mode None, r_val 0, from_a_val 0, the rate, TransitionDetector.last true
+static std::vector<float> busvca_fresh(const BusVca& F, size_t n)
+{
+    const float one[kBusVcaFields] = {0.0f, (float)SRACK_ADSR_MODE_NONE, 0.0f, 0.0f, F.rate, 1.0f};
+    std::vector<float> s((size_t)kBusVcaFields * n);
+    for (int f = 0; f < kBusVcaFields; f++) std::fill(s.begin() + (size_t)f * n, s.begin() + (size_t)(f + 1) * n, one[f]);
+    return s;
+}
+
+static bool busvca_all_fresh(const BusVca& F) { return F.pending.empty() && (!F.d_state || F.fresh); }
+
+// The state as it stands, f32 [6][n]
+static int busvca_fetch(BusVca& F, size_t n, std::vector<float>& out)
+{
+    if (!F.pending.empty()) {
+        out = F.pending;
+        return SRACK_OK;
+    }
+    out = busvca_fresh(F, n);
+    if (busvca_all_fresh(F)) return SRACK_OK;
+    busvca_wait(F);
+    HIP_TRY(hipMemcpy(out.data(), F.d_state, sizeof(float) * out.size(), hipMemcpyDeviceToHost));
+    return SRACK_OK;
+}
+
+void device_busvca_changed(PatchHandle& h) { h.busvca.tab_dirty = true; }
+
+void device_busvca_reset(PatchHandle& h)
+{
+    h.busvca.pending.clear();
+    h.busvca.fresh = true;  // uploaded before the next call's kernel
+}
+
+int device_busvca_modes(PatchHandle& h, const std::vector<int32_t>& mode)
+{
+    BusVca& F = h.busvca;
+    if (!F.set || busvca_all_fresh(F)) return SRACK_OK;  // fresh stays fresh
+    const size_t n = h.n_buses;
+    bool moved = false;
+    for (size_t b = 0; b < n; b++) moved = moved || ((F.mode[b] == SRACK_BUS_VCA_GATE) != (mode[b] == SRACK_BUS_VCA_GATE));
+    if (!moved) return SRACK_OK;
+    std::vector<float> cur;
+    const int rc = busvca_fetch(F, n, cur);
+    if (rc != SRACK_OK) return rc;
+    const std::vector<float> fresh = busvca_fresh(F, 1);
+    for (size_t b = 0; b < n; b++)  // a bus that stays GATE keeps its state; one that becomes GATE starts fresh; one that leaves drops it
+        if (F.mode[b] != SRACK_BUS_VCA_GATE || mode[b] != SRACK_BUS_VCA_GATE)
+            for (int f = 0; f < kBusVcaFields; f++) cur[(size_t)f * n + b] = fresh[f];
+    F.pending = std::move(cur);
+    return SRACK_OK;
+}
+
+int device_busvca_state(PatchHandle& h, float* state, uint32_t cap)
+{
+    BusVca& F = h.busvca;
+    const size_t n_buses = h.n_buses, n = std::min<size_t>(cap, n_buses);
+    std::vector<float> cur;
+    const int rc = busvca_fetch(F, n_buses, cur);
+    if (rc != SRACK_OK) return rc;
+    const std::vector<float> fresh = busvca_fresh(F, 1);
+    for (size_t b = 0; b < n; b++)
+        for (int f = 0; f < kBusVcaFields; f++) state[b * kBusVcaFields + f] = F.mode[b] == SRACK_BUS_VCA_GATE ? cur[(size_t)f * n_buses + b] : fresh[f];
+    return SRACK_OK;
+}
+
+void device_busvca_drop(PatchHandle& h)
+{
+    BusVca& F = h.busvca;
+    busvca_wait(F);
+    if (F.d_state) (void)hipFree(F.d_state);
+    if (F.d_tab) (void)hipFree(F.d_tab);
+    if (F.ev_done) (void)hipEventDestroy((hipEvent_t)F.ev_done);
+    F = BusVca();
+}
+
+int device_buses_vca(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_ctl, float* d_out, float* d_env, void* stream)
+{
+    BusVca& F = h.busvca;
+    const hipStream_t st = (hipStream_t)stream;
+    const uint32_t n_buses = h.n_buses;
+    if (!F.ev_done) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        F.ev_done = e;
+    } else {
+        HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)F.ev_done, 0));  // (calls may come on different streams: the state is one)
+    }
+    const size_t state_bytes = sizeof(float) * kBusVcaFields * n_buses, tab_bytes = sizeof(BusVcaBus) * n_buses;
+    if (!F.d_state || !F.d_tab) {  // (n_buses is fixed while the VCAs live: another n_buses drops them)
+        void *ps = nullptr, *pt = nullptr;
+        if (hipMalloc(&ps, state_bytes) != hipSuccess || hipMalloc(&pt, tab_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            if (ps) (void)hipFree(ps);
+            set_error("buses_vca: out of device memory for the VCAs' state and table (" + std::to_string(state_bytes + tab_bytes) + " bytes)");
+            return SRACK_ERR_NOMEM;
+        }
+        F.d_state = ps;
+        F.d_tab = pt;
+        F.tab_dirty = true;
+        if (F.pending.empty()) F.fresh = true;
+    }
+    if (!F.pending.empty() || F.fresh) {
+        const std::vector<float> up = F.pending.empty() ? busvca_fresh(F, n_buses) : F.pending;
+        busvca_wait(F);
+        HIP_TRY(hipMemcpy(F.d_state, up.data(), state_bytes, hipMemcpyHostToDevice));
+        F.pending.clear();
+        F.fresh = false;
+    }
+    uint32_t n_on = 0, n_gated = 0;
+    for (uint32_t b = 0; b < n_buses; b++) {
+        n_on += F.mode[b] != SRACK_BUS_VCA_OFF;
+        n_gated += F.mode[b] == SRACK_BUS_VCA_GATE;
+    }
+    if (F.tab_dirty) {
+        std::vector<BusVcaBus> tab(n_buses);
+        for (uint32_t b = 0; b < n_buses; b++) {
+            BusVcaBus& r = tab[b];
+            r.a_sec = F.params[(size_t)b * SRACK_BUS_VCA_NPARAMS + SRACK_ADSR_A_SEC];
+            r.d_sec = F.params[(size_t)b * SRACK_BUS_VCA_NPARAMS + SRACK_ADSR_D_SEC];
+            r.s_val = F.params[(size_t)b * SRACK_BUS_VCA_NPARAMS + SRACK_ADSR_S_VAL];
+            r.r_sec = F.params[(size_t)b * SRACK_BUS_VCA_NPARAMS + SRACK_ADSR_R_SEC];
+            r.mode = (uint32_t)F.mode[b];
+            r.negative = F.negative[b];
+            r.pad[0] = r.pad[1] = 0;
+        }
+        busvca_wait(F);
+        HIP_TRY(hipMemcpy(F.d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice));
+        F.tab_dirty = false;
+    }
+    BusVcaArgs a;
+    a.rows = d_rows;
+    a.ctl = d_ctl;
+    a.out = d_out;
+    a.env = d_env;
+    a.state = (float*)F.d_state;
+    a.tab = (const BusVcaBus*)F.d_tab;
+    a.rate = F.rate;
+    a.n = n_samples;
+    a.n_buses = n_buses;
+    a.row_channels = row_channels;
+    a.used = row_channels < 2 ? row_channels : 2u;
+    launch_bus_vca(a, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord((hipEvent_t)F.ev_done, st));
+    F.last_on = n_on;
+    F.last_gated = n_gated;
+    F.ran = true;
+    return SRACK_OK;
+}
+
+std::string device_busvca_note(const PatchHandle& h)
+{
+    return h.busvca.ran ? " busvca=" + std::to_string(h.busvca.last_on) + "[" + std::to_string(h.busvca.last_gated) + " gated]" : std::string();
 }
 
 const char* device_kernel_name(const PatchHandle& h) { return h.dev ? h.dev->kernel_name : ""; }

@@ -102,6 +102,29 @@ struct BusVcf {
     bool ran = false;
 };
 
+// The bus VCAs (srack_buses_set_vca / srack_buses_vca): an ADSRModule and its VCAModules per mix bus, behind the mixer.  Like the filters
+// they hang off the handle: not the program's, not DeviceState's; dropped with the table.
+// The state is indexed by bus, f32 [SRACK_BUS_VCA_NSTATE][n_buses] on the device between calls, every value as the C ABI hands it out
+// (busvca.hip.h): nothing moves when modes change.  A bus that is not GATE holds the fresh state there; when the set of GATE buses
+// changes, the state comes to the host, the buses that joined or left are made fresh (`pending`) and it goes up again before the
+// next call's kernel.
+struct BusVca {
+    bool set = false;
+    std::vector<float> params;      // [n_buses][SRACK_BUS_VCA_NPARAMS], as the host gave them
+    std::vector<int32_t> mode;      // [n_buses] SRACK_BUS_VCA_OFF / _CV / _GATE
+    std::vector<uint8_t> negative;  // [n_buses]
+    float rate = 0.0f;              // the f32 sample rate a fresh ADSRModule of this patch carries (Graph::adsr_sample_rate)
+    // device side (render.hip); nothing of it exists before the first srack_buses_vca
+    void* d_state = nullptr;        // f32 [6][n_buses]
+    bool fresh = true;              // every state is to be made fresh before the next call uses it (nothing ran yet, or reset_vca)
+    std::vector<float> pending;     // [6][n_buses] the state to be uploaded before the next call; empty: none
+    void* d_tab = nullptr;          // BusVcaBus [n_buses]
+    bool tab_dirty = true;          // sliders, modes or flags changed
+    void* ev_done = nullptr;        // hipEvent_t behind every call's kernel: the next call, and whoever frees or rewrites, waits for it
+    uint32_t last_on = 0, last_gated = 0;  // srack_render_info, once a call has run
+    bool ran = false;
+};
+
 struct PatchHandle {
     Graph graph;
     uint32_t n_voices = 0;
@@ -140,6 +163,7 @@ struct PatchHandle {
     Master master;                  // the master section; dropped with the table as well
     Sends sends;                    // the bus sends; dropped with the table as well
     BusVcf busvcf;                  // the bus filters; dropped with the table as well
+    BusVca busvca;                  // the bus VCAs; dropped with the table as well
     bool timing_armed = false;      // srack_render_kernel_ms has been called: renders bracket the dominant kernel with HIP events
 
     ~PatchHandle();
@@ -182,6 +206,14 @@ void device_busvcf_changed(PatchHandle& h);  // parameters, ports or the enabled
 void device_busvcf_reset(PatchHandle& h);    // every state to zero, before the next call uses it
 void device_busvcf_drop(PatchHandle& h);     // parameters, state, table and the note
 std::string device_busvcf_note(const PatchHandle& h);  // " busvcf=48[2 waves]" once a call has run, else ""
+// The bus VCAs: one call's work enqueued on `stream` (allocating and uploading what is missing); state handling without a call.
+int device_buses_vca(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_ctl, float* d_out, float* d_env, void* stream);
+int device_busvca_modes(PatchHandle& h, const std::vector<int32_t>& mode);  // the modes are about to become these: a bus that joins or leaves GATE is made fresh
+int device_busvca_state(PatchHandle& h, float* state, uint32_t cap);        // host, f32 [cap][6] as the C ABI hands it out, behind a wait for the last call
+void device_busvca_changed(PatchHandle& h);  // sliders, modes or flags were replaced: the next call uploads the table
+void device_busvca_reset(PatchHandle& h);    // every state fresh, before the next call uses it
+void device_busvca_drop(PatchHandle& h);     // settings, state, table and the note
+std::string device_busvca_note(const PatchHandle& h);  // " busvca=48[32 gated]" once a call has run, else ""
 std::string device_bus_note(const PatchHandle& h);  // " buses=4096[fold]" when the last render filled bus mixes, else ""
 std::string device_waves_note(const PatchHandle& h);  // " waves=9[lds]" / " waves=9[global]" for a patch that renders with a wave assignment, else ""
 std::string device_sequences_note(const PatchHandle& h);  // " sequences=9[global]" for a patch that renders with a sequence assignment, else ""

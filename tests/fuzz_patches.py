@@ -1,4 +1,5 @@
-"""Random patches for differential tests (tests/test_gpu_fuzz.py: GPU vs oracle; tests/test_oracle.py: C oracle vs NumPy twin)."""
+"""Random patches for differential tests (tests/test_gpu_fuzz.py and tests/test_gpu_banked_fuzz.py: GPU vs oracle; tests/test_oracle.py and
+tests/test_banked_fuzz_host.py: C oracle vs NumPy twin)."""
 import numpy as np
 
 import srack_pkg
@@ -124,3 +125,159 @@ def random_patch(seed, noise=False):
                     else:
                         overrides.append((m, f, lambda V, g=gen, a=lo_, b=hi_: g.uniform(a, b, V).astype(np.float32)))
     return B, build, overrides
+
+
+# ---- the banked family: a wave / a sequence per voice (tests/test_gpu_banked_fuzz.py, tests/test_banked_fuzz_host.py) ----------------
+BANK_WAVE_LENGTHS = [0, 1, 2, 3, 63, 64, 65, 255, 256, 257]
+BANK_RATES = [8000.0, 22050.0, 44100.0, 48000.0, 96000.0]
+BANK_SEQ_LENGTHS = [1, 2, 7, 63, 64]
+BANK_AMPLITUDES = [1.0, 1.0, 4.0]   # a bank's samples are uniform in +-a: a third of the banks are louder than any own wave
+BANK_NOTE_MAX = 48                  # a bank's grid values are 0 ... 48, the own ones 0 ... 24: the bank's highest note is above the own one
+
+
+def random_banked_patch(seed):
+    """-> (B, build(g) -> ids, overrides, banks, assignments): random_patch's draw (types, fields, wiring rule, cycles, OutputModule anywhere)
+    from a stream of its own, with at least one sample player and one sequencer, and a bank on every one of them.
+
+    banks: [{"m", "type": SMP, "waves": [f32 arrays], "rates": [...]} | {"m", "type": GRID | PAT, "states": u8 [n][64] | [n][8][64],
+    "values": u16 [n][64] | None, "lengths": int [n]}]; assignments: {m: fn(V, edit=0) -> int32 [V] in [-1, n)} — a bank whose module is
+    not a key stays without an assignment; edit > 0 draws the fresh assignment of an edit.  build.types / .conns / .out_conns describe
+    the graph to the guards; build.own ({m: (wave, rate) | None}) and build.cells are what build() leaves in the players and sequencers."""
+    rng = np.random.default_rng((seed, 0xBA2C))
+    B = int(rng.choice([1, 3, 16, 64, 1024]))
+    n_smp = 1 if rng.random() < 0.65 else int(rng.integers(2, 4))
+    seqs = [GRID, PAT] if rng.random() < 0.35 else [int(rng.choice([GRID, PAT]))]
+    forced = [OSC, OSC] + [SMP] * n_smp + seqs
+    n = int(rng.integers(max(4, len(forced)), 11))
+    types = forced + [int(rng.choice([OSC, VCF, ADSR, VCA, MIX, MATH, GRID, PAT, SMP], p=[.2, .15, .12, .13, .1, .15, .05, .05, .05])) for _ in range(n - len(forced))]
+    rng.shuffle(types)
+    fields, steps, conns, waves, own = [], [], [], [], {}
+    for m, t in enumerate(types):
+        if t == OSC:
+            fields.append((m, W.OSC_VAL, float(np.float32(rng.uniform(-6, 3)))))
+            if rng.random() < 0.2:
+                fields.append((m, W.OSC_ANTIALIASING, 0))
+        elif t == VCF:
+            fields += [(m, W.VCF_FREQ, float(np.float32(rng.uniform(0.02, 0.8)))), (m, W.VCF_RES, float(np.float32(rng.uniform(0, 1)))),
+                       (m, W.VCF_EXP_AMT, float(np.float32(rng.uniform(0, 1))))]
+        elif t == ADSR:
+            fields += [(m, f, float(np.float32(v))) for f, v in zip((W.ADSR_A_SEC, W.ADSR_D_SEC, W.ADSR_S_VAL, W.ADSR_R_SEC),
+                                                                    (rng.choice([0.0, 0.001, 0.004]), rng.uniform(0.001, 0.01), rng.uniform(0, 1), rng.uniform(0.001, 0.01)))]
+        elif t == VCA:
+            fields.append((m, W.VCA_NEGATIVE, int(rng.random() < 0.3)))
+        elif t == MIX:
+            fields += [(m, W.MIX_GAIN0 + k, float(np.float32(rng.uniform(0, 1.2)))) for k in range(4)]
+        elif t == MATH:
+            fields += [(m, W.MATH_CONSTANT, float(np.float32(rng.uniform(-1, 1)))), (m, W.MATH_OPERATION, int(rng.integers(0, 3)))]
+        elif t == SMP:
+            wave, rate = rng.uniform(-1, 1, int(rng.integers(1, 401))).astype(np.float32), float(rng.choice([8000.0, 44100.0, 48000.0, 96000.0]))
+            own[m] = None if rng.random() < 0.125 else (wave, rate)   # one in eight: a player nobody loaded a wave into
+            if own[m]:
+                waves.append((m, wave, rate))
+        elif t in (GRID, PAT):
+            length = int(rng.integers(1, 9))
+            fields.append((m, W.GRIDSEQ_LENGTH if t == GRID else W.PATSEQ_LENGTH, length))
+            for i in range(length):
+                for ch in ([0] if t == GRID else [0, 3, 7]):
+                    steps.append((m, ch, i, int(rng.integers(0, 3)), int(rng.integers(0, 25))))
+    for m, t in enumerate(types):
+        for k in range(N_IN[t]):
+            if rng.random() < 0.75:
+                src = int(rng.integers(0, n - 1))
+                src += src >= m
+                conns.append((src, int(rng.choice(OUT_PORTS[types[src]])), m, k))
+    out_src = [int(rng.integers(0, n)) for _ in range(2)]
+    if rng.random() < 0.4:   # (the one weight that differs from random_patch's: else half of the family's assigned modules are dead code)
+        out_src[0] = int(rng.choice([m for m, t in enumerate(types) if t in (SMP, GRID, PAT)]))
+    out_conns = [(s, int(rng.choice(OUT_PORTS[types[s]])), c) for c, s in enumerate(out_src) if rng.random() < 0.9]
+    if not out_conns:
+        out_conns = [(out_src[0], OUT_PORTS[types[out_src[0]]][0], 0)]
+    out_pos = int(rng.integers(0, n + 1))
+
+    def build(g):
+        ids = []
+        for i, t in enumerate(types):
+            if i == out_pos:
+                build.out = g.add_module(0)
+            ids.append(g.add_module(t))
+        if out_pos == n:
+            build.out = g.add_module(0)
+        for m, f, v in fields:
+            g.set_field(ids[m], f, v)
+        for m, ch, i, st, val in steps:
+            g.set_step(ids[m], ch, i, st, val)
+        for m, wave, rate in waves:
+            g.set_wave(ids[m], wave, rate)
+        for s, sp, k, kp in conns:
+            g.connect(ids[s], sp, ids[k], kp)
+        for s, sp, c in out_conns:
+            g.connect(ids[s], sp, build.out, c)
+        return ids
+
+    build.types, build.conns, build.out_conns, build.own = list(types), list(conns), list(out_conns), own
+    build.cells = {}   # what build() leaves in a sequencer: {m: (states u8 [channels][64], values u16 [64], length)}
+    for m, t in enumerate(types):
+        if t in (GRID, PAT):
+            build.cells[m] = (np.zeros((1 if t == GRID else 8, 64), dtype=np.uint8), np.zeros(64, dtype=np.uint16), next(v for mm, f, v in fields if mm == m))
+    for m, ch, i, st, val in steps:
+        build.cells[m][0][ch, i] = st
+        if types[m] == GRID:
+            build.cells[m][1][i] = val
+
+    overrides = []
+    for m, t in enumerate(types):
+        if rng.random() < 0.45:
+            gen = np.random.default_rng((seed, 0xBA2C, m))
+            if t == OSC:
+                overrides.append((m, W.OSC_VAL, lambda V, r=gen: r.uniform(-5, 2, V).astype(np.float32)))
+            elif t == VCF:
+                overrides.append((m, W.VCF_FREQ, lambda V, r=gen: r.uniform(0.03, 0.7, V).astype(np.float32)))
+            elif t == MATH:
+                overrides.append((m, W.MATH_CONSTANT, lambda V, r=gen: r.uniform(-1, 1, V).astype(np.float32)))
+            elif t == MIX:
+                overrides.append((m, W.MIX_GAIN0 + 1, lambda V, r=gen: r.uniform(0, 1, V).astype(np.float32)))
+            elif t == ADSR:
+                overrides.append((m, W.ADSR_S_VAL, lambda V, r=gen: r.uniform(0, 1, V).astype(np.float32)))
+
+    # ---- banks, assignments, and the overrides that meet them ----
+    banks, assignments = [], {}
+    long_wave_at = int(rng.integers(0, n_smp)) if rng.random() < 0.25 else -1   # a quarter of the patches: one wave past the 2 048 an LDS copy holds
+    k_smp = 0
+    for m, t in enumerate(types):
+        if t == SMP:
+            n_waves = int(rng.integers(1, 10))
+            lengths = [int(rng.choice(BANK_WAVE_LENGTHS)) if rng.random() < 0.7 else int(rng.integers(0, 1201)) for _ in range(n_waves)]
+            if rng.random() < 0.5:   # a small bank: with the own wave it fits one LDS copy
+                lengths = [min(x, 257) for x in lengths]
+            if k_smp == long_wave_at:
+                lengths[int(rng.integers(0, n_waves))] = int(rng.integers(2049, 5001))
+            k_smp += 1
+            a = float(rng.choice(BANK_AMPLITUDES))
+            banks.append({"m": m, "type": SMP, "waves": [rng.uniform(-a, a, x).astype(np.float32) for x in lengths],
+                          "rates": [float(rng.choice(BANK_RATES)) for _ in range(n_waves)]})
+            n_items = n_waves
+        elif t in (GRID, PAT):
+            n_items = int(rng.integers(1, 9))
+            lengths = np.array([int(rng.choice(BANK_SEQ_LENGTHS)) if rng.random() < 0.6 else int(rng.integers(1, 65)) for _ in range(n_items)], dtype=np.intc)
+            if t == GRID:   # cells past a sequence's length are drawn like the others: only `lengths` may delimit
+                st, vals = rng.integers(0, 3, (n_items, 64)).astype(np.uint8), rng.integers(0, BANK_NOTE_MAX + 1, (n_items, 64)).astype(np.uint16)
+            else:
+                st, vals = rng.integers(0, 3, (n_items, 8, 64)).astype(np.uint8), None
+            banks.append({"m": m, "type": t, "states": st, "values": vals, "lengths": lengths})
+            if rng.random() < 0.5:   # at or past most lengths: the wrap happens at sample 0
+                overrides.append((m, W.GRIDSEQ_CURRENT_STEP if t == GRID else W.PATSEQ_CURRENT_STEP,
+                                  lambda V, r=np.random.default_rng((seed, 0xBA2C, m, 1)): r.integers(0, 64, V).astype(np.float32)))
+        else:
+            continue
+        if rng.random() < 0.8:
+            const = int(rng.integers(-1, n_items)) if rng.random() < 0.2 else None   # one assignment in five: the same item for every voice
+
+            def assign(V, edit=0, m=m, n_items=n_items, const=const):
+                if const is not None and edit == 0:
+                    return np.full(V, const, dtype=np.intc)
+                return np.random.default_rng((seed, 0xBA2C, m, 2, edit)).integers(-1, n_items, V).astype(np.intc)
+
+            assignments[m] = assign
+            if t == SMP and rng.random() < 0.35:   # honoured by the voices on the own wave, ignored by the banked ones
+                overrides.append((m, W.SAMPLE_WAVE_SAMPLE_RATE, lambda V, r=np.random.default_rng((seed, 0xBA2C, m, 3)): r.choice(BANK_RATES + [12345.0, 32000.0], V).astype(np.float32)))
+    return B, build, overrides, banks, assignments

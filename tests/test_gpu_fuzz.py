@@ -5,6 +5,10 @@ saw / square ports, ladder filter, ADSR, VCA, mixer, math, both sequencers, the 
 patches — the noise source), wired at random — cycles included, so the
 planner's broken edges become delay rings — with random parameters and random per-voice overrides.  What this is after
 is the host side: planning, dead-code elimination, uniform hoisting, control units, wire-slot reuse, rings, tiles.
+
+What a lane READS per voice — a wave per voice for the sample players, a sequence per voice for the sequencers — is a family of its own,
+random_banked_patch, with a reference of its own: tests/test_gpu_banked_fuzz.py.  random_patch draws neither, so the seeds here keep
+their patches.
 """
 import numpy as np
 import pytest

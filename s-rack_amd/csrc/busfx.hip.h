@@ -23,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "busfx_args.hpp"
 #include "program.hpp"
 
 namespace srack {
@@ -32,21 +33,6 @@ constexpr int kBusFxThreads = 256;  // = the longest block: one sample per threa
 // 2 (mod 32) doubles puts the 16 rows 4 banks apart — conflict-free; the threads' column accesses are consecutive doubles
 constexpr int kBusFxPitch = 258;
 constexpr int kBusFxScan = 8;       // scan steps whose LDS reads are issued together
-
-struct BusFxDev {    // one bus, on the device
-    double* state;   // [kFvStates + sum of line lengths]; null: the bus has no reverb
-    double par[7];   // comb feedback, comb dampening, 1 - dampening, wet_gains.0, wet_gains.1, dry, input_gain (freeverb_params.hpp)
-};
-
-struct BusFxArgs {
-    const float* in;       // [n_buses][channels][n]
-    float* out;            // [n_buses][2][n]
-    const BusFxDev* tab;   // [n_buses]
-    uint32_t n, channels;
-    uint32_t block;        // T: 1 <= T <= min(kBusFxThreads, shortest line)
-    uint32_t len[kFvLines], first[kFvLines];
-    uint32_t pos[kFvLines];  // slot of the call's first sample in each line: samples since the last reset mod length
-};
 
 __global__ __launch_bounds__(kBusFxThreads) void bus_reverb(const BusFxArgs a)
 {

@@ -33,15 +33,6 @@ struct srack_patch {
         }                                     \
     } while (0)
 
-#define HIP_TRY_C(expr)                                                     \
-    do {                                                                    \
-        hipError_t e_ = (expr);                                             \
-        if (e_ != hipSuccess) {                                             \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));   \
-            return SRACK_ERR_DEVICE;                                        \
-        }                                                                   \
-    } while (0)
-
 // No C++ exception may cross the C boundary (a Rust or ctypes host cannot unwind it): allocation failures become
 // SRACK_ERR_NOMEM, anything else SRACK_ERR_INVALID with the text in srack_last_error().
 template <class F>
@@ -686,11 +677,7 @@ int srack_voices_configure(srack_patch* p, uint32_t n_voices)
         p->h.bus_gain.clear();
         p->h.bus_plan = BusPlan();
         p->h.bus_revision++;
-        device_busfx_drop(p->h);  // the reverbs sat behind that table
-        device_master_drop(p->h);  // ... and so did the master's gains
-        device_sends_drop(p->h);   // ... and the sends between its buses
-        device_busvcf_drop(p->h);  // ... and the filters on them
-        device_busvca_drop(p->h);  // ... and their VCAs
+        device_console_drop(p->h);  // the console's stages sat behind that table
         return SRACK_OK;
     });
 }
@@ -762,13 +749,7 @@ int srack_voices_set_buses(srack_patch* p, uint32_t n_buses, const int* bus, con
         if (bus) std::copy(bus, bus + h.n_voices, b.begin());
         if (gain) std::copy(gain, gain + h.n_voices, g.begin());
         BusPlan plan = bus_plan_make(h.n_voices, n_buses, b.data());
-        if (n_buses != h.n_buses) {  // other buses: their reverbs go, parameters and state, the master's gains and the sends (the same count keeps all)
-            device_busfx_drop(h);
-            device_master_drop(h);
-            device_sends_drop(h);
-            device_busvcf_drop(h);
-            device_busvca_drop(h);
-        }
+        if (n_buses != h.n_buses) device_console_drop(h);  // other buses: the console's stages go, settings and state (the same count keeps all)
         h.n_buses = n_buses;
         h.bus = std::move(b);
         h.bus_gain = std::move(g);
@@ -832,11 +813,9 @@ int srack_render_buses(srack_patch* p, uint32_t n_samples, float* d_frames, floa
     });
 }
 
-// ---- the bus reverbs ---------------------------------------------------------------------------------------------
-static const double kFvDefaults[SRACK_FREEVERB__NFIELDS] = {0.5, 0.0, 1.0, 0.5, 0.5, 0.0};  // FreeverbModule::new (freeverb.rs:36-60), in field order
-
-// what every one of the five calls asks first
-static int busfx_preamble(const srack_patch* p, const char* who)
+// ---- the bus console: what its calls ask of their arguments ------------------------------------------------------
+// what every call of every stage asks first
+static int console_preamble(const srack_patch* p, const char* who)
 {
     CHECK_HANDLE(p);
     const PatchHandle& h = p->h;
@@ -850,6 +829,34 @@ static int busfx_preamble(const srack_patch* p, const char* who)
     }
     return SRACK_OK;
 }
+
+// a stage's calls other than its setter and getter: `noun` ("filters") must have been set by srack_buses_set_<setter> ("filter")
+static int need_set(bool set, const char* who, const char* noun, const char* setter)
+{
+    if (set) return SRACK_OK;
+    set_error(std::string(who) + ": no " + noun + " set: call srack_buses_set_" + setter + " first");
+    return SRACK_ERR_STATE;
+}
+
+// the rows a stage reads and the buffer `out` ("d_out", the master's "d_master") it writes
+static int need_rows(const char* who, const void* d_rows, const void* d_out, const char* out, uint32_t row_channels)
+{
+    if (!d_rows || !d_out) {
+        set_error(std::string(who) + ": d_rows and " + out + " must be given");
+        return SRACK_ERR_INVALID;
+    }
+    if (row_channels < 1 || row_channels > 8) {
+        set_error(std::string(who) + ": row_channels must be 1 .. 8");
+        return SRACK_ERR_INVALID;
+    }
+    return SRACK_OK;
+}
+
+// do na bytes at a and nb bytes at b overlap
+static bool meet(const void* a, uint64_t na, const void* b, uint64_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
+
+// ---- the bus reverbs ---------------------------------------------------------------------------------------------
+static const double kFvDefaults[SRACK_FREEVERB__NFIELDS] = {0.5, 0.0, 1.0, 0.5, 0.5, 0.0};  // FreeverbModule::new (freeverb.rs:36-60), in field order
 
 static int busfx_lines(const srack_patch* p, const char* who, uint32_t len[kFvLines], uint32_t first[kFvLines], uint32_t* total, uint32_t* block)
 {
@@ -865,10 +872,10 @@ static int busfx_lines(const srack_patch* p, const char* who, uint32_t len[kFvLi
 int srack_buses_set_reverb(srack_patch* p, const double* params, const int* enabled)
 {
     return guarded([&]() -> int {
-        int rc = busfx_preamble(p, "buses_set_reverb");
+        int rc = console_preamble(p, "buses_set_reverb");
         if (rc != SRACK_OK) return rc;
         PatchHandle& h = p->h;
-        BusFx& F = h.busfx;
+        BusFx& F = h.console.busfx;
         uint32_t len[kFvLines], first[kFvLines], total = 0, block = 0;
         if ((rc = busfx_lines(p, "buses_set_reverb", len, first, &total, &block)) != SRACK_OK) return rc;
         const size_t n = h.n_buses;
@@ -901,10 +908,10 @@ int srack_buses_set_reverb(srack_patch* p, const double* params, const int* enab
 int srack_buses_get_reverb(const srack_patch* p, double* params, int* enabled, uint32_t cap)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_get_reverb");
+        const int rc = console_preamble(p, "buses_get_reverb");
         if (rc != SRACK_OK) return rc;
         const PatchHandle& h = p->h;
-        const BusFx& F = h.busfx;
+        const BusFx& F = h.console.busfx;
         if (!F.set) return 0;
         const size_t n = std::min<size_t>(cap, h.n_buses);
         if (params) std::copy(F.params.begin(), F.params.begin() + n * SRACK_FREEVERB__NFIELDS, params);
@@ -916,13 +923,10 @@ int srack_buses_get_reverb(const srack_patch* p, double* params, int* enabled, u
 int srack_buses_reset_reverb(srack_patch* p)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_reset_reverb");
+        int rc = console_preamble(p, "buses_reset_reverb");
         if (rc != SRACK_OK) return rc;
-        BusFx& F = p->h.busfx;
-        if (!F.set) {
-            set_error("buses_reset_reverb: no reverbs set: call srack_buses_set_reverb first");
-            return SRACK_ERR_STATE;
-        }
+        BusFx& F = p->h.console.busfx;
+        if ((rc = need_set(F.set, "buses_reset_reverb", "reverbs", "reverb")) != SRACK_OK) return rc;
         std::fill(F.fresh.begin(), F.fresh.end(), (uint8_t)1);  // zeroed on the next call's stream, before its kernel
         F.counter = 0;
         return SRACK_OK;
@@ -932,7 +936,7 @@ int srack_buses_reset_reverb(srack_patch* p)
 int srack_buses_reverb_plan(const srack_patch* p, int* line_lengths, int* block)
 {
     return guarded([&]() -> int {
-        int rc = busfx_preamble(p, "buses_reverb_plan");
+        int rc = console_preamble(p, "buses_reverb_plan");
         if (rc != SRACK_OK) return rc;
         uint32_t len[kFvLines], first[kFvLines], total = 0, T = 0;
         if ((rc = busfx_lines(p, "buses_reverb_plan", len, first, &total, &T)) != SRACK_OK) return rc;
@@ -945,21 +949,17 @@ int srack_buses_reverb_plan(const srack_patch* p, int* line_lengths, int* block)
 int srack_buses_reverb(srack_patch* p, uint32_t n_samples, const float* d_bus_mix, float* d_bus_fx, void* stream)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_reverb");
+        int rc = console_preamble(p, "buses_reverb");
         if (rc != SRACK_OK) return rc;
         PatchHandle& h = p->h;
-        if (!h.busfx.set) {
-            set_error("buses_reverb: no reverbs set: call srack_buses_set_reverb first");
-            return SRACK_ERR_STATE;
-        }
+        if ((rc = need_set(h.console.busfx.set, "buses_reverb", "reverbs", "reverb")) != SRACK_OK) return rc;
         if (n_samples == 0) return SRACK_OK;
         if (!d_bus_mix || !d_bus_fx) {
             set_error("buses_reverb: d_bus_mix and d_bus_fx must be given");
             return SRACK_ERR_INVALID;
         }
-        const uintptr_t in0 = (uintptr_t)d_bus_mix, out0 = (uintptr_t)d_bus_fx;
         const uint64_t in_bytes = 4ull * h.n_buses * h.graph.cfg.channels * n_samples, out_bytes = 4ull * h.n_buses * 2 * n_samples;
-        if (in0 < out0 + out_bytes && out0 < in0 + in_bytes) {
+        if (meet(d_bus_mix, in_bytes, d_bus_fx, out_bytes)) {
             set_error("buses_reverb: d_bus_fx overlaps d_bus_mix");
             return SRACK_ERR_INVALID;
         }
@@ -971,14 +971,14 @@ int srack_buses_reverb(srack_patch* p, uint32_t n_samples, const float* d_bus_mi
 int srack_buses_set_master(srack_patch* p, const float* gain)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_set_master");
+        const int rc = console_preamble(p, "buses_set_master");
         if (rc != SRACK_OK) return rc;
         PatchHandle& h = p->h;
         // (built aside: an allocation failure leaves the earlier gains in place)
         std::vector<float> g((size_t)h.n_buses * 2, 1.0f);
         if (gain) std::memcpy(g.data(), gain, sizeof(float) * g.size());  // (bit for bit: NaN payloads, signed zeros)
-        h.master.gain = std::move(g);
-        h.master.set = true;
+        h.console.master.gain = std::move(g);
+        h.console.master.set = true;
         device_master_gains_changed(h);
         return SRACK_OK;
     });
@@ -987,12 +987,12 @@ int srack_buses_set_master(srack_patch* p, const float* gain)
 int srack_buses_get_master(const srack_patch* p, float* gain, uint32_t cap)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_get_master");
+        const int rc = console_preamble(p, "buses_get_master");
         if (rc != SRACK_OK) return rc;
         const PatchHandle& h = p->h;
-        if (!h.master.set) return 0;
+        if (!h.console.master.set) return 0;
         const size_t n = std::min<size_t>(cap, h.n_buses);
-        if (gain && n) std::memcpy(gain, h.master.gain.data(), sizeof(float) * 2 * n);
+        if (gain && n) std::memcpy(gain, h.console.master.gain.data(), sizeof(float) * 2 * n);
         return (int)h.n_buses;
     });
 }
@@ -1000,25 +1000,16 @@ int srack_buses_get_master(const srack_patch* p, float* gain, uint32_t cap)
 int srack_buses_master(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_master, double* d_master_stats, void* stream)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_master");
+        int rc = console_preamble(p, "buses_master");
         if (rc != SRACK_OK) return rc;
         PatchHandle& h = p->h;
         if (n_samples == 0) return SRACK_OK;
-        if (!d_rows || !d_master) {
-            set_error("buses_master: d_rows and d_master must be given");
-            return SRACK_ERR_INVALID;
-        }
-        if (row_channels < 1 || row_channels > 8) {
-            set_error("buses_master: row_channels must be 1 .. 8");
-            return SRACK_ERR_INVALID;
-        }
+        if ((rc = need_rows("buses_master", d_rows, d_master, "d_master", row_channels)) != SRACK_OK) return rc;
         if (((uintptr_t)d_master_stats & 7u) != 0) {
             set_error("buses_master: d_master_stats must be 8-byte aligned");
             return SRACK_ERR_INVALID;
         }
-        const uintptr_t in0 = (uintptr_t)d_rows, out0 = (uintptr_t)d_master;
-        const uint64_t in_bytes = 4ull * h.n_buses * row_channels * n_samples, out_bytes = 4ull * 2 * n_samples;
-        if (in0 < out0 + out_bytes && out0 < in0 + in_bytes) {
+        if (meet(d_rows, 4ull * h.n_buses * row_channels * n_samples, d_master, 4ull * 2 * n_samples)) {
             set_error("buses_master: d_master overlaps d_rows");
             return SRACK_ERR_INVALID;
         }
@@ -1075,7 +1066,7 @@ static void sends_plan_make(Sends& S, uint32_t n_buses)
 int srack_buses_set_sends(srack_patch* p, uint32_t n_sends, const int* src, const int* dst, const float* gain, const float* through)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_set_sends");
+        const int rc = console_preamble(p, "buses_set_sends");
         if (rc != SRACK_OK) return rc;
         PatchHandle& h = p->h;
         if (n_sends > SRACK_MAX_SENDS) {
@@ -1111,7 +1102,7 @@ int srack_buses_set_sends(srack_patch* p, uint32_t n_sends, const int* src, cons
         if (gain) std::memcpy(S.gain.data(), gain, sizeof(float) * S.gain.size());  // (bit for bit: NaN payloads, signed zeros)
         if (through) std::memcpy(S.through.data(), through, sizeof(float) * S.through.size());
         sends_plan_make(S, h.n_buses);
-        Sends& T = h.sends;  // the device side stays: tables (uploaded again by the next call), scratch, event and note
+        Sends& T = h.console.sends;  // the device side stays: tables (uploaded again by the next call), scratch, event and note
         T.src = std::move(S.src), T.dst = std::move(S.dst), T.gain = std::move(S.gain), T.through = std::move(S.through);
         T.n_terms = std::move(S.n_terms), T.order = std::move(S.order), T.term_src = std::move(S.term_src), T.term_gain = std::move(S.term_gain);
         T.runs = std::move(S.runs), T.multi = std::move(S.multi);
@@ -1126,10 +1117,10 @@ int srack_buses_set_sends(srack_patch* p, uint32_t n_sends, const int* src, cons
 int srack_buses_get_sends(const srack_patch* p, int* src, int* dst, float* gain, uint32_t cap, float* through, uint32_t through_cap)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_get_sends");
+        const int rc = console_preamble(p, "buses_get_sends");
         if (rc != SRACK_OK) return rc;
         const PatchHandle& h = p->h;
-        const Sends& S = h.sends;
+        const Sends& S = h.console.sends;
         if (!S.set) return 0;
         const size_t n = std::min<size_t>(cap, S.src.size()), nb = std::min<size_t>(through_cap, h.n_buses);
         if (src && n) std::memcpy(src, S.src.data(), sizeof(int) * n);
@@ -1143,10 +1134,10 @@ int srack_buses_get_sends(const srack_patch* p, int* src, int* dst, float* gain,
 int srack_buses_send_plan(const srack_patch* p, int* n_terms, uint32_t bus_cap, int* order, uint32_t order_cap)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_send_plan");
+        const int rc = console_preamble(p, "buses_send_plan");
         if (rc != SRACK_OK) return rc;
         const PatchHandle& h = p->h;
-        const Sends& S = h.sends;
+        const Sends& S = h.console.sends;
         if (!S.set) return 0;
         const size_t nb = std::min<size_t>(bus_cap, h.n_buses), n = std::min<size_t>(order_cap, S.order.size());
         if (n_terms && nb) std::memcpy(n_terms, S.n_terms.data(), sizeof(int) * nb);
@@ -1158,25 +1149,14 @@ int srack_buses_send_plan(const srack_patch* p, int* n_terms, uint32_t bus_cap, 
 int srack_buses_send(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_out, void* stream)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_send");
+        int rc = console_preamble(p, "buses_send");
         if (rc != SRACK_OK) return rc;
         PatchHandle& h = p->h;
-        if (!h.sends.set) {
-            set_error("buses_send: no sends set: call srack_buses_set_sends first");
-            return SRACK_ERR_STATE;
-        }
+        if ((rc = need_set(h.console.sends.set, "buses_send", "sends", "sends")) != SRACK_OK) return rc;
         if (n_samples == 0) return SRACK_OK;
-        if (!d_rows || !d_out) {
-            set_error("buses_send: d_rows and d_out must be given");
-            return SRACK_ERR_INVALID;
-        }
-        if (row_channels < 1 || row_channels > 8) {
-            set_error("buses_send: row_channels must be 1 .. 8");
-            return SRACK_ERR_INVALID;
-        }
-        const uintptr_t in0 = (uintptr_t)d_rows, out0 = (uintptr_t)d_out;
+        if ((rc = need_rows("buses_send", d_rows, d_out, "d_out", row_channels)) != SRACK_OK) return rc;
         const uint64_t bytes = 4ull * h.n_buses * row_channels * n_samples;
-        if (in0 < out0 + bytes && out0 < in0 + bytes) {
+        if (meet(d_rows, bytes, d_out, bytes)) {
             set_error("buses_send: d_out overlaps d_rows");
             return SRACK_ERR_INVALID;
         }
@@ -1187,20 +1167,13 @@ int srack_buses_send(srack_patch* p, uint32_t n_samples, const float* d_rows, ui
 // ---- the bus filters -----------------------------------------------------------------------------------------------
 static const float kBusVcfDefaults[SRACK_BUS_FILTER_NPARAMS] = {0.2f, 0.5f, 0.5f};  // MoogFilterModule::new: freq, res, exp_amt
 
-static int busvcf_need_set(const srack_patch* p, const char* who)
-{
-    if (p->h.busvcf.set) return SRACK_OK;
-    set_error(std::string(who) + ": no filters set: call srack_buses_set_filter first");
-    return SRACK_ERR_STATE;
-}
-
 int srack_buses_set_filter(srack_patch* p, const float* params, const int* port, const int* enabled)
 {
     return guarded([&]() -> int {
-        int rc = busfx_preamble(p, "buses_set_filter");
+        int rc = console_preamble(p, "buses_set_filter");
         if (rc != SRACK_OK) return rc;
         PatchHandle& h = p->h;
-        BusVcf& F = h.busvcf;
+        BusVcf& F = h.console.busvcf;
         const size_t n = h.n_buses;
         for (size_t b = 0; port && b < n; b++)
             if (port[b] < SRACK_VCF_OUT_LOWPASS || port[b] > SRACK_VCF_OUT_HIGHPASS) {
@@ -1230,10 +1203,10 @@ int srack_buses_set_filter(srack_patch* p, const float* params, const int* port,
 int srack_buses_get_filter(const srack_patch* p, float* params, int* port, int* enabled, uint32_t cap)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_get_filter");
+        const int rc = console_preamble(p, "buses_get_filter");
         if (rc != SRACK_OK) return rc;
         const PatchHandle& h = p->h;
-        const BusVcf& F = h.busvcf;
+        const BusVcf& F = h.console.busvcf;
         if (!F.set) return 0;
         const size_t n = std::min<size_t>(cap, h.n_buses);
         if (params && n) std::memcpy(params, F.params.data(), sizeof(float) * n * SRACK_BUS_FILTER_NPARAMS);
@@ -1246,9 +1219,9 @@ int srack_buses_get_filter(const srack_patch* p, float* params, int* port, int* 
 int srack_buses_reset_filter(srack_patch* p)
 {
     return guarded([&]() -> int {
-        int rc = busfx_preamble(p, "buses_reset_filter");
+        int rc = console_preamble(p, "buses_reset_filter");
         if (rc != SRACK_OK) return rc;
-        if ((rc = busvcf_need_set(p, "buses_reset_filter")) != SRACK_OK) return rc;
+        if ((rc = need_set(p->h.console.busvcf.set, "buses_reset_filter", "filters", "filter")) != SRACK_OK) return rc;
         device_busvcf_reset(p->h);
         return SRACK_OK;
     });
@@ -1257,9 +1230,9 @@ int srack_buses_reset_filter(srack_patch* p)
 int srack_buses_filter_state(srack_patch* p, float* state, uint32_t cap)
 {
     return guarded([&]() -> int {
-        int rc = busfx_preamble(p, "buses_filter_state");
+        int rc = console_preamble(p, "buses_filter_state");
         if (rc != SRACK_OK) return rc;
-        if ((rc = busvcf_need_set(p, "buses_filter_state")) != SRACK_OK) return rc;
+        if ((rc = need_set(p->h.console.busvcf.set, "buses_filter_state", "filters", "filter")) != SRACK_OK) return rc;
         if (state && cap && (rc = device_busvcf_state(p->h, state, cap)) != SRACK_OK) return rc;
         return (int)p->h.n_buses;
     });
@@ -1268,26 +1241,18 @@ int srack_buses_filter_state(srack_patch* p, float* state, uint32_t cap)
 int srack_buses_filter(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream)
 {
     return guarded([&]() -> int {
-        int rc = busfx_preamble(p, "buses_filter");
+        int rc = console_preamble(p, "buses_filter");
         if (rc != SRACK_OK) return rc;
-        if ((rc = busvcf_need_set(p, "buses_filter")) != SRACK_OK) return rc;
         PatchHandle& h = p->h;
+        if ((rc = need_set(h.console.busvcf.set, "buses_filter", "filters", "filter")) != SRACK_OK) return rc;
         if (n_samples == 0) return SRACK_OK;
-        if (!d_rows || !d_out) {
-            set_error("buses_filter: d_rows and d_out must be given");
-            return SRACK_ERR_INVALID;
-        }
-        if (row_channels < 1 || row_channels > 8) {
-            set_error("buses_filter: row_channels must be 1 .. 8");
-            return SRACK_ERR_INVALID;
-        }
-        const uintptr_t in0 = (uintptr_t)d_rows, out0 = (uintptr_t)d_out, cv0 = (uintptr_t)d_cv;
+        if ((rc = need_rows("buses_filter", d_rows, d_out, "d_out", row_channels)) != SRACK_OK) return rc;
         const uint64_t bytes = 4ull * h.n_buses * row_channels * n_samples, cv_bytes = 4ull * h.n_buses * n_samples;
-        if (in0 != out0 && in0 < out0 + bytes && out0 < in0 + bytes) {
+        if (d_rows != d_out && meet(d_rows, bytes, d_out, bytes)) {
             set_error("buses_filter: d_out overlaps d_rows in part: it must be d_rows itself or disjoint from it");
             return SRACK_ERR_INVALID;
         }
-        if (d_cv && cv0 < out0 + bytes && out0 < cv0 + cv_bytes) {
+        if (d_cv && meet(d_cv, cv_bytes, d_out, bytes)) {
             set_error("buses_filter: d_cv overlaps d_out");
             return SRACK_ERR_INVALID;
         }
@@ -1298,20 +1263,13 @@ int srack_buses_filter(srack_patch* p, uint32_t n_samples, const float* d_rows, 
 // ---- the bus VCAs ----------------------------------------------------------------------------------------------------
 static const float kBusVcaDefaults[SRACK_BUS_VCA_NPARAMS] = {0.0f, 0.5f, 0.25f, 0.5f};  // ADSRModule::new: a_sec, d_sec, s_val, r_sec
 
-static int busvca_need_set(const srack_patch* p, const char* who)
-{
-    if (p->h.busvca.set) return SRACK_OK;
-    set_error(std::string(who) + ": no VCAs set: call srack_buses_set_vca first");
-    return SRACK_ERR_STATE;
-}
-
 int srack_buses_set_vca(srack_patch* p, const float* params, const int* mode, const int* negative)
 {
     return guarded([&]() -> int {
-        int rc = busfx_preamble(p, "buses_set_vca");
+        int rc = console_preamble(p, "buses_set_vca");
         if (rc != SRACK_OK) return rc;
         PatchHandle& h = p->h;
-        BusVca& F = h.busvca;
+        BusVca& F = h.console.busvca;
         const size_t n = h.n_buses;
         for (size_t b = 0; mode && b < n; b++)
             if (mode[b] < SRACK_BUS_VCA_OFF || mode[b] > SRACK_BUS_VCA_GATE) {
@@ -1342,10 +1300,10 @@ int srack_buses_set_vca(srack_patch* p, const float* params, const int* mode, co
 int srack_buses_get_vca(const srack_patch* p, float* params, int* mode, int* negative, uint32_t cap)
 {
     return guarded([&]() -> int {
-        const int rc = busfx_preamble(p, "buses_get_vca");
+        const int rc = console_preamble(p, "buses_get_vca");
         if (rc != SRACK_OK) return rc;
         const PatchHandle& h = p->h;
-        const BusVca& F = h.busvca;
+        const BusVca& F = h.console.busvca;
         if (!F.set) return 0;
         const size_t n = std::min<size_t>(cap, h.n_buses);
         if (params && n) std::memcpy(params, F.params.data(), sizeof(float) * n * SRACK_BUS_VCA_NPARAMS);
@@ -1358,9 +1316,9 @@ int srack_buses_get_vca(const srack_patch* p, float* params, int* mode, int* neg
 int srack_buses_reset_vca(srack_patch* p)
 {
     return guarded([&]() -> int {
-        int rc = busfx_preamble(p, "buses_reset_vca");
+        int rc = console_preamble(p, "buses_reset_vca");
         if (rc != SRACK_OK) return rc;
-        if ((rc = busvca_need_set(p, "buses_reset_vca")) != SRACK_OK) return rc;
+        if ((rc = need_set(p->h.console.busvca.set, "buses_reset_vca", "VCAs", "vca")) != SRACK_OK) return rc;
         device_busvca_reset(p->h);
         return SRACK_OK;
     });
@@ -1369,9 +1327,9 @@ int srack_buses_reset_vca(srack_patch* p)
 int srack_buses_vca_state(srack_patch* p, float* state, uint32_t cap)
 {
     return guarded([&]() -> int {
-        int rc = busfx_preamble(p, "buses_vca_state");
+        int rc = console_preamble(p, "buses_vca_state");
         if (rc != SRACK_OK) return rc;
-        if ((rc = busvca_need_set(p, "buses_vca_state")) != SRACK_OK) return rc;
+        if ((rc = need_set(p->h.console.busvca.set, "buses_vca_state", "VCAs", "vca")) != SRACK_OK) return rc;
         if (state && cap && (rc = device_busvca_state(p->h, state, cap)) != SRACK_OK) return rc;
         return (int)p->h.n_buses;
     });
@@ -1381,35 +1339,26 @@ int srack_buses_vca(srack_patch* p, uint32_t n_samples, const float* d_rows, uin
                     void* stream)
 {
     return guarded([&]() -> int {
-        int rc = busfx_preamble(p, "buses_vca");
+        int rc = console_preamble(p, "buses_vca");
         if (rc != SRACK_OK) return rc;
-        if ((rc = busvca_need_set(p, "buses_vca")) != SRACK_OK) return rc;
         PatchHandle& h = p->h;
+        if ((rc = need_set(h.console.busvca.set, "buses_vca", "VCAs", "vca")) != SRACK_OK) return rc;
         if (n_samples == 0) return SRACK_OK;
-        if (!d_rows || !d_out) {
-            set_error("buses_vca: d_rows and d_out must be given");
-            return SRACK_ERR_INVALID;
-        }
-        if (row_channels < 1 || row_channels > 8) {
-            set_error("buses_vca: row_channels must be 1 .. 8");
-            return SRACK_ERR_INVALID;
-        }
-        const uintptr_t in0 = (uintptr_t)d_rows, out0 = (uintptr_t)d_out, ctl0 = (uintptr_t)d_ctl, env0 = (uintptr_t)d_env;
+        if ((rc = need_rows("buses_vca", d_rows, d_out, "d_out", row_channels)) != SRACK_OK) return rc;
         const uint64_t bytes = 4ull * h.n_buses * row_channels * n_samples, row_bytes = 4ull * h.n_buses * n_samples;
-        auto meet = [](uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) { return a < b + nb && b < a + na; };
-        if (in0 != out0 && meet(in0, bytes, out0, bytes)) {
+        if (d_rows != d_out && meet(d_rows, bytes, d_out, bytes)) {
             set_error("buses_vca: d_out overlaps d_rows in part: it must be d_rows itself or disjoint from it");
             return SRACK_ERR_INVALID;
         }
-        if (d_ctl && meet(ctl0, row_bytes, out0, bytes)) {
+        if (d_ctl && meet(d_ctl, row_bytes, d_out, bytes)) {
             set_error("buses_vca: d_ctl overlaps d_out");
             return SRACK_ERR_INVALID;
         }
-        if (d_env && (meet(env0, row_bytes, out0, bytes) || meet(env0, row_bytes, in0, bytes))) {
-            set_error(std::string("buses_vca: d_env overlaps ") + (meet(env0, row_bytes, out0, bytes) ? "d_out" : "d_rows"));
+        if (d_env && (meet(d_env, row_bytes, d_out, bytes) || meet(d_env, row_bytes, d_rows, bytes))) {
+            set_error(std::string("buses_vca: d_env overlaps ") + (meet(d_env, row_bytes, d_out, bytes) ? "d_out" : "d_rows"));
             return SRACK_ERR_INVALID;
         }
-        if (d_env && d_ctl && meet(env0, row_bytes, ctl0, row_bytes)) {
+        if (d_env && d_ctl && meet(d_env, row_bytes, d_ctl, row_bytes)) {
             set_error("buses_vca: d_env overlaps d_ctl");
             return SRACK_ERR_INVALID;
         }
@@ -1457,11 +1406,7 @@ int srack_render_info(srack_patch* p, char* buf, size_t cap)
         const char* k = device_kernel_name(p->h);
         // (the kernel's name stays LAST: hosts and tests read it with split("kernel="))
         s += device_bus_note(p->h);
-        s += device_sends_note(p->h);
-        s += device_busvcf_note(p->h);
-        s += device_busvca_note(p->h);
-        s += device_busfx_note(p->h);
-        s += device_master_note(p->h);
+        s += device_console_note(p->h);
         s += device_waves_note(p->h);
         s += device_sequences_note(p->h);
         s += device_jit_note(p->h);
@@ -1637,7 +1582,7 @@ int srack_device_count(int* n)
 int srack_device_set(int device)
 {
     return guarded([&]() -> int {
-        HIP_TRY_C(hipSetDevice(device));
+        HIP_TRY(hipSetDevice(device));
         return SRACK_OK;
     });
 }
@@ -1646,11 +1591,11 @@ int srack_device_get(int* device, char* pci_bus_id, size_t cap)
 {
     return guarded([&]() -> int {
         int dev = -1;
-        HIP_TRY_C(hipGetDevice(&dev));
+        HIP_TRY(hipGetDevice(&dev));
         if (device) *device = dev;
         if (pci_bus_id && cap > 0) {
             pci_bus_id[0] = 0;
-            HIP_TRY_C(hipDeviceGetPCIBusId(pci_bus_id, (int)std::min<size_t>(cap, 1u << 20), dev));
+            HIP_TRY(hipDeviceGetPCIBusId(pci_bus_id, (int)std::min<size_t>(cap, 1u << 20), dev));
         }
         return SRACK_OK;
     });
@@ -1660,9 +1605,9 @@ int srack_device_alloc(void** d_ptr, size_t bytes)
 {
     return guarded([&]() -> int {
         if (!d_ptr) return SRACK_ERR_INVALID;
-        HIP_TRY_C(hipMalloc(d_ptr, bytes));
+        HIP_TRY(hipMalloc(d_ptr, bytes));
 #if defined(SRK_POISON) && SRK_POISON
-        HIP_TRY_C(hipMemset(*d_ptr, 0xff, bytes));
+        HIP_TRY(hipMemset(*d_ptr, 0xff, bytes));
 #endif
         return SRACK_OK;
     });
@@ -1671,7 +1616,7 @@ int srack_device_alloc(void** d_ptr, size_t bytes)
 int srack_device_free(void* d_ptr)
 {
     return guarded([&]() -> int {
-        HIP_TRY_C(hipFree(d_ptr));
+        HIP_TRY(hipFree(d_ptr));
         return SRACK_OK;
     });
 }
@@ -1721,10 +1666,10 @@ struct BouncePool {
         b->device = device;
         auto build = [&]() -> int {
             for (int k = 0; k < 2; k++) {
-                HIP_TRY_C(hipHostMalloc(&b->half[k], kBounceBytes, hipHostMallocDefault));
-                HIP_TRY_C(hipEventCreateWithFlags(&b->done[k], hipEventDisableTiming));
+                HIP_TRY(hipHostMalloc(&b->half[k], kBounceBytes, hipHostMallocDefault));
+                HIP_TRY(hipEventCreateWithFlags(&b->done[k], hipEventDisableTiming));
             }
-            HIP_TRY_C(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
+            HIP_TRY(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
             return SRACK_OK;
         };
         const int rc = build();
@@ -1756,7 +1701,7 @@ BouncePool g_bounce_pool;
 // one slice, through one set: DMA of chunk k + 1 under the memcpy of chunk k
 int bounce_copy(int device, char* dst, const char* src, size_t bytes)
 {
-    HIP_TRY_C(hipSetDevice(device));  // (helper threads start on device 0)
+    HIP_TRY(hipSetDevice(device));  // (helper threads start on device 0)
     BounceSet* b = nullptr;
     int rc = g_bounce_pool.take(device, &b);
     auto run = [&]() -> int {
@@ -1764,15 +1709,15 @@ int bounce_copy(int device, char* dst, const char* src, size_t bytes)
         const size_t n_chunks = (bytes + kBounceBytes - 1) / kBounceBytes;
         auto len = [&](size_t k) { return std::min(kBounceBytes, bytes - k * kBounceBytes); };
         auto issue = [&](size_t k) -> int {
-            HIP_TRY_C(hipMemcpyAsync(b->half[k & 1], src + k * kBounceBytes, len(k), hipMemcpyDeviceToHost, b->st));
-            HIP_TRY_C(hipEventRecord(b->done[k & 1], b->st));
+            HIP_TRY(hipMemcpyAsync(b->half[k & 1], src + k * kBounceBytes, len(k), hipMemcpyDeviceToHost, b->st));
+            HIP_TRY(hipEventRecord(b->done[k & 1], b->st));
             return SRACK_OK;
         };
         int r = issue(0);
         for (size_t k = 0; k < n_chunks && r == SRACK_OK; k++) {
             if (k + 1 < n_chunks) r = issue(k + 1);  // (its half was emptied by the memcpy of chunk k - 1)
             if (r != SRACK_OK) break;
-            HIP_TRY_C(hipEventSynchronize(b->done[k & 1]));
+            HIP_TRY(hipEventSynchronize(b->done[k & 1]));
             std::memcpy(dst + k * kBounceBytes, b->half[k & 1], len(k));
         }
         if (r != SRACK_OK) (void)hipStreamSynchronize(b->st);  // nothing of ours in flight when the set goes back
@@ -1788,8 +1733,8 @@ int srack_device_from_host(void* d_dst, const void* h_src, size_t bytes, void* s
     return guarded([&]() -> int {
         if (bytes == 0) return SRACK_OK;
         if (!d_dst || !h_src) return SRACK_ERR_INVALID;
-        HIP_TRY_C(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
-        HIP_TRY_C(hipStreamSynchronize((hipStream_t)stream));  // the host's memory may be pageable and reused as soon as this returns
+        HIP_TRY(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the host's memory may be pageable and reused as soon as this returns
         return SRACK_OK;
     });
 }
@@ -1800,8 +1745,8 @@ int srack_device_to_host(void* h_dst, const void* d_src, size_t bytes, void* str
         if (bytes == 0) return SRACK_OK;
         if (!h_dst || !d_src) return SRACK_ERR_INVALID;
         int device = 0;
-        HIP_TRY_C(hipGetDevice(&device));
-        HIP_TRY_C(hipStreamSynchronize((hipStream_t)stream));  // what the caller enqueued before the copy
+        HIP_TRY(hipGetDevice(&device));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // what the caller enqueued before the copy
         const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
         const int helpers = (int)std::min<size_t>({(size_t)kMaxHelpers, (size_t)hw, bytes / kSliceMin});
         if (helpers <= 1) return bounce_copy(device, (char*)h_dst, (const char*)d_src, bytes);
@@ -1836,7 +1781,7 @@ int srack_device_to_host(void* h_dst, const void* d_src, size_t bytes, void* str
 int srack_device_sync(void* stream)
 {
     return guarded([&]() -> int {
-        HIP_TRY_C(hipStreamSynchronize((hipStream_t)stream));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
         return SRACK_OK;
     });
 }

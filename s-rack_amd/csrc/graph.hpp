@@ -127,3 +127,14 @@ void set_error(const std::string& msg);
 const char* last_error();
 
 }  // namespace srack
+
+// A HIP runtime call that failed, in a function that returns an SRACK_* code: the call's text and the runtime's words into the error,
+// SRACK_ERR_DEVICE back (render.hip, console.cpp, capi.cpp — units that include the HIP runtime's header)
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess) {                                                                         \
+            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                               \
+            return SRACK_ERR_DEVICE;                                                                    \
+        }                                                                                               \
+    } while (0)

@@ -1,4 +1,4 @@
-// launch.hpp — what render.hip calls to launch the pre-built kernels.  Every kernel family is a translation unit of its own (its kernels
+// launch.hpp — what render.hip and console.cpp call to launch the pre-built kernels.  Every kernel family is a translation unit of its own (its kernels
 // in its own header, its launch functions in <family>.hip), so this header carries only what both sides of that seam need: the
 // launch-side types, the dispatch helpers several families share, and the launch functions' declarations.  No kernel is visible here.
 #pragma once
@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "busfx_args.hpp"
 #include "kernel_args.hip.h"
 #include "launch_types.hpp"
 
@@ -82,6 +83,9 @@ inline size_t interp_lds_bytes(const DevProgram& H)
 void launch_interp(const FlatProgram& P, const KernelArgs& ka, hipStream_t st, bool debug_occ);
 // the control pipeline: one block per control unit, `slots` its argument blocks of this launch
 void launch_interp_stages(bool exact, uint32_t n_stages, size_t lds, const KernelArgs* slots, hipStream_t st);
+
+// ---- the bus reverbs (busfx.hip): a workgroup per bus of a.tab, n_buses of them ----
+void launch_bus_reverb(const BusFxArgs& a, uint32_t n_buses, hipStream_t st);
 
 // ---- the master section (master.hip): run sums into a.runs, the tree over them into a.master, a.stats when given ----
 void launch_master(const MasterArgs& a, hipStream_t st);

@@ -5,8 +5,9 @@
 // never interact).  A wave owns its voices for the whole render because every module is a recurrence in time (phase
 // accumulator, IIR state, envelope state).  The voice kernels are translation units of their own, one per kernel family — the tile
 // interpreter (interp.hip), whole patch shapes in registers (chain*.hip, seq.hip, fm_pair.hip, fm_block.hip) — reached through the
-// launch functions of launch.hpp: this file is the host side and sees none of them.  It keeps the small passes over what they wrote
-// (folds.hip.h: mix-down, statistics, bus folds; busfx.hip.h: the bus reverbs); the per-sample module arithmetic is in modules.hip.h.
+// launch functions of launch.hpp: this file is the host side of a render and sees none of them.  It keeps the small passes over what
+// they wrote (folds.hip.h: mix-down, statistics, bus folds); the per-sample module arithmetic is in modules.hip.h.  What comes behind
+// the mixer — the bus console's stages — has a host side of its own, console.cpp.
 //
 // HBM layout (all voice-minor so that lane == voice gives 256 B contiguous per wave access):
 //   table   u32 [n_rows][V]           state rows, then per-voice parameter rows
@@ -25,9 +26,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "busfx.hip.h"
 #include "folds.hip.h"
-#include "freeverb_params.hpp"
 #include "jit.hpp"
 #include "kernel_args.hip.h"
 #include "launch.hpp"
@@ -39,15 +38,6 @@ namespace srack {
 // ====================================================================================================
 // host side
 // ====================================================================================================
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                               \
-            return SRACK_ERR_DEVICE;                                                                    \
-        }                                                                                               \
-    } while (0)
 
 // Tuning knobs of tools/ (not part of the interface): read once per process and clamped to values the schedule can run with.
 struct Knobs {
@@ -239,11 +229,7 @@ void device_release(DeviceState* d)
 
 PatchHandle::~PatchHandle()
 {
-    device_busfx_drop(*this);
-    device_master_drop(*this);
-    device_sends_drop(*this);
-    device_busvcf_drop(*this);
-    device_busvca_drop(*this);
+    device_console_drop(*this);
     device_release(dev);
     device_release(dev_old);
 }
@@ -1513,680 +1499,6 @@ int device_read_rows(PatchHandle& h, int ctl_stage, int first_row, int n_rows, u
         std::memcpy(host_dst, P.table.data() + (size_t)first_row * V, sizeof(uint32_t) * V * (size_t)n_rows);
     }
     return SRACK_OK;
-}
-
-// ---- the bus reverbs (busfx.hip.h) ------------------------------------------------------------------------------------------------
-// One workgroup per bus.  The state of an enabled bus is allocated on first use and zeroed on the call's stream; the table of the
-// buses (state pointer, derived doubles) is rewritten only after a change of parameters — behind a host-side wait for the last call's
-// kernel, which may still be reading it —, so a tick session of unchanged reverbs is one launch and one event per call.
-static void busfx_wait(BusFx& F)
-{
-    if (F.ev_done) (void)hipEventSynchronize((hipEvent_t)F.ev_done);
-}
-
-void device_busfx_free_bus(PatchHandle& h, uint32_t bus)
-{
-    BusFx& F = h.busfx;
-    if (bus >= F.d_state.size() || !F.d_state[bus]) return;
-    busfx_wait(F);
-    (void)hipFree(F.d_state[bus]);
-    F.d_state[bus] = nullptr;
-    F.tab_dirty = true;
-}
-
-void device_busfx_drop(PatchHandle& h)
-{
-    BusFx& F = h.busfx;
-    busfx_wait(F);
-    for (double* p : F.d_state)
-        if (p) (void)hipFree(p);
-    if (F.d_tab) (void)hipFree(F.d_tab);
-    if (F.ev_done) (void)hipEventDestroy((hipEvent_t)F.ev_done);
-    F = BusFx();
-}
-
-int device_buses_reverb(PatchHandle& h, uint32_t n_samples, const float* d_bus_mix, float* d_bus_fx, void* stream)
-{
-    BusFx& F = h.busfx;
-    const hipStream_t st = (hipStream_t)stream;
-    const uint32_t n_buses = h.n_buses;
-    if (!F.ev_done) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        F.ev_done = e;
-    } else {
-        HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)F.ev_done, 0));  // (calls may come on different streams: the state is one)
-    }
-    const size_t state_bytes = sizeof(double) * ((size_t)kFvStates + F.total);
-    uint32_t n_enabled = 0;
-    for (uint32_t b = 0; b < n_buses; b++) {
-        if (!F.enabled[b]) continue;
-        n_enabled++;
-        if (!F.d_state[b]) {
-            void* p = nullptr;
-            if (hipMalloc(&p, state_bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("buses_reverb: out of device memory for the state of bus " + std::to_string(b) + " (" + std::to_string(state_bytes) + " bytes per enabled bus)");
-                return SRACK_ERR_NOMEM;
-            }
-            F.d_state[b] = (double*)p;
-            F.fresh[b] = 1;
-            F.tab_dirty = true;
-        }
-        if (F.fresh[b]) {  // DelayLine::new is vec![0.0; n], filter_state 0.0
-            HIP_TRY(hipMemsetAsync(F.d_state[b], 0, state_bytes, st));
-            F.fresh[b] = 0;
-        }
-    }
-    if (F.tab_dirty || !F.d_tab) {
-        std::vector<BusFxDev> tab(n_buses);
-        for (uint32_t b = 0; b < n_buses; b++) {
-            tab[b].state = F.enabled[b] ? F.d_state[b] : nullptr;
-            fv_derive(&F.params[(size_t)b * SRACK_FREEVERB__NFIELDS], tab[b].par);
-        }
-        busfx_wait(F);
-        if (F.tab_buses < n_buses) {
-            if (F.d_tab) (void)hipFree(F.d_tab);
-            F.d_tab = nullptr;
-            F.tab_buses = 0;
-            if (hipMalloc(&F.d_tab, sizeof(BusFxDev) * n_buses) != hipSuccess) {
-                (void)hipGetLastError();
-                F.d_tab = nullptr;
-                set_error("buses_reverb: out of device memory for the table of the buses");
-                return SRACK_ERR_NOMEM;
-            }
-            F.tab_buses = n_buses;
-        }
-        HIP_TRY(hipMemcpy(F.d_tab, tab.data(), sizeof(BusFxDev) * n_buses, hipMemcpyHostToDevice));
-        F.tab_dirty = false;
-    }
-    BusFxArgs a;
-    a.in = d_bus_mix;
-    a.out = d_bus_fx;
-    a.tab = (const BusFxDev*)F.d_tab;
-    a.n = n_samples;
-    a.channels = h.graph.cfg.channels;
-    a.block = F.block;
-    for (int j = 0; j < kFvLines; j++) {
-        a.len[j] = F.len[j];
-        a.first[j] = F.first[j];
-        a.pos[j] = (uint32_t)(F.counter % F.len[j]);
-    }
-    hipLaunchKernelGGL(bus_reverb, dim3(n_buses), dim3(kBusFxThreads), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord((hipEvent_t)F.ev_done, st));
-    F.counter += n_samples;
-    F.last_enabled = n_enabled;
-    F.last_block = F.block;
-    F.ran = true;
-    return SRACK_OK;
-}
-
-std::string device_busfx_note(const PatchHandle& h)
-{
-    return h.busfx.ran ? " busfx=" + std::to_string(h.busfx.last_enabled) + "[block " + std::to_string(h.busfx.last_block) + "]" : std::string();
-}
-
-// ---- the master section (master.hip.h, launched through launch_master) -------------------------------------------------------------
-// Gains on the device, uploaded again after a change — behind a host-side wait for the last call's kernels, which may still be reading
-// them —, and the run sums' scratch, grown on demand (the old one freed behind the same wait).  A tick session of unchanged gains and
-// call lengths is the launches and one event per call.
-static void master_wait(Master& M)
-{
-    if (M.ev_done) (void)hipEventSynchronize((hipEvent_t)M.ev_done);
-}
-
-void device_master_gains_changed(PatchHandle& h) { h.master.gain_dirty = true; }
-
-void device_master_drop(PatchHandle& h)
-{
-    Master& M = h.master;
-    master_wait(M);
-    if (M.d_gain) (void)hipFree(M.d_gain);
-    if (M.d_runs) (void)hipFree(M.d_runs);
-    if (M.ev_done) (void)hipEventDestroy((hipEvent_t)M.ev_done);
-    M = Master();
-}
-
-int device_buses_master(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_master, double* d_master_stats, void* stream)
-{
-    Master& M = h.master;
-    const hipStream_t st = (hipStream_t)stream;
-    const uint32_t n_buses = h.n_buses;
-    const uint32_t n_runs = (n_buses + SRACK_MASTER_RUN - 1) / SRACK_MASTER_RUN;
-    if (!M.ev_done) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        M.ev_done = e;
-    } else {
-        HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)M.ev_done, 0));  // (calls may come on different streams: the scratch is one)
-    }
-    const size_t want = (size_t)n_runs * 2 * n_samples;
-    if (M.runs_floats < want) {  // (allocated first, swapped in on success: a failure leaves the earlier scratch)
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(float) * want) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("buses_master: out of device memory for the run sums (" + std::to_string(sizeof(float) * want) + " bytes)");
-            return SRACK_ERR_NOMEM;
-        }
-        master_wait(M);
-        if (M.d_runs) (void)hipFree(M.d_runs);
-        M.d_runs = p;
-        M.runs_floats = want;
-    }
-    if (M.gain_dirty || !M.d_gain) {
-        if (M.gain_buses < n_buses) {
-            void* p = nullptr;
-            if (hipMalloc(&p, sizeof(float) * 2 * n_buses) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("buses_master: out of device memory for the gains");
-                return SRACK_ERR_NOMEM;
-            }
-            master_wait(M);
-            if (M.d_gain) (void)hipFree(M.d_gain);
-            M.d_gain = p;
-            M.gain_buses = n_buses;
-        }
-        master_wait(M);
-        const std::vector<float> ones(M.set ? 0 : (size_t)2 * n_buses, 1.0f);
-        HIP_TRY(hipMemcpy(M.d_gain, M.set ? M.gain.data() : ones.data(), sizeof(float) * 2 * n_buses, hipMemcpyHostToDevice));
-        M.gain_dirty = false;
-    }
-    MasterArgs a;
-    a.rows = d_rows;
-    a.gain = (const float*)M.d_gain;
-    a.runs = (float*)M.d_runs;
-    a.master = d_master;
-    a.stats = d_master_stats;
-    a.n = n_samples;
-    a.n_buses = n_buses;
-    a.row_channels = row_channels;
-    a.used = row_channels < 2 ? row_channels : 2u;
-    launch_master(a, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord((hipEvent_t)M.ev_done, st));
-    M.last_buses = n_buses;
-    M.ran = true;
-    return SRACK_OK;
-}
-
-std::string device_master_note(const PatchHandle& h)
-{
-    if (!h.master.ran) return std::string();
-    const uint32_t n_runs = (h.master.last_buses + SRACK_MASTER_RUN - 1) / SRACK_MASTER_RUN;
-    return " master=" + std::to_string(h.master.last_buses) + "[" + std::to_string(n_runs) + " runs]";
-}
-
-// ---- the bus sends (sends.hip.h, launched through launch_sends) ----------------------------------------------------------------------
-// The tables of the plan on the device in one allocation, uploaded again after a change — behind a host-side wait for the last call's
-// kernels, which may still be reading them —, and the scratch for the run sums of the destinations of several runs, grown on demand
-// (the old one freed behind the same wait).  A tick session of an unchanged list and call lengths is the launches and one event per call.
-static void sends_wait(Sends& S)
-{
-    if (S.ev_done) (void)hipEventSynchronize((hipEvent_t)S.ev_done);
-}
-
-void device_sends_changed(PatchHandle& h) { h.sends.tab_dirty = true; }
-
-void device_sends_drop(PatchHandle& h)
-{
-    Sends& S = h.sends;
-    sends_wait(S);
-    if (S.d_tab) (void)hipFree(S.d_tab);
-    if (S.d_scratch) (void)hipFree(S.d_scratch);
-    if (S.ev_done) (void)hipEventDestroy((hipEvent_t)S.ev_done);
-    S = Sends();
-}
-
-int device_buses_send(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_out, void* stream)
-{
-    Sends& S = h.sends;
-    const hipStream_t st = (hipStream_t)stream;
-    if (!S.ev_done) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        S.ev_done = e;
-    } else {
-        HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)S.ev_done, 0));  // (calls may come on different streams: the scratch is one)
-    }
-    const size_t want = (size_t)S.scratch_rows * 2 * n_samples;
-    if (S.scratch_floats < want) {  // (allocated first, swapped in on success: a failure leaves the earlier scratch)
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(float) * want) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("buses_send: out of device memory for the run sums (" + std::to_string(sizeof(float) * want) + " bytes)");
-            return SRACK_ERR_NOMEM;
-        }
-        sends_wait(S);
-        if (S.d_scratch) (void)hipFree(S.d_scratch);
-        S.d_scratch = p;
-        S.scratch_floats = want;
-    }
-    // the tables side by side, each from a 16-byte boundary
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t at_src = 0, at_gain = up16(at_src + sizeof(uint32_t) * S.term_src.size());
-    const size_t at_runs = up16(at_gain + sizeof(float) * S.term_gain.size()), at_multi = up16(at_runs + sizeof(uint32_t) * S.runs.size());
-    const size_t bytes = up16(at_multi + sizeof(uint32_t) * S.multi.size()) + 16;
-    if (S.tab_dirty || !S.d_tab) {
-        if (S.tab_bytes < bytes) {
-            void* p = nullptr;
-            if (hipMalloc(&p, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("buses_send: out of device memory for the send tables (" + std::to_string(bytes) + " bytes)");
-                return SRACK_ERR_NOMEM;
-            }
-            sends_wait(S);
-            if (S.d_tab) (void)hipFree(S.d_tab);
-            S.d_tab = p;
-            S.tab_bytes = bytes;
-        }
-        sends_wait(S);
-        char* tab = (char*)S.d_tab;
-        HIP_TRY(hipMemcpy(tab + at_src, S.term_src.data(), sizeof(uint32_t) * S.term_src.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(tab + at_gain, S.term_gain.data(), sizeof(float) * S.term_gain.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(tab + at_runs, S.runs.data(), sizeof(uint32_t) * S.runs.size(), hipMemcpyHostToDevice));
-        if (!S.multi.empty()) HIP_TRY(hipMemcpy(tab + at_multi, S.multi.data(), sizeof(uint32_t) * S.multi.size(), hipMemcpyHostToDevice));
-        S.tab_dirty = false;
-    }
-    const char* tab = (const char*)S.d_tab;
-    SendArgs a;
-    a.rows = d_rows;
-    a.out = d_out;
-    a.scratch = (float*)S.d_scratch;
-    a.term_src = (const uint32_t*)(tab + at_src);
-    a.term_gain = (const float*)(tab + at_gain);
-    a.runs = (const SendRun*)(tab + at_runs);
-    a.multi = (const SendMulti*)(tab + at_multi);
-    a.n = n_samples;
-    a.row_channels = row_channels;
-    a.used = row_channels < 2 ? row_channels : 2u;
-    a.n_runs = (uint32_t)(S.runs.size() / 4);
-    a.n_multi = (uint32_t)(S.multi.size() / 4);
-    a.max_blocks = S.max_blocks;
-    launch_sends(a, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord((hipEvent_t)S.ev_done, st));
-    S.last_sends = (uint32_t)S.src.size();
-    S.last_runs = a.n_runs;
-    S.ran = true;
-    return SRACK_OK;
-}
-
-std::string device_sends_note(const PatchHandle& h)
-{
-    return h.sends.ran ? " sends=" + std::to_string(h.sends.last_sends) + "[" + std::to_string(h.sends.last_runs) + " runs]" : std::string();
-}
-
-// ---- the bus filters (busvcf.hip.h, launched through launch_bus_filter) -----------------------------------------------------------------
-// One lane per (enabled bus, used channel) row.  The row table — where each row lies, its state slot, its bus's sliders and port, and
-// the rows of the disabled buses, which an out-of-place call copies — is made again after a change of the setting or of row_channels,
-// behind a host-side wait for the last call's kernels, which may still be reading it.  The state is one allocation, zeroed on the
-// call's stream when it is fresh; after a change of the enabled set it comes up from the host in its new layout (BusVcf::pending).  A
-// tick session of unchanged filters is the launch and one event per call.
-static void busvcf_wait(BusVcf& F)
-{
-    if (F.ev_done) (void)hipEventSynchronize((hipEvent_t)F.ev_done);
-}
-
-static uint32_t busvcf_enabled(const std::vector<uint8_t>& en)
-{
-    uint32_t n = 0;
-    for (uint8_t e : en) n += e != 0;
-    return n;
-}
-
-// The state as it stands, f32 [slots][kBusVcfFields] in the order of F.enabled; `have` false: there is none, every filter is at zero.
-static int busvcf_fetch(BusVcf& F, std::vector<float>& out, bool& have)
-{
-    have = false;
-    if (!F.pending.empty()) {
-        out = F.pending;
-        have = true;
-        return SRACK_OK;
-    }
-    if (!F.d_state || F.fresh) return SRACK_OK;
-    const size_t slots = (size_t)2 * busvcf_enabled(F.enabled);
-    if (slots == 0) return SRACK_OK;
-    busvcf_wait(F);
-    std::vector<float> raw((slots + 63) / 64 * (kBusVcfFields * 64));
-    HIP_TRY(hipMemcpy(raw.data(), F.d_state, sizeof(float) * raw.size(), hipMemcpyDeviceToHost));
-    out.resize(slots * kBusVcfFields);
-    for (size_t sl = 0; sl < slots; sl++)
-        for (int f = 0; f < kBusVcfFields; f++) out[sl * kBusVcfFields + f] = raw[(sl >> 6) * (kBusVcfFields * 64) + (size_t)f * 64 + (sl & 63)];
-    have = true;
-    return SRACK_OK;
-}
-
-void device_busvcf_changed(PatchHandle& h) { h.busvcf.tab_dirty = true; }
-
-void device_busvcf_reset(PatchHandle& h)
-{
-    h.busvcf.pending.clear();
-    h.busvcf.fresh = true;  // zeroed on the next call's stream, before its kernel
-}
-
-int device_busvcf_enable(PatchHandle& h, const std::vector<uint8_t>& enabled)
-{
-    BusVcf& F = h.busvcf;
-    if (!F.set || enabled == F.enabled) return SRACK_OK;
-    std::vector<float> old;
-    bool have = false;
-    const int rc = busvcf_fetch(F, old, have);
-    if (rc != SRACK_OK) return rc;
-    if (!have) return SRACK_OK;  // all zeros, in any layout
-    std::vector<float> now((size_t)2 * busvcf_enabled(enabled) * kBusVcfFields, 0.0f);
-    size_t from = 0, to = 0;
-    for (size_t b = 0; b < enabled.size(); b++) {  // a bus that stays enabled keeps its state; one enabled now starts from zeros; a disabled one drops it
-        if (F.enabled[b] && enabled[b]) std::copy(old.begin() + from, old.begin() + from + 2 * kBusVcfFields, now.begin() + to);
-        if (F.enabled[b]) from += 2 * kBusVcfFields;
-        if (enabled[b]) to += 2 * kBusVcfFields;
-    }
-    F.pending = std::move(now);
-    if (F.pending.empty()) F.fresh = true;
-    return SRACK_OK;
-}
-
-int device_busvcf_state(PatchHandle& h, float* state, uint32_t cap)
-{
-    BusVcf& F = h.busvcf;
-    const size_t n = std::min<size_t>(cap, h.n_buses);
-    std::vector<float> cur;
-    bool have = false;
-    const int rc = busvcf_fetch(F, cur, have);
-    if (rc != SRACK_OK) return rc;
-    std::fill(state, state + n * 2 * kBusVcfFields, 0.0f);
-    size_t from = 0;
-    for (size_t b = 0; have && b < n; b++) {
-        if (!F.enabled[b]) continue;
-        std::copy(cur.begin() + from, cur.begin() + from + 2 * kBusVcfFields, state + b * 2 * kBusVcfFields);
-        from += 2 * kBusVcfFields;
-    }
-    return SRACK_OK;
-}
-
-void device_busvcf_drop(PatchHandle& h)
-{
-    BusVcf& F = h.busvcf;
-    busvcf_wait(F);
-    if (F.d_state) (void)hipFree(F.d_state);
-    if (F.d_tab) (void)hipFree(F.d_tab);
-    if (F.ev_done) (void)hipEventDestroy((hipEvent_t)F.ev_done);
-    F = BusVcf();
-}
-
-int device_buses_filter(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream)
-{
-    BusVcf& F = h.busvcf;
-    const hipStream_t st = (hipStream_t)stream;
-    const uint32_t n_buses = h.n_buses, used = row_channels < 2 ? row_channels : 2u;
-    const uint32_t n_enabled = busvcf_enabled(F.enabled);
-    if (!F.ev_done) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        F.ev_done = e;
-    } else {
-        HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)F.ev_done, 0));  // (calls may come on different streams: the state is one)
-    }
-    // the state: two slots per enabled bus, whole waves of 64
-    const size_t need = ((size_t)2 * n_enabled + 63) / 64 * 64;
-    const size_t state_bytes = sizeof(float) * kBusVcfFields * need;
-    if (F.state_slots < need) {  // (allocated first, swapped in on success: a failure leaves the earlier state, which then is `pending` or nothing)
-        void* p = nullptr;
-        if (hipMalloc(&p, state_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("buses_filter: out of device memory for the filters' state (" + std::to_string(state_bytes) + " bytes)");
-            return SRACK_ERR_NOMEM;
-        }
-        busvcf_wait(F);
-        if (F.d_state) (void)hipFree(F.d_state);
-        F.d_state = p;
-        F.state_slots = need;
-        if (F.pending.empty()) F.fresh = true;
-    }
-    if (!F.pending.empty()) {
-        std::vector<float> raw((size_t)kBusVcfFields * need, 0.0f);
-        const size_t slots = F.pending.size() / kBusVcfFields;
-        for (size_t sl = 0; sl < slots; sl++)
-            for (int f = 0; f < kBusVcfFields; f++) raw[(sl >> 6) * (kBusVcfFields * 64) + (size_t)f * 64 + (sl & 63)] = F.pending[sl * kBusVcfFields + f];
-        busvcf_wait(F);
-        HIP_TRY(hipMemcpy(F.d_state, raw.data(), sizeof(float) * raw.size(), hipMemcpyHostToDevice));
-        F.pending.clear();
-        F.fresh = false;
-    } else if (F.fresh && need) {  // InternalMoogFilterState::default(): all zeros
-        HIP_TRY(hipMemsetAsync(F.d_state, 0, state_bytes, st));
-        F.fresh = false;
-    }
-    if (F.tab_dirty || !F.d_tab || F.tab_row_channels != row_channels) {
-        std::vector<BusVcfRow> rows;
-        std::vector<uint32_t> copy;
-        uint32_t k = 0;
-        for (uint32_t b = 0; b < n_buses; b++) {
-            for (uint32_t c = 0; c < used; c++) {
-                if (!F.enabled[b]) {
-                    copy.push_back(b * row_channels + c);
-                    continue;
-                }
-                BusVcfRow r;
-                r.row = b * row_channels + c;
-                r.bus = b;
-                r.slot = 2 * k + c;
-                r.port = (uint32_t)F.port[b];
-                r.freq = F.params[(size_t)b * SRACK_BUS_FILTER_NPARAMS + SRACK_VCF_FREQ];
-                r.res = F.params[(size_t)b * SRACK_BUS_FILTER_NPARAMS + SRACK_VCF_RES];
-                r.exp_amt = F.params[(size_t)b * SRACK_BUS_FILTER_NPARAMS + SRACK_VCF_EXP_AMT];
-                r.pad = 0;
-                rows.push_back(r);
-            }
-            k += F.enabled[b] != 0;
-        }
-        const size_t at_copy = sizeof(BusVcfRow) * rows.size(), bytes = at_copy + sizeof(uint32_t) * copy.size() + 16;
-        if (F.tab_bytes < bytes) {
-            void* p = nullptr;
-            if (hipMalloc(&p, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("buses_filter: out of device memory for the table of the rows (" + std::to_string(bytes) + " bytes)");
-                return SRACK_ERR_NOMEM;
-            }
-            busvcf_wait(F);
-            if (F.d_tab) (void)hipFree(F.d_tab);
-            F.d_tab = p;
-            F.tab_bytes = bytes;
-        }
-        busvcf_wait(F);
-        if (!rows.empty()) HIP_TRY(hipMemcpy(F.d_tab, rows.data(), at_copy, hipMemcpyHostToDevice));
-        if (!copy.empty()) HIP_TRY(hipMemcpy((char*)F.d_tab + at_copy, copy.data(), sizeof(uint32_t) * copy.size(), hipMemcpyHostToDevice));
-        F.n_rows = (uint32_t)rows.size();
-        F.n_copy = (uint32_t)copy.size();
-        F.tab_row_channels = row_channels;
-        F.tab_dirty = false;
-    }
-    BusVcfArgs a;
-    a.rows = d_rows;
-    a.cv = d_cv;
-    a.out = d_out;
-    a.state = (float*)F.d_state;
-    a.tab = (const BusVcfRow*)F.d_tab;
-    a.copy_rows = (const uint32_t*)((const char*)F.d_tab + sizeof(BusVcfRow) * F.n_rows);
-    a.n = n_samples;
-    a.n_rows = F.n_rows;
-    a.n_copy = F.n_copy;
-    a.used = used;
-    launch_bus_filter(a, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord((hipEvent_t)F.ev_done, st));
-    F.last_enabled = n_enabled;
-    F.last_waves = (F.n_rows + 63) / 64;
-    F.ran = true;
-    return SRACK_OK;
-}
-
-std::string device_busvcf_note(const PatchHandle& h)
-{
-    return h.busvcf.ran ? " busvcf=" + std::to_string(h.busvcf.last_enabled) + "[" + std::to_string(h.busvcf.last_waves) + " waves]" : std::string();
-}
-
-// ---- the bus VCAs (busvca.hip.h, launched through launch_bus_vca) -------------------------------------------------------------------------
-// A table entry and six state values per bus, in bus order: nothing is compacted, so a change of modes moves nothing.  The table goes
-// up again after a change of the setting, the state after a change of the set of GATE buses or a reset — both behind a host-side wait
-// for the last call's kernel, which may still be using them.  A tick session of unchanged VCAs is the launch and one event per call.
-static void busvca_wait(BusVca& F)
-{
-    if (F.ev_done) (void)hipEventSynchronize((hipEvent_t)F.ev_done);
-}
-
-// ADSRModule::new's state, f32 [6][n]: phase 0, mode None, r_val 0, from_a_val 0, the rate, TransitionDetector.last true
-static std::vector<float> busvca_fresh(const BusVca& F, size_t n)
-{
-    const float one[kBusVcaFields] = {0.0f, (float)SRACK_ADSR_MODE_NONE, 0.0f, 0.0f, F.rate, 1.0f};
-    std::vector<float> s((size_t)kBusVcaFields * n);
-    for (int f = 0; f < kBusVcaFields; f++) std::fill(s.begin() + (size_t)f * n, s.begin() + (size_t)(f + 1) * n, one[f]);
-    return s;
-}
-
-static bool busvca_all_fresh(const BusVca& F) { return F.pending.empty() && (!F.d_state || F.fresh); }
-
-// The state as it stands, f32 [6][n]
-static int busvca_fetch(BusVca& F, size_t n, std::vector<float>& out)
-{
-    if (!F.pending.empty()) {
-        out = F.pending;
-        return SRACK_OK;
-    }
-    out = busvca_fresh(F, n);
-    if (busvca_all_fresh(F)) return SRACK_OK;
-    busvca_wait(F);
-    HIP_TRY(hipMemcpy(out.data(), F.d_state, sizeof(float) * out.size(), hipMemcpyDeviceToHost));
-    return SRACK_OK;
-}
-
-void device_busvca_changed(PatchHandle& h) { h.busvca.tab_dirty = true; }
-
-void device_busvca_reset(PatchHandle& h)
-{
-    h.busvca.pending.clear();
-    h.busvca.fresh = true;  // uploaded before the next call's kernel
-}
-
-int device_busvca_modes(PatchHandle& h, const std::vector<int32_t>& mode)
-{
-    BusVca& F = h.busvca;
-    if (!F.set || busvca_all_fresh(F)) return SRACK_OK;  // fresh stays fresh
-    const size_t n = h.n_buses;
-    bool moved = false;
-    for (size_t b = 0; b < n; b++) moved = moved || ((F.mode[b] == SRACK_BUS_VCA_GATE) != (mode[b] == SRACK_BUS_VCA_GATE));
-    if (!moved) return SRACK_OK;
-    std::vector<float> cur;
-    const int rc = busvca_fetch(F, n, cur);
-    if (rc != SRACK_OK) return rc;
-    const std::vector<float> fresh = busvca_fresh(F, 1);
-    for (size_t b = 0; b < n; b++)  // a bus that stays GATE keeps its state; one that becomes GATE starts fresh; one that leaves drops it
-        if (F.mode[b] != SRACK_BUS_VCA_GATE || mode[b] != SRACK_BUS_VCA_GATE)
-            for (int f = 0; f < kBusVcaFields; f++) cur[(size_t)f * n + b] = fresh[f];
-    F.pending = std::move(cur);
-    return SRACK_OK;
-}
-
-int device_busvca_state(PatchHandle& h, float* state, uint32_t cap)
-{
-    BusVca& F = h.busvca;
-    const size_t n_buses = h.n_buses, n = std::min<size_t>(cap, n_buses);
-    std::vector<float> cur;
-    const int rc = busvca_fetch(F, n_buses, cur);
-    if (rc != SRACK_OK) return rc;
-    const std::vector<float> fresh = busvca_fresh(F, 1);
-    for (size_t b = 0; b < n; b++)
-        for (int f = 0; f < kBusVcaFields; f++) state[b * kBusVcaFields + f] = F.mode[b] == SRACK_BUS_VCA_GATE ? cur[(size_t)f * n_buses + b] : fresh[f];
-    return SRACK_OK;
-}
-
-void device_busvca_drop(PatchHandle& h)
-{
-    BusVca& F = h.busvca;
-    busvca_wait(F);
-    if (F.d_state) (void)hipFree(F.d_state);
-    if (F.d_tab) (void)hipFree(F.d_tab);
-    if (F.ev_done) (void)hipEventDestroy((hipEvent_t)F.ev_done);
-    F = BusVca();
-}
-
-int device_buses_vca(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_ctl, float* d_out, float* d_env, void* stream)
-{
-    BusVca& F = h.busvca;
-    const hipStream_t st = (hipStream_t)stream;
-    const uint32_t n_buses = h.n_buses;
-    if (!F.ev_done) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        F.ev_done = e;
-    } else {
-        HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)F.ev_done, 0));  // (calls may come on different streams: the state is one)
-    }
-    const size_t state_bytes = sizeof(float) * kBusVcaFields * n_buses, tab_bytes = sizeof(BusVcaBus) * n_buses;
-    if (!F.d_state || !F.d_tab) {  // (n_buses is fixed while the VCAs live: another n_buses drops them)
-        void *ps = nullptr, *pt = nullptr;
-        if (hipMalloc(&ps, state_bytes) != hipSuccess || hipMalloc(&pt, tab_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            if (ps) (void)hipFree(ps);
-            set_error("buses_vca: out of device memory for the VCAs' state and table (" + std::to_string(state_bytes + tab_bytes) + " bytes)");
-            return SRACK_ERR_NOMEM;
-        }
-        F.d_state = ps;
-        F.d_tab = pt;
-        F.tab_dirty = true;
-        if (F.pending.empty()) F.fresh = true;
-    }
-    if (!F.pending.empty() || F.fresh) {
-        const std::vector<float> up = F.pending.empty() ? busvca_fresh(F, n_buses) : F.pending;
-        busvca_wait(F);
-        HIP_TRY(hipMemcpy(F.d_state, up.data(), state_bytes, hipMemcpyHostToDevice));
-        F.pending.clear();
-        F.fresh = false;
-    }
-    uint32_t n_on = 0, n_gated = 0;
-    for (uint32_t b = 0; b < n_buses; b++) {
-        n_on += F.mode[b] != SRACK_BUS_VCA_OFF;
-        n_gated += F.mode[b] == SRACK_BUS_VCA_GATE;
-    }
-    if (F.tab_dirty) {
-        std::vector<BusVcaBus> tab(n_buses);
-        for (uint32_t b = 0; b < n_buses; b++) {
-            BusVcaBus& r = tab[b];
-            r.a_sec = F.params[(size_t)b * SRACK_BUS_VCA_NPARAMS + SRACK_ADSR_A_SEC];
-            r.d_sec = F.params[(size_t)b * SRACK_BUS_VCA_NPARAMS + SRACK_ADSR_D_SEC];
-            r.s_val = F.params[(size_t)b * SRACK_BUS_VCA_NPARAMS + SRACK_ADSR_S_VAL];
-            r.r_sec = F.params[(size_t)b * SRACK_BUS_VCA_NPARAMS + SRACK_ADSR_R_SEC];
-            r.mode = (uint32_t)F.mode[b];
-            r.negative = F.negative[b];
-            r.pad[0] = r.pad[1] = 0;
-        }
-        busvca_wait(F);
-        HIP_TRY(hipMemcpy(F.d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice));
-        F.tab_dirty = false;
-    }
-    BusVcaArgs a;
-    a.rows = d_rows;
-    a.ctl = d_ctl;
-    a.out = d_out;
-    a.env = d_env;
-    a.state = (float*)F.d_state;
-    a.tab = (const BusVcaBus*)F.d_tab;
-    a.rate = F.rate;
-    a.n = n_samples;
-    a.n_buses = n_buses;
-    a.row_channels = row_channels;
-    a.used = row_channels < 2 ? row_channels : 2u;
-    launch_bus_vca(a, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord((hipEvent_t)F.ev_done, st));
-    F.last_on = n_on;
-    F.last_gated = n_gated;
-    F.ran = true;
-    return SRACK_OK;
-}
-
-std::string device_busvca_note(const PatchHandle& h)
-{
-    return h.busvca.ran ? " busvca=" + std::to_string(h.busvca.last_on) + "[" + std::to_string(h.busvca.last_gated) + " gated]" : std::string();
 }
 
 const char* device_kernel_name(const PatchHandle& h) { return h.dev ? h.dev->kernel_name : ""; }

@@ -4,7 +4,7 @@ to.  The criterion is BIT EQUALITY of every intermediate (NaN matching NaN), der
 for that stage, and a stage's output is the next one's input word for word.  No tolerance anywhere in this file.  The guards that make
 the reference worth comparing with are asserted in tests/test_console_host.py, with their figures.
 
-Part one (tests 1-4) runs in process on the null stream, the way the stages' own files do.  Part two compares arrays which
+Part one (tests 1-5) runs in process on the null stream, the way the stages' own files do.  Part two compares arrays which
 tests/console_stream_driver.py wrote in a process of its own (torch must start HIP before the library loads: INTEGRATION.md section 3):
 the same chain on the caller's streams, nothing synchronised, with settings edited, state read back, streams destroyed and tables
 replaced while the previous calls are provably still waiting behind a stalled stream.  What is held there is the stream contract of
@@ -190,6 +190,56 @@ def test_from_the_voices(S):
     got = run_chain(S, p, rows, ctl[:, :T], [T], render=lambda n, d_rows: p.render_buses_raw(n, d_rows))
     assert_same_console(got, ref, "render_buses, then the console")
     assert "buses=70[fold]" in p.info() and " master=70[2 runs]" in p.info(), p.info()
+
+
+# ---- 5. the five stages go with the mix table: another n_buses, srack_voices_configure -----------------------------------------------------------
+NOTES = (" sends=", " busvcf=", " busvca=", " busfx=", " master=")
+
+
+def notes_of(p, s):
+    """what srack_render_info says of the console once every stage has run with the settings s, the filters and the master on two channels"""
+    runs = int(((1 + np.bincount(s.send_dst, minlength=s.n_buses) + 63) // 64).sum())
+    vcf = int(np.count_nonzero(s.vcf_enabled))
+    return (f" sends={len(s.send_src)}[{runs} runs] busvcf={vcf}[{(2 * vcf + 63) // 64} waves] busvca={int(np.count_nonzero(s.vca_mode != 0))}"
+            f"[{int(np.count_nonzero(s.vca_mode == 2))} gated] busfx={int(np.count_nonzero(s.rv_enabled))}[block {p.bus_reverb_plan()[1]}]"
+            f" master={s.n_buses}[{(s.n_buses + 63) // 64} runs]")
+
+
+def nothing_set(p):
+    return (p.get_sends() is None and p.get_bus_reverbs()[0] == 0 and p.get_bus_vca()[0] == 0 and p.get_bus_filter()[0] == 0 and p.get_master() is None
+            and not any(t in p.info() for t in NOTES))
+
+
+# (130 samples: two tiles of 64 and a tail of 2.  2 kHz: the reverb's lines are 10 .. 74 slots, so its tail is in the state that must go)
+@pytest.mark.parametrize("how,first,second", [("another n_buses", (3, 2, 130, CR.SEED3 + 23, 1, 2000), (5, 2, 130, CR.SEED3 + 3, 2, 2000)),
+                                              ("configure_voices", (3, 2, 66, CR.SEED3 + 10, 1, 2000), None)], ids=["another n_buses", "configure_voices"])
+def test_the_stages_go_with_the_table(S, how, first, second):
+    """One handle: the chain, then the table goes (srack_voices_set_buses with another n_buses; srack_voices_configure) and every stage
+    with it, then all five set again and the chain again — both runs held to the reference FROM FRESH STATE.
+    The guard, on the reference alone: had the first run's state stayed, a second run of the same rows would differ from the fresh one on
+    more than 1/16 of the reverbs', the envelopes' and the filters' samples (the seeds are chosen for it: 0.33, 0.22, 0.67 of them for
+    the 130 samples, 0.33, 0.31, 0.67 for the 66; one bus in three has a reverb, one is gated)."""
+    rows, ctl, s, ref, states, _ = reference(*first)
+    T = rows.shape[2]
+    carried, _, _ = CR.render(rows, ctl, s, [T], state=states[-1])
+    assert np.abs(ref["master"]).max() > 1e-3 and np.count_nonzero(ref["master"]) > T // 2, "the master is (nearly) silent"
+    assert all(CR.fraction_differing(carried[k], ref[k]) > 1 / 16 for k in ("fx", "env", "vcf")), "state that stayed is meant to show in the second run"
+    p = CR.host(S, s)
+    assert_same_console(run_chain(S, p, rows, ctl, [T]), ref, f"{how}: the first run")
+    assert notes_of(p, s) in p.info(), p.info()
+    if how == "another n_buses":
+        p.set_buses(second[0])
+        rows, ctl, s, ref, states, _ = reference(*second)
+    else:
+        p.configure_voices(1)
+        assert not any(t in p.info() for t in NOTES), p.info()
+        p.set_buses(s.n_buses)
+    assert nothing_set(p), p.info()
+    CR.push_all(p, s)
+    assert_same_console(run_chain(S, p, rows, ctl, [T]), ref, f"{how}: the second run")
+    assert_same_bits(p.bus_vca_state(), states[-1].vca, "the VCAs' state")
+    assert_same_bits(p.bus_filter_state(), states[-1].vcf, "the filters' state")
+    assert notes_of(p, s) in p.info(), p.info()
 
 
 # ---- part two: the caller's streams (tests/console_stream_driver.py) ------------------------------------------------------------------------------

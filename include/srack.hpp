@@ -263,6 +263,17 @@ public:
     {
         check(srack_buses_vca(p_, n_samples, d_rows, row_channels, d_ctl, d_out, d_env, stream));
     }
+    // A drive, a waveshaper and a make-up gain per mix bus, behind the mixer: params f32 [n_buses][SRACK_BUS_SHAPER_NPARAMS] = pre, exponent,
+    // post (any f32; nullptr: 1, 1, 1), mode [n_buses] SRACK_BUS_SHAPER_* (nullptr: every bus CONST).  sign(a) |a|^e with the host libm's powf,
+    // bit for bit.  Calling set_bus_shaper again is the slider; there is no state.  Not part of the program.
+    void set_bus_shaper(const float* params = nullptr, const int* mode = nullptr) { check(srack_buses_set_shaper(p_, params, mode)); }
+    uint32_t get_bus_shaper(float* params = nullptr, int* mode = nullptr, uint32_t cap = 0) const { return (uint32_t)check(srack_buses_get_shaper(p_, params, mode, cap)); }
+    // d_rows f32 [n_buses][row_channels][n_samples] -> d_out of the same shape: d_rows itself (in place) or disjoint; d_cv f32
+    // [n_buses][n_samples], the exponent of a CV bus sample by sample, or null (its EXPONENT then).  Asynchronous on `stream`.
+    void bus_shaper(uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream = nullptr)
+    {
+        check(srack_buses_shaper(p_, n_samples, d_rows, row_channels, d_cv, d_out, stream));
+    }
     // execute_batch plus d_bus_mix, f32 [n_buses][channels][n_samples] (written); d_frames, d_mix, d_stats may each be null
     void execute_batch_buses(uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags = 0, void* stream = nullptr)
     {

@@ -717,6 +717,53 @@ int srack_buses_vca_state(srack_patch* p, float* state /* host, f32 [n_buses][SR
 int srack_buses_vca(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels,
                     const float* d_ctl, float* d_out, float* d_env, void* stream);
 
+/* ---- the bus shapers: a drive, a waveshaper and a make-up gain per mix bus, behind the mixer ---------------------------------------
+ * The non-linearity of a strip: saturating a drum group, expanding an aux bus, riding the curve from an automation row.  A shaper on
+ * the sum is not the sum of shapers, so no patch can stand in for it.  Channel c in {0, 1} of a bus that is not OFF is three reference
+ * modules in series, ticked once per sample:
+ *   MathModule(Multiply)   In1 = d_rows[b][c][t], In2 unconnected, constant = PRE
+ *   NonLinearModule        (math.rs:203-205, 292-311) In1 = that product: a > 0 ? a.powf(e) : -(-a).powf(e).  The exponent e is
+ *                          d_cv[b][t] when the bus is SRACK_BUS_SHAPER_CV and d_cv is given (In2 connected); otherwise In2 is unconnected
+ *                          and e is EXPONENT (the module's (Some, None) arm) — for a CONST bus always.
+ *   MathModule(Multiply)   by POST, written to d_out[b][c][t]
+ * The two products are IEEE f32, one rounding each, no fma.  The power is the HOST libm's powf (Rust's f32::powf is glibc's), operation
+ * for operation and misroundings included — never a correctly rounded power, never the device library's — in every render mode.  A
+ * sample that is not > 0 takes the second arm: both zeros and NaN do (+0.0 with exponent -1 is -(-0.0).powf(-1) = +inf, -0.0 gives -inf).  ANY f32 parameter is accepted;
+ * a non-finite sample, CV value or parameter affects that bus's rows and no other.  There is no state: no reset call, no state call, and
+ * the result cannot depend on how the samples are cut into calls.
+ *
+ * params: f32 [n_buses][SRACK_BUS_SHAPER_NPARAMS] = PRE, EXPONENT, POST; NULL = 1, 1, 1
+ * mode:   int [n_buses], SRACK_BUS_SHAPER_*; NULL = every bus CONST
+ * Both are host memory.  A mode outside 0..2 is SRACK_ERR_INVALID and leaves the earlier setting in place.  get_shaper copies up to cap
+ * buses (any pointer may be NULL) and returns n_buses, or 0 when no shapers are set.
+ * Lifecycle (the VCAs' rules): the shapers belong to the handle, NOT to the patch's program: setting, changing or running them does not
+ * re-flatten, restarts nothing, changes no bit of any other output; they survive an edit that re-flattens the patch.
+ * srack_voices_configure drops them; so does srack_voices_set_buses with another n_buses (the same n_buses keeps them).  Rack files
+ * carry nothing of this.
+ *
+ * The call:
+ *   d_rows : device, f32 [n_buses][row_channels][n_samples], as for srack_buses_vca.  1 <= row_channels <= 8; channels 0 and 1 are
+ *            processed, channels beyond the second are neither read nor written.
+ *   d_cv   : device, f32 [n_buses][n_samples], or NULL; one row per bus, shared by its channels.  Must not overlap d_out.
+ *   d_out  : device, the shape of d_rows, written: d_rows itself (in place) or disjoint from it.  An OFF bus's channels 0 and 1 are
+ *            copied as 32-bit words; in place they are left alone (no work is launched for them).
+ *   Any 4-byte aligned address is accepted for all three.
+ *   stream : as for srack_render: asynchronous, and the library touches the stream only during the call.
+ * Errors, in this order: SRACK_ERR_INVALID for a null handle; SRACK_ERR_STATE before srack_voices_configure or before a mix table
+ * exists (all three calls); SRACK_ERR_STATE for srack_buses_shaper before set_shaper; n_samples == 0 is SRACK_OK and touches nothing;
+ * SRACK_ERR_INVALID for a null d_rows or d_out, row_channels outside 1..8 or an overlap as above; SRACK_ERR_NOMEM if the table cannot
+ * be allocated, the earlier table kept.
+ * The kernel is a streaming pass, lanes on time: a wave takes 1024 samples of one bus and both its channels, several loads in flight,
+ * the libm's tables in LDS (csrc/busshape.hip.h).  srack_render_info says " busshp=<buses not OFF>[<CV buses> cv]" between " busvca="
+ * and " busfx=" once a call has run. */
+#define SRACK_BUS_SHAPER_NPARAMS 3
+enum { SRACK_BUS_SHAPER_PRE = 0, SRACK_BUS_SHAPER_EXPONENT = 1, SRACK_BUS_SHAPER_POST = 2 };
+enum { SRACK_BUS_SHAPER_OFF = 0, SRACK_BUS_SHAPER_CONST = 1, SRACK_BUS_SHAPER_CV = 2 };
+int srack_buses_set_shaper(srack_patch* p, const float* params, const int* mode);
+int srack_buses_get_shaper(const srack_patch* p, float* params, int* mode, uint32_t cap);
+int srack_buses_shaper(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels,
+                       const float* d_cv, float* d_out, void* stream);
+
 /* Optional: do everything a later srack_render(p, <= n_samples, ..., flags) would do on first use — flatten the graph,
  * upload the programs and the voice table, size the scratch buffers (mix partials when want_mix, control tracks) — so
  * that the first render costs what every render costs.  Renders nothing and leaves the voice state untouched. */

@@ -90,6 +90,9 @@ mod ffi {
         pub fn srack_buses_reset_vca(p: *mut SrackPatch) -> c_int;
         pub fn srack_buses_vca_state(p: *mut SrackPatch, state: *mut f32, cap: u32) -> c_int;
         pub fn srack_buses_vca(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_ctl: *const f32, d_out: *mut f32, d_env: *mut f32, stream: *mut c_void) -> c_int;
+        pub fn srack_buses_set_shaper(p: *mut SrackPatch, params: *const f32, mode: *const c_int) -> c_int;
+        pub fn srack_buses_get_shaper(p: *const SrackPatch, params: *mut f32, mode: *mut c_int, cap: u32) -> c_int;
+        pub fn srack_buses_shaper(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_cv: *const f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
         pub fn srack_device_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
         pub fn srack_device_free(d_ptr: *mut c_void) -> c_int;
         pub fn srack_device_to_host(h_dst: *mut c_void, d_src: *const c_void, bytes: usize, stream: *mut c_void) -> c_int;
@@ -577,6 +580,33 @@ impl Patch {
         let o = out.map_or(rows.as_f32(), |b| b.as_f32());
         let e = env.map_or(std::ptr::null_mut(), |b| b.as_f32());
         check(unsafe { ffi::srack_buses_vca(self.raw, n_samples, rows.as_f32() as *const f32, row_channels, c, o, e, std::ptr::null_mut()) }).map(|_| ())
+    }
+    /// A drive, a waveshaper and a make-up gain per mix bus, behind the mixer (`srack_buses_set_shaper`): `params` is `[n_buses][3]` f32 —
+    /// pre, exponent, post, any f32; None: 1, 1, 1 —, `mode` `[n_buses]` 0 off, 1 the exponent is the constant, 2 it is the bus's CV row
+    /// (None: every bus constant).  `sign(a) |a|^e` with the host libm's `powf`, bit for bit.  Calling it again is the slider; there is no
+    /// state.  Not part of the program: restarts nothing.
+    pub fn set_bus_shaper(&mut self, params: Option<&[f32]>, mode: Option<&[i32]>) -> Result<(), Error> {
+        let a = params.map_or(std::ptr::null(), |x| x.as_ptr());
+        let m = mode.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        check(unsafe { ffi::srack_buses_set_shaper(self.raw, a, m) }).map(|_| ())
+    }
+    /// `(params [n_buses][3], mode [n_buses])` of the shapers set; None when none are.
+    pub fn get_bus_shaper(&self) -> Result<Option<(Vec<f32>, Vec<i32>)>, Error> {
+        let n = check(unsafe { ffi::srack_buses_get_shaper(self.raw, std::ptr::null_mut(), std::ptr::null_mut(), 0) })? as usize;
+        if n == 0 {
+            return Ok(None);
+        }
+        let (mut a, mut m) = (vec![0f32; n * 3], vec![0 as c_int; n]);
+        check(unsafe { ffi::srack_buses_get_shaper(self.raw, a.as_mut_ptr(), m.as_mut_ptr(), n as u32) })?;
+        Ok(Some((a, m)))
+    }
+    /// The bus rows through their shapers (`srack_buses_shaper`): `rows` `[n_buses][row_channels][n_samples]` f32 in, `cv`
+    /// `[n_buses][n_samples]` f32 the exponent of a CV bus sample by sample (None: its constant), `out` of the shape of `rows` written —
+    /// None: in place.  Channels 0 and 1 are processed; a bus that is off passes word for word.
+    pub fn bus_shaper(&mut self, n_samples: u32, rows: &DeviceBuffer, row_channels: u32, cv: Option<&DeviceBuffer>, out: Option<&DeviceBuffer>) -> Result<(), Error> {
+        let c = cv.map_or(std::ptr::null(), |b| b.as_f32() as *const f32);
+        let o = out.map_or(rows.as_f32(), |b| b.as_f32());
+        check(unsafe { ffi::srack_buses_shaper(self.raw, n_samples, rows.as_f32() as *const f32, row_channels, c, o, std::ptr::null_mut()) }).map(|_| ())
     }
 }
 

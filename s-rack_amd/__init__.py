@@ -25,6 +25,10 @@ BUS_FILTER_DEFAULTS = (0.2, 0.5, 0.5)  # MoogFilterModule's three sliders: what 
 BUS_VCA_NPARAMS, BUS_VCA_NSTATE = 4, 6  # srack_buses_set_vca: ADSR_A_SEC .. ADSR_R_SEC per bus; srack_buses_vca_state: ADSR_PHASE .. ADSR_GATE_LAST per bus
 BUS_VCA_OFF, BUS_VCA_CV, BUS_VCA_GATE = 0, 1, 2  # a bus's mode: it passes; its control row is the VCAs' CV; it is the gate of the bus's ADSR
 BUS_VCA_DEFAULTS = (0.0, 0.5, 0.25, 0.5)  # ADSRModule's four sliders: what set_bus_vca(None) gives every bus
+BUS_SHAPER_NPARAMS = 3  # srack_buses_set_shaper: PRE, EXPONENT, POST per bus
+BUS_SHAPER_PRE, BUS_SHAPER_EXPONENT, BUS_SHAPER_POST = 0, 1, 2
+BUS_SHAPER_OFF, BUS_SHAPER_CONST, BUS_SHAPER_CV = 0, 1, 2  # a bus's mode: it passes; the exponent is EXPONENT; the exponent is the bus's CV row
+BUS_SHAPER_DEFAULTS = (1.0, 1.0, 1.0)  # drive, exponent, make-up gain: what set_bus_shaper(None) gives every bus
 ADSR_MODE_ATTACK, ADSR_MODE_DECAY, ADSR_MODE_SUSTAIN, ADSR_MODE_RELEASE, ADSR_MODE_NONE = 0, 1, 2, 3, 4  # the values of ADSR_MODE
 FREEVERB_DEFAULTS = (0.5, 0.0, 1.0, 0.5, 0.5, 0.0)  # FreeverbModule's six parameters in field order: what set_bus_reverbs(None) gives every bus
 WAVE_OWN = -1
@@ -46,6 +50,7 @@ ABI_SYMBOLS = [
     "srack_buses_set_sends", "srack_buses_get_sends", "srack_buses_send_plan", "srack_buses_send",
     "srack_buses_set_filter", "srack_buses_get_filter", "srack_buses_reset_filter", "srack_buses_filter_state", "srack_buses_filter",
     "srack_buses_set_vca", "srack_buses_get_vca", "srack_buses_reset_vca", "srack_buses_vca_state", "srack_buses_vca",
+    "srack_buses_set_shaper", "srack_buses_get_shaper", "srack_buses_shaper",
     "srack_patch_set_wave_bank", "srack_patch_get_wave_bank", "srack_patch_get_wave_bank_samples", "srack_voices_set_waves", "srack_voices_get_waves",
     "srack_patch_set_sequence_bank", "srack_patch_get_sequence_bank", "srack_voices_set_sequences", "srack_voices_get_sequences",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
@@ -144,6 +149,10 @@ def _load():
         L.srack_buses_reset_vca.argtypes = [vp]
         L.srack_buses_vca_state.argtypes = [vp, fp, u32]
         L.srack_buses_vca.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
+    if hasattr(L, "srack_buses_shaper"):
+        L.srack_buses_set_shaper.argtypes = [vp, fp, ip]
+        L.srack_buses_get_shaper.argtypes = [vp, fp, ip, u32]
+        L.srack_buses_shaper.argtypes = [vp, u32, vp, u32, vp, vp, vp]
     if hasattr(L, "srack_voices_set_waves"):  # (tools/ alternate older builds of the library under this binding)
         L.srack_patch_set_wave_bank.argtypes = [vp, i32, fp, ip, fp, u32]
         L.srack_patch_get_wave_bank.argtypes = [vp, i32, ip, fp, u32]
@@ -878,6 +887,73 @@ class Patch:
             return (out, env) if want_env else out
         finally:
             for d in (d_in, d_out, d_ctl, d_env):
+                if d.value:
+                    lib.srack_device_free(d)
+
+    # ---- bus shapers: a drive, a waveshaper and a make-up gain per mix bus, behind the mixer ----------------
+    def set_bus_shaper(self, params=None, mode=None):
+        """srack_buses_set_shaper: params f32 [n_buses][3] = PRE, EXPONENT, POST, any f32 (None: 1, 1, 1), mode int [n_buses]
+        BUS_SHAPER_OFF / _CONST / _CV (None: every bus CONST).  Calling it again is the slider; there is no state.  Not part of the
+        program: restarts nothing."""
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        a = mo = None
+        if params is not None:
+            a = np.ascontiguousarray(params, dtype=np.float32)
+            assert a.shape == (n_buses, BUS_SHAPER_NPARAMS), a.shape
+        if mode is not None:
+            mo = np.ascontiguousarray(mode, dtype=np.intc)
+            assert mo.shape == (n_buses,), mo.shape
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        _check(lib.srack_buses_set_shaper(self.h, None if a is None else a.ctypes.data_as(fp), None if mo is None else mo.ctypes.data_as(ip)))
+
+    def get_bus_shaper(self):
+        """-> (n_buses, params f32 [n_buses][3], mode int32 [n_buses]); (0, None, None) when no shapers are set"""
+        n = _check(lib.srack_buses_get_shaper(self.h, None, None, 0))
+        if n == 0:
+            return 0, None, None
+        a, mo = np.empty((n, BUS_SHAPER_NPARAMS), dtype=np.float32), np.empty(n, dtype=np.intc)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        _check(lib.srack_buses_get_shaper(self.h, a.ctypes.data_as(fp), mo.ctypes.data_as(ip), n))
+        return n, a, mo
+
+    def bus_shaper_raw(self, n_samples, d_rows, row_channels, d_cv, d_out, stream=None):
+        """Device pointers in; asynchronous on `stream` (srack_buses_shaper): d_rows and d_out f32 [n_buses][row_channels][n] (d_out may be
+        d_rows), d_cv f32 [n_buses][n] or None."""
+        _check(lib.srack_buses_shaper(self.h, n_samples, d_rows, row_channels, d_cv, d_out, stream))
+
+    def bus_shaper(self, rows, cv=None, in_place=False):
+        """Convenience for tests: rows f32 [n_buses][row_channels][T] (and cv f32 [n_buses][T]) from the host through the shapers -> f32 of
+        the shape of rows.  Out of place the output buffer starts as zeros, which is what channels beyond the second come back as; in
+        place they come back as they went in."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
+        c = None
+        if cv is not None:
+            c = np.ascontiguousarray(cv, dtype=np.float32)
+            assert c.shape == (n_buses, x.shape[2]), c.shape
+        out = np.zeros_like(x)
+        d_in, d_out, d_cv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        try:
+            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
+            if not in_place:
+                _check(lib.srack_device_alloc(C.byref(d_out), max(4, out.nbytes)))
+            if c is not None:
+                _check(lib.srack_device_alloc(C.byref(d_cv), max(4, c.nbytes)))
+            if x.nbytes:
+                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
+                if not in_place:
+                    _check(lib.srack_device_from_host(d_out, out.ctypes.data_as(C.c_void_p), out.nbytes, None))
+                if c is not None:
+                    _check(lib.srack_device_from_host(d_cv, c.ctypes.data_as(C.c_void_p), c.nbytes, None))
+            to = d_in if in_place else d_out
+            self.bus_shaper_raw(x.shape[2], d_in, x.shape[1], d_cv if c is not None else None, to, None)
+            if out.nbytes:
+                _check(lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), to, out.nbytes, None))
+            _check(lib.srack_device_sync(None))
+            return out
+        finally:
+            for d in (d_in, d_out, d_cv):
                 if d.value:
                     lib.srack_device_free(d)
 

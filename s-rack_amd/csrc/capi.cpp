@@ -1366,6 +1366,75 @@ int srack_buses_vca(srack_patch* p, uint32_t n_samples, const float* d_rows, uin
     });
 }
 
+// ---- the bus shapers -------------------------------------------------------------------------------------------------
+static const float kBusShaperDefaults[SRACK_BUS_SHAPER_NPARAMS] = {1.0f, 1.0f, 1.0f};  // pre, exponent (NonLinearModule::new's constant), post
+
+int srack_buses_set_shaper(srack_patch* p, const float* params, const int* mode)
+{
+    return guarded([&]() -> int {
+        const int rc = console_preamble(p, "buses_set_shaper");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        BusShaper& F = h.console.busshaper;
+        const size_t n = h.n_buses;
+        for (size_t b = 0; mode && b < n; b++)
+            if (mode[b] < SRACK_BUS_SHAPER_OFF || mode[b] > SRACK_BUS_SHAPER_CV) {
+                set_error("buses_set_shaper: bus " + std::to_string(b) + " asks for mode " + std::to_string(mode[b]) + ": a bus shaper is off (0), constant (1) or CV (2)");
+                return SRACK_ERR_INVALID;
+            }
+        // (built aside: a failure leaves the earlier setting in place)
+        std::vector<float> par(n * SRACK_BUS_SHAPER_NPARAMS);
+        std::vector<int32_t> mo(n, SRACK_BUS_SHAPER_CONST);
+        for (size_t b = 0; b < n; b++) {
+            for (int f = 0; f < SRACK_BUS_SHAPER_NPARAMS; f++) par[b * SRACK_BUS_SHAPER_NPARAMS + f] = kBusShaperDefaults[f];
+            if (mode) mo[b] = mode[b];
+        }
+        if (params) std::memcpy(par.data(), params, sizeof(float) * par.size());  // bit for bit
+        F.params = std::move(par);
+        F.mode = std::move(mo);
+        F.set = true;
+        device_busshaper_changed(h);  // the table goes up again before the next call's kernel
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_get_shaper(const srack_patch* p, float* params, int* mode, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        const int rc = console_preamble(p, "buses_get_shaper");
+        if (rc != SRACK_OK) return rc;
+        const PatchHandle& h = p->h;
+        const BusShaper& F = h.console.busshaper;
+        if (!F.set) return 0;
+        const size_t n = std::min<size_t>(cap, h.n_buses);
+        if (params && n) std::memcpy(params, F.params.data(), sizeof(float) * n * SRACK_BUS_SHAPER_NPARAMS);
+        for (size_t b = 0; mode && b < n; b++) mode[b] = F.mode[b];
+        return (int)h.n_buses;
+    });
+}
+
+int srack_buses_shaper(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream)
+{
+    return guarded([&]() -> int {
+        int rc = console_preamble(p, "buses_shaper");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        if ((rc = need_set(h.console.busshaper.set, "buses_shaper", "shapers", "shaper")) != SRACK_OK) return rc;
+        if (n_samples == 0) return SRACK_OK;
+        if ((rc = need_rows("buses_shaper", d_rows, d_out, "d_out", row_channels)) != SRACK_OK) return rc;
+        const uint64_t bytes = 4ull * h.n_buses * row_channels * n_samples, cv_bytes = 4ull * h.n_buses * n_samples;
+        if (d_rows != d_out && meet(d_rows, bytes, d_out, bytes)) {
+            set_error("buses_shaper: d_out overlaps d_rows in part: it must be d_rows itself or disjoint from it");
+            return SRACK_ERR_INVALID;
+        }
+        if (d_cv && meet(d_cv, cv_bytes, d_out, bytes)) {
+            set_error("buses_shaper: d_cv overlaps d_out");
+            return SRACK_ERR_INVALID;
+        }
+        return device_buses_shaper(h, n_samples, d_rows, row_channels, d_cv, d_out, stream);
+    });
+}
+
 int srack_render_reserve(srack_patch* p, uint32_t n_samples, int want_mix, uint32_t flags)
 {
     return guarded([&]() -> int {

@@ -595,7 +595,76 @@ static std::string busvca_note(const BusVca& F)
     return F.ran ? " busvca=" + std::to_string(F.last_on) + "[" + std::to_string(F.last_gated) + " gated]" : std::string();
 }
 
-// ---- the five together --------------------------------------------------------------------------------------------------------------
+// ---- the bus shapers (busshape.hip.h, launched through launch_bus_shaper) -----------------------------------------------------------------
+// A table entry per bus, in bus order, and behind it the list of the buses that are not OFF: an in-place call launches work for those
+// alone, an out-of-place one for every bus (an OFF bus is a copy).  There is no state.  The table goes up again after a change of the
+// setting, behind a host-side wait for the last call's kernel, which may still be reading it.  A tick session of unchanged shapers is
+// the launch and one event per call.
+void device_busshaper_changed(PatchHandle& h) { h.console.busshaper.tab_dirty = true; }
+
+static void busshaper_drop(BusShaper& F)
+{
+    F.sync.wait();
+    F.d_tab.release();
+    F.sync.destroy();
+    F = BusShaper();
+}
+
+int device_buses_shaper(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream)
+{
+    BusShaper& F = h.console.busshaper;
+    const uint32_t n_buses = h.n_buses;
+    int rc;
+    if ((rc = F.sync.begin(stream)) != SRACK_OK) return rc;
+    std::vector<uint32_t> on;
+    uint32_t n_cv = 0;
+    for (uint32_t b = 0; b < n_buses; b++) {
+        if (F.mode[b] != SRACK_BUS_SHAPER_OFF) on.push_back(b);
+        n_cv += F.mode[b] == SRACK_BUS_SHAPER_CV;
+    }
+    const size_t at_list = sizeof(BusShaperBus) * n_buses;
+    if (F.tab_dirty || !F.d_tab.p) {  // (n_buses is fixed while the shapers live: another n_buses drops them)
+        std::vector<BusShaperBus> tab(n_buses);
+        for (uint32_t b = 0; b < n_buses; b++) {
+            BusShaperBus& r = tab[b];
+            r.pre = F.params[(size_t)b * SRACK_BUS_SHAPER_NPARAMS + SRACK_BUS_SHAPER_PRE];
+            r.exponent = F.params[(size_t)b * SRACK_BUS_SHAPER_NPARAMS + SRACK_BUS_SHAPER_EXPONENT];
+            r.post = F.params[(size_t)b * SRACK_BUS_SHAPER_NPARAMS + SRACK_BUS_SHAPER_POST];
+            r.mode = (uint32_t)F.mode[b];
+        }
+        if ((rc = F.d_tab.grow(F.sync, at_list + sizeof(uint32_t) * n_buses, "buses_shaper", "the shapers' table")) != SRACK_OK) return rc;
+        F.sync.wait();
+        HIP_TRY(hipMemcpy(F.d_tab.p, tab.data(), at_list, hipMemcpyHostToDevice));
+        if (!on.empty()) HIP_TRY(hipMemcpy((char*)F.d_tab.p + at_list, on.data(), sizeof(uint32_t) * on.size(), hipMemcpyHostToDevice));
+        F.tab_dirty = false;
+    }
+    const bool in_place = d_out == d_rows;
+    BusShaperArgs a;
+    a.rows = d_rows;
+    a.cv = d_cv;
+    a.out = d_out;
+    a.tab = (const BusShaperBus*)F.d_tab.p;
+    a.list = in_place ? (const uint32_t*)((const char*)F.d_tab.p + at_list) : nullptr;
+    a.n = n_samples;
+    a.n_work = in_place ? (uint32_t)on.size() : n_buses;
+    a.n_stretches = (n_samples + kBusShaperStretch - 1) / kBusShaperStretch;
+    a.n_units = a.n_work * a.n_stretches;  // (rows of 4 n_units KiB at the least: far below 2^32 in any memory)
+    a.row_channels = row_channels;
+    a.used = row_channels < 2 ? row_channels : 2u;
+    launch_bus_shaper(a, (hipStream_t)stream);
+    if ((rc = F.sync.end(stream)) != SRACK_OK) return rc;
+    F.last_on = (uint32_t)on.size();
+    F.last_cv = n_cv;
+    F.ran = true;
+    return SRACK_OK;
+}
+
+static std::string busshaper_note(const BusShaper& F)
+{
+    return F.ran ? " busshp=" + std::to_string(F.last_on) + "[" + std::to_string(F.last_cv) + " cv]" : std::string();
+}
+
+// ---- the six together ---------------------------------------------------------------------------------------------------------------
 void device_console_drop(PatchHandle& h)
 {
     busfx_drop(h.console.busfx);
@@ -603,12 +672,13 @@ void device_console_drop(PatchHandle& h)
     device_sends_drop(h);
     busvcf_drop(h.console.busvcf);
     busvca_drop(h.console.busvca);
+    busshaper_drop(h.console.busshaper);
 }
 
 std::string device_console_note(const PatchHandle& h)
 {
     const Console& C = h.console;
-    return sends_note(C.sends) + busvcf_note(C.busvcf) + busvca_note(C.busvca) + busfx_note(C.busfx) + master_note(C.master);
+    return sends_note(C.sends) + busvcf_note(C.busvcf) + busvca_note(C.busvca) + busshaper_note(C.busshaper) + busfx_note(C.busfx) + master_note(C.master);
 }
 
 }  // namespace srack

@@ -1,5 +1,5 @@
-// console.hpp — the host side of the bus console (console.cpp): the five stages behind the mixer — sends, reverbs, VCAs, filters, master
-// section — as they hang off the handle.  None of them is part of the program or of DeviceState (that is replaced on every re-flatten,
+// console.hpp — the host side of the bus console (console.cpp): the six stages behind the mixer — sends, reverbs, VCAs, shapers, filters,
+// master section — as they hang off the handle.  None of them is part of the program or of DeviceState (that is replaced on every re-flatten,
 // and a reverb's tail or a filter's state carries on across an edit of the patch); all are dropped with the mix table.
 #pragma once
 #include <cstddef>
@@ -133,16 +133,31 @@ struct BusVca {
     bool ran = false;
 };
 
+// The bus shapers (srack_buses_set_shaper / srack_buses_shaper): a drive, a NonLinearModule and a make-up gain per mix bus and channel.
+// No state: the setting, and on the device a table entry per bus with the list of the buses that are not OFF behind it (busshape.hip.h).
+struct BusShaper {
+    bool set = false;
+    std::vector<float> params;      // [n_buses][SRACK_BUS_SHAPER_NPARAMS], as the host gave them
+    std::vector<int32_t> mode;      // [n_buses] SRACK_BUS_SHAPER_OFF / _CONST / _CV
+    // device side; nothing of it exists before the first srack_buses_shaper
+    DeviceBuf d_tab;                // BusShaperBus [n_buses], then u32 [n_on]: the buses that are not OFF
+    bool tab_dirty = true;          // constants or modes changed
+    StageSync sync;
+    uint32_t last_on = 0, last_cv = 0;  // srack_render_info, once a call has run
+    bool ran = false;
+};
+
 struct Console {
     BusFx busfx;
     Master master;
     Sends sends;
     BusVcf busvcf;
     BusVca busvca;
+    BusShaper busshaper;
 };
 
-void device_console_drop(PatchHandle& h);               // all five stages: settings, device memory, events and notes
-std::string device_console_note(const PatchHandle& h);  // the notes of the stages that have run: sends, busvcf, busvca, busfx, master
+void device_console_drop(PatchHandle& h);               // all six stages: settings, device memory, events and notes
+std::string device_console_note(const PatchHandle& h);  // the notes of the stages that have run: sends, busvcf, busvca, busshp, busfx, master
 // The bus reverbs: one call's work enqueued on `stream` (allocating and zeroing what is missing); state handling without a call.
 int device_buses_reverb(PatchHandle& h, uint32_t n_samples, const float* d_bus_mix, float* d_bus_fx, void* stream);
 void device_busfx_free_bus(PatchHandle& h, uint32_t bus);  // the bus's state, once no call uses it any more
@@ -165,5 +180,8 @@ int device_busvca_modes(PatchHandle& h, const std::vector<int32_t>& mode);  // t
 int device_busvca_state(PatchHandle& h, float* state, uint32_t cap);        // host, f32 [cap][6] as the C ABI hands it out, behind a wait for the last call
 void device_busvca_changed(PatchHandle& h);  // sliders, modes or flags were replaced: the next call uploads the table
 void device_busvca_reset(PatchHandle& h);    // every state fresh, before the next call uses it
+// The bus shapers: one call's work enqueued on `stream` (allocating and uploading the table when it is missing or changed).
+int device_buses_shaper(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream);
+void device_busshaper_changed(PatchHandle& h);  // constants or modes were replaced: the next call uploads the table
 
 }  // namespace srack

@@ -113,4 +113,26 @@ struct BusVcaArgs {
     uint32_t used;              // min(row_channels, 2): the channels that are processed
 };
 
+// One srack_buses_shaper call (busshape.hip.h).  The table has an entry per bus, in bus order; behind it lies the list of the buses
+// that are not OFF, which an in-place call works through (an out-of-place one takes every bus: an OFF bus is a copy).
+struct BusShaperBus {
+    float pre, exponent, post;  // the bus's three constants, as given
+    uint32_t mode;              // SRACK_BUS_SHAPER_OFF / _CONST / _CV
+};
+static_assert(sizeof(BusShaperBus) == 16, "the host uploads the table as it stands");
+constexpr uint32_t kBusShaperStretch = 1024;  // samples of one bus a wave takes
+struct BusShaperArgs {
+    const float* rows;          // [n_buses][row_channels][n]
+    const float* cv;            // [n_buses][n] or null
+    float* out;                 // [n_buses][row_channels][n]; may be rows itself
+    const BusShaperBus* tab;    // [n_buses]
+    const uint32_t* list;       // [n_work] the buses to work on; null: buses 0 .. n_work - 1
+    uint32_t n;                 // samples
+    uint32_t n_work;            // buses this call works on
+    uint32_t n_stretches;       // ceil(n / kBusShaperStretch): the stretches of a bus
+    uint32_t n_units;           // n_work * n_stretches: a wave each
+    uint32_t row_channels;
+    uint32_t used;              // min(row_channels, 2): the channels that are processed
+};
+
 }  // namespace srack

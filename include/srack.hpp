@@ -274,6 +274,15 @@ public:
     {
         check(srack_buses_shaper(p_, n_samples, d_rows, row_channels, d_cv, d_out, stream));
     }
+    // The bus meters, a read-only tap between any two console calls: d_rows f32 [n_buses][row_channels][n_samples] -> d_levels f64
+    // [n_windows][SRACK_STAT_COUNT][n_buses][2] (record k: stream positions [k * window, (k + 1) * window); the call's samples are
+    // first_sample .. first_sample + n_samples - 1) and d_totals f64 [SRACK_STAT_COUNT][n_buses][2]; either may be null, not both.  Both
+    // are ADDED TO: zero-fill once, cut the stream into calls as you like.  No state on the handle.  Asynchronous on `stream`.
+    void bus_meter(uint64_t first_sample, uint32_t n_samples, const float* d_rows, uint32_t row_channels, uint32_t window, double* d_levels,
+                   uint32_t n_windows, double* d_totals, void* stream = nullptr)
+    {
+        check(srack_buses_meter(p_, first_sample, n_samples, d_rows, row_channels, window, d_levels, n_windows, d_totals, stream));
+    }
     // execute_batch plus d_bus_mix, f32 [n_buses][channels][n_samples] (written); d_frames, d_mix, d_stats may each be null
     void execute_batch_buses(uint32_t n_samples, float* d_frames, float* d_mix, double* d_stats, float* d_bus_mix, uint32_t flags = 0, void* stream = nullptr)
     {

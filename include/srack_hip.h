@@ -764,6 +764,44 @@ int srack_buses_get_shaper(const srack_patch* p, float* params, int* mode, uint3
 int srack_buses_shaper(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels,
                        const float* d_cv, float* d_out, void* stream);
 
+/* ---- the bus meters: windowed level tracks and totals per mix bus, a read-only tap between any two console calls ---------------------
+ * Which strip clips behind its shaper, how loud an aux bus is after its reverb, what the envelope of a drum group looks like over the
+ * second: the per-voice statistics (srack_render_stats) applied to the f32 words of bus rows, per window of a stream and over all of it,
+ * without the rows ever leaving the device.
+ *   d_rows   : device, f32 [n_buses][row_channels][n_samples]: what any console call writes.  1 <= row_channels <= 8; channels 0 and 1
+ *              are metered, channels beyond the second are not read.  Any 4-byte aligned address.  Never written.
+ *   first_sample, n_samples : the call's samples are positions first_sample .. first_sample + n_samples - 1 of a metered stream that the
+ *              HOST counts.
+ *   d_levels : device, f64 [n_windows][SRACK_STAT_COUNT][n_buses][2], 8-byte aligned, or NULL.  Entity-minor like the per-voice
+ *              statistics: one window is one contiguous frame of every strip's meters.  Record k of (bus, channel) covers stream
+ *              positions [k * window, (k + 1) * window).  window >= SRACK_BUS_METER_MIN_WINDOW, n_windows >= 1 and
+ *              first_sample + n_samples <= (uint64)n_windows * window.
+ *   d_totals : device, f64 [SRACK_STAT_COUNT][n_buses][2], 8-byte aligned, or NULL: the same six numbers over everything the calls
+ *              were given.
+ * The definitions are the per-voice ones (SRACK_STAT_*), through the same device function: NaN or +-inf adds 1 to NONFINITE and nothing
+ * else; otherwise SUM, SUM_SQ, PEAK_POS, PEAK_NEG and CLIPPED (|x| > 1; exactly +-1.0 does not clip) are updated, a peak only to a
+ * strictly larger value.  RMS and dB are the host's division and root.
+ * The call ADDS TO WHAT THE BUFFERS HOLD, for every record it touches and for the totals: SUM and SUM_SQ continue the sequential f64
+ * loop in sample order from the stored value, bit for bit; the peaks are read back as f32; the counts are added as integers.  So the
+ * host zero-fills once, a window cut by a call boundary is finished by the next call, and no bit depends on how the samples are cut
+ * into calls.  For that reason the stage has no state on the handle: no reset call, no state call.
+ * Untouched: records of windows outside floor(first_sample / window) .. floor((first_sample + n_samples - 1) / window) are neither
+ * read nor written; with row_channels == 1 every channel-1 entry is left alone (the master's convention).
+ * d_levels and d_totals must not overlap d_rows or each other.
+ * Errors, in this order: SRACK_ERR_INVALID for a null handle; SRACK_ERR_STATE before srack_voices_configure or before a mix table
+ * exists; n_samples == 0 is SRACK_OK and touches nothing; SRACK_ERR_INVALID for a null d_rows, row_channels outside 1..8, both outputs
+ * NULL, a misaligned output, with d_levels given a window below the minimum, n_windows == 0 or a span too short, or an overlap.  With
+ * d_levels == NULL, window, n_windows and first_sample are ignored.
+ * The stage belongs to the handle like every console stage, and owns nothing: running it does not re-flatten, restarts nothing and
+ * changes no bit of any other output or state.  srack_render_info says " meter=<n_buses>[w<window>]" behind " master=" once a call has
+ * run; the window reads "-" when only totals were taken.
+ * The kernel is the bus filters' shape: a lane per (bus, channel) row, tiles of 64 rows x 64 samples turned through LDS, two sets of
+ * statistics in registers, the open record stored and the next one loaded at a window boundary (csrc/busmeter.hip.h). */
+#define SRACK_BUS_METER_MIN_WINDOW 64
+int srack_buses_meter(srack_patch* p, uint64_t first_sample, uint32_t n_samples,
+                      const float* d_rows, uint32_t row_channels, uint32_t window,
+                      double* d_levels, uint32_t n_windows, double* d_totals, void* stream);
+
 /* Optional: do everything a later srack_render(p, <= n_samples, ..., flags) would do on first use — flatten the graph,
  * upload the programs and the voice table, size the scratch buffers (mix partials when want_mix, control tracks) — so
  * that the first render costs what every render costs.  Renders nothing and leaves the voice state untouched. */

@@ -93,6 +93,7 @@ mod ffi {
         pub fn srack_buses_set_shaper(p: *mut SrackPatch, params: *const f32, mode: *const c_int) -> c_int;
         pub fn srack_buses_get_shaper(p: *const SrackPatch, params: *mut f32, mode: *mut c_int, cap: u32) -> c_int;
         pub fn srack_buses_shaper(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_cv: *const f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
+        pub fn srack_buses_meter(p: *mut SrackPatch, first_sample: u64, n_samples: u32, d_rows: *const f32, row_channels: u32, window: u32, d_levels: *mut f64, n_windows: u32, d_totals: *mut f64, stream: *mut c_void) -> c_int;
         pub fn srack_device_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
         pub fn srack_device_free(d_ptr: *mut c_void) -> c_int;
         pub fn srack_device_to_host(h_dst: *mut c_void, d_src: *const c_void, bytes: usize, stream: *mut c_void) -> c_int;
@@ -607,6 +608,15 @@ impl Patch {
         let c = cv.map_or(std::ptr::null(), |b| b.as_f32() as *const f32);
         let o = out.map_or(rows.as_f32(), |b| b.as_f32());
         check(unsafe { ffi::srack_buses_shaper(self.raw, n_samples, rows.as_f32() as *const f32, row_channels, c, o, std::ptr::null_mut()) }).map(|_| ())
+    }
+    /// The bus meters (`srack_buses_meter`), a read-only tap on bus rows: `rows` `[n_buses][row_channels][n_samples]` f32 are positions
+    /// `first_sample ..` of a stream the caller counts; `levels` `(buffer, window, n_windows)` is f64
+    /// `[n_windows][6][n_buses][2]`, record `k` covering `[k * window, (k + 1) * window)`; `totals` is f64 `[6][n_buses][2]`.  Both are
+    /// added to: zero-fill once, cut the stream into calls at will.  One of the two must be given.
+    pub fn bus_meter(&mut self, first_sample: u64, n_samples: u32, rows: &DeviceBuffer, row_channels: u32, levels: Option<(&DeviceBuffer, u32, u32)>, totals: Option<&DeviceBuffer>) -> Result<(), Error> {
+        let (l, window, n_windows) = levels.map_or((std::ptr::null_mut(), 0, 0), |(b, w, n)| (b.as_f64(), w, n));
+        let t = totals.map_or(std::ptr::null_mut(), |b| b.as_f64());
+        check(unsafe { ffi::srack_buses_meter(self.raw, first_sample, n_samples, rows.as_f32() as *const f32, row_channels, window, l, n_windows, t, std::ptr::null_mut()) }).map(|_| ())
     }
 }
 

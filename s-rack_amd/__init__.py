@@ -29,6 +29,7 @@ BUS_SHAPER_NPARAMS = 3  # srack_buses_set_shaper: PRE, EXPONENT, POST per bus
 BUS_SHAPER_PRE, BUS_SHAPER_EXPONENT, BUS_SHAPER_POST = 0, 1, 2
 BUS_SHAPER_OFF, BUS_SHAPER_CONST, BUS_SHAPER_CV = 0, 1, 2  # a bus's mode: it passes; the exponent is EXPONENT; the exponent is the bus's CV row
 BUS_SHAPER_DEFAULTS = (1.0, 1.0, 1.0)  # drive, exponent, make-up gain: what set_bus_shaper(None) gives every bus
+BUS_METER_MIN_WINDOW = 64  # srack_buses_meter: the shortest window of a level track, in samples
 ADSR_MODE_ATTACK, ADSR_MODE_DECAY, ADSR_MODE_SUSTAIN, ADSR_MODE_RELEASE, ADSR_MODE_NONE = 0, 1, 2, 3, 4  # the values of ADSR_MODE
 FREEVERB_DEFAULTS = (0.5, 0.0, 1.0, 0.5, 0.5, 0.0)  # FreeverbModule's six parameters in field order: what set_bus_reverbs(None) gives every bus
 WAVE_OWN = -1
@@ -51,6 +52,7 @@ ABI_SYMBOLS = [
     "srack_buses_set_filter", "srack_buses_get_filter", "srack_buses_reset_filter", "srack_buses_filter_state", "srack_buses_filter",
     "srack_buses_set_vca", "srack_buses_get_vca", "srack_buses_reset_vca", "srack_buses_vca_state", "srack_buses_vca",
     "srack_buses_set_shaper", "srack_buses_get_shaper", "srack_buses_shaper",
+    "srack_buses_meter",
     "srack_patch_set_wave_bank", "srack_patch_get_wave_bank", "srack_patch_get_wave_bank_samples", "srack_voices_set_waves", "srack_voices_get_waves",
     "srack_patch_set_sequence_bank", "srack_patch_get_sequence_bank", "srack_voices_set_sequences", "srack_voices_get_sequences",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
@@ -153,6 +155,8 @@ def _load():
         L.srack_buses_set_shaper.argtypes = [vp, fp, ip]
         L.srack_buses_get_shaper.argtypes = [vp, fp, ip, u32]
         L.srack_buses_shaper.argtypes = [vp, u32, vp, u32, vp, vp, vp]
+    if hasattr(L, "srack_buses_meter"):
+        L.srack_buses_meter.argtypes = [vp, C.c_uint64, u32, vp, u32, u32, vp, u32, vp, vp]
     if hasattr(L, "srack_voices_set_waves"):  # (tools/ alternate older builds of the library under this binding)
         L.srack_patch_set_wave_bank.argtypes = [vp, i32, fp, ip, fp, u32]
         L.srack_patch_get_wave_bank.argtypes = [vp, i32, ip, fp, u32]
@@ -954,6 +958,51 @@ class Patch:
             return out
         finally:
             for d in (d_in, d_out, d_cv):
+                if d.value:
+                    lib.srack_device_free(d)
+
+    # ---- bus meters: windowed level tracks and totals per mix bus, a read-only tap on bus rows ---------------
+    def bus_meter_raw(self, first_sample, n_samples, d_rows, row_channels, window, d_levels, n_windows, d_totals, stream=None):
+        """Device pointers in; asynchronous on `stream` (srack_buses_meter): d_rows f32 [n_buses][row_channels][n] (read only), d_levels
+        f64 [n_windows][STAT_COUNT][n_buses][2] or None, d_totals f64 [STAT_COUNT][n_buses][2] or None; both are added to."""
+        _check(lib.srack_buses_meter(self.h, first_sample, n_samples, d_rows, row_channels, window, d_levels, n_windows, d_totals, stream))
+
+    def bus_meter(self, rows, window=None, first_sample=0, levels=None, totals=None):
+        """Convenience for tests: rows f32 [n_buses][row_channels][T] from the host through the meters -> (levels, totals), the updated
+        arrays.  window None: no level track (levels comes back None); otherwise levels f64 [n_windows][STAT_COUNT][n_buses][2] to
+        continue from (a copy comes back), None for zeros over ceil((first_sample + T) / window) windows.  totals f64
+        [STAT_COUNT][n_buses][2] to continue from, None for zeros, False for no totals (None comes back)."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
+        T = x.shape[2]
+        lv = tt = None
+        if window is not None:
+            if levels is None:
+                levels = np.zeros((max(1, -(-(first_sample + T) // max(1, window))), STAT_COUNT, n_buses, 2))
+            lv = np.array(levels, dtype=np.float64, order="C", copy=True)
+            assert lv.ndim == 4 and lv.shape[1:] == (STAT_COUNT, n_buses, 2), lv.shape
+        if totals is not False:
+            tt = np.zeros((STAT_COUNT, n_buses, 2)) if totals is None else np.array(totals, dtype=np.float64, order="C", copy=True)
+            assert tt.shape == (STAT_COUNT, n_buses, 2), tt.shape
+        d_in, d_lv, d_tt = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        try:
+            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
+            if x.nbytes:
+                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
+            for a, d in ((lv, d_lv), (tt, d_tt)):
+                if a is not None:
+                    _check(lib.srack_device_alloc(C.byref(d), a.nbytes))
+                    _check(lib.srack_device_from_host(d, a.ctypes.data_as(C.c_void_p), a.nbytes, None))
+            self.bus_meter_raw(first_sample, T, d_in, x.shape[1], 0 if lv is None else window, d_lv if lv is not None else None,
+                               0 if lv is None else lv.shape[0], d_tt if tt is not None else None, None)
+            for a, d in ((lv, d_lv), (tt, d_tt)):
+                if a is not None:
+                    _check(lib.srack_device_to_host(a.ctypes.data_as(C.c_void_p), d, a.nbytes, None))
+            _check(lib.srack_device_sync(None))
+            return lv, tt
+        finally:
+            for d in (d_in, d_lv, d_tt):
                 if d.value:
                     lib.srack_device_free(d)
 

@@ -1435,6 +1435,40 @@ int srack_buses_shaper(srack_patch* p, uint32_t n_samples, const float* d_rows, 
     });
 }
 
+// ---- the bus meters --------------------------------------------------------------------------------------------------
+int srack_buses_meter(srack_patch* p, uint64_t first_sample, uint32_t n_samples, const float* d_rows, uint32_t row_channels, uint32_t window,
+                      double* d_levels, uint32_t n_windows, double* d_totals, void* stream)
+{
+    return guarded([&]() -> int {
+        const int rc = console_preamble(p, "buses_meter");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        if (n_samples == 0) return SRACK_OK;
+        auto bad = [](const char* what) {
+            set_error(std::string("buses_meter: ") + what);
+            return SRACK_ERR_INVALID;
+        };
+        if (!d_rows) return bad("d_rows must be given");
+        if (row_channels < 1 || row_channels > 8) return bad("row_channels must be 1 .. 8");
+        if (!d_levels && !d_totals) return bad("d_levels or d_totals must be given");
+        if (((uintptr_t)d_levels & 7u) != 0) return bad("d_levels must be 8-byte aligned");
+        if (((uintptr_t)d_totals & 7u) != 0) return bad("d_totals must be 8-byte aligned");
+        if (d_levels) {
+            if (window < SRACK_BUS_METER_MIN_WINDOW) return bad("window must be at least SRACK_BUS_METER_MIN_WINDOW (64) samples");
+            if (n_windows == 0) return bad("n_windows must be at least 1");
+            // (n_windows * window < 2^64; the sum is taken apart so that a first_sample near 2^64 cannot wrap)
+            const uint64_t span = (uint64_t)n_windows * window;
+            if (first_sample > span || n_samples > span - first_sample) return bad("first_sample + n_samples exceeds n_windows * window");
+        }
+        const uint64_t row_bytes = 4ull * h.n_buses * row_channels * n_samples, total_bytes = 8ull * SRACK_STAT_COUNT * h.n_buses * 2;
+        const uint64_t level_bytes = total_bytes * n_windows;
+        if (d_levels && meet(d_levels, level_bytes, d_rows, row_bytes)) return bad("d_levels overlaps d_rows");
+        if (d_totals && meet(d_totals, total_bytes, d_rows, row_bytes)) return bad("d_totals overlaps d_rows");
+        if (d_levels && d_totals && meet(d_levels, level_bytes, d_totals, total_bytes)) return bad("d_levels overlaps d_totals");
+        return device_buses_meter(h, first_sample, n_samples, d_rows, row_channels, window, d_levels, n_windows, d_totals, stream);
+    });
+}
+
 int srack_render_reserve(srack_patch* p, uint32_t n_samples, int want_mix, uint32_t flags)
 {
     return guarded([&]() -> int {

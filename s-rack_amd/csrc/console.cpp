@@ -664,7 +664,38 @@ static std::string busshaper_note(const BusShaper& F)
     return F.ran ? " busshp=" + std::to_string(F.last_on) + "[" + std::to_string(F.last_cv) + " cv]" : std::string();
 }
 
-// ---- the six together ---------------------------------------------------------------------------------------------------------------
+// ---- the bus meters (busmeter.hip.h, launched through launch_bus_meter) ------------------------------------------------------------------
+// A tap: the kernel reads the caller's rows and continues the caller's records.  The stage has no memory of its own, so there is nothing
+// to order between its calls beyond what the caller's streams order: a call is the launch and its error.
+int device_buses_meter(PatchHandle& h, uint64_t first_sample, uint32_t n_samples, const float* d_rows, uint32_t row_channels, uint32_t window,
+                       double* d_levels, uint32_t n_windows, double* d_totals, void* stream)
+{
+    BusMeter& F = h.console.busmeter;
+    (void)n_windows;  // (capi.cpp has held the call's span against it: the kernel's window index stays below it)
+    BusMeterArgs a;
+    a.rows = d_rows;
+    a.levels = d_levels;
+    a.totals = d_totals;
+    a.first = d_levels ? first_sample : 0;
+    a.window = d_levels ? window : 0;
+    a.n = n_samples;
+    a.n_buses = h.n_buses;
+    a.row_channels = row_channels;
+    a.used = row_channels < 2 ? row_channels : 2u;
+    launch_bus_meter(a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    F.last_buses = h.n_buses;
+    F.last_window = a.window;
+    F.ran = true;
+    return SRACK_OK;
+}
+
+static std::string busmeter_note(const BusMeter& F)
+{
+    return F.ran ? " meter=" + std::to_string(F.last_buses) + "[w" + (F.last_window ? std::to_string(F.last_window) : std::string("-")) + "]" : std::string();
+}
+
+// ---- the seven together -------------------------------------------------------------------------------------------------------------
 void device_console_drop(PatchHandle& h)
 {
     busfx_drop(h.console.busfx);
@@ -673,12 +704,13 @@ void device_console_drop(PatchHandle& h)
     busvcf_drop(h.console.busvcf);
     busvca_drop(h.console.busvca);
     busshaper_drop(h.console.busshaper);
+    h.console.busmeter = BusMeter();
 }
 
 std::string device_console_note(const PatchHandle& h)
 {
     const Console& C = h.console;
-    return sends_note(C.sends) + busvcf_note(C.busvcf) + busvca_note(C.busvca) + busshaper_note(C.busshaper) + busfx_note(C.busfx) + master_note(C.master);
+    return sends_note(C.sends) + busvcf_note(C.busvcf) + busvca_note(C.busvca) + busshaper_note(C.busshaper) + busfx_note(C.busfx) + master_note(C.master) + busmeter_note(C.busmeter);
 }
 
 }  // namespace srack

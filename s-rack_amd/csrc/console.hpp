@@ -1,5 +1,5 @@
-// console.hpp — the host side of the bus console (console.cpp): the six stages behind the mixer — sends, reverbs, VCAs, shapers, filters,
-// master section — as they hang off the handle.  None of them is part of the program or of DeviceState (that is replaced on every re-flatten,
+// console.hpp — the host side of the bus console (console.cpp): the seven stages behind the mixer — sends, reverbs, VCAs, shapers, filters,
+// master section, meters — as they hang off the handle.  None of them is part of the program or of DeviceState (that is replaced on every re-flatten,
 // and a reverb's tail or a filter's state carries on across an edit of the patch); all are dropped with the mix table.
 #pragma once
 #include <cstddef>
@@ -147,6 +147,13 @@ struct BusShaper {
     bool ran = false;
 };
 
+// The bus meters (srack_buses_meter): a read-only tap on the bus rows.  The records and totals are the caller's buffers and the stream
+// position is the caller's count, so there is nothing to own: no setting, no device memory, no event — only what srack_render_info says.
+struct BusMeter {
+    uint32_t last_buses = 0, last_window = 0;  // srack_render_info, once a call has run; window 0: only totals were taken
+    bool ran = false;
+};
+
 struct Console {
     BusFx busfx;
     Master master;
@@ -154,10 +161,11 @@ struct Console {
     BusVcf busvcf;
     BusVca busvca;
     BusShaper busshaper;
+    BusMeter busmeter;
 };
 
-void device_console_drop(PatchHandle& h);               // all six stages: settings, device memory, events and notes
-std::string device_console_note(const PatchHandle& h);  // the notes of the stages that have run: sends, busvcf, busvca, busshp, busfx, master
+void device_console_drop(PatchHandle& h);               // all seven stages: settings, device memory, events and notes
+std::string device_console_note(const PatchHandle& h);  // the notes of the stages that have run: sends, busvcf, busvca, busshp, busfx, master, meter
 // The bus reverbs: one call's work enqueued on `stream` (allocating and zeroing what is missing); state handling without a call.
 int device_buses_reverb(PatchHandle& h, uint32_t n_samples, const float* d_bus_mix, float* d_bus_fx, void* stream);
 void device_busfx_free_bus(PatchHandle& h, uint32_t bus);  // the bus's state, once no call uses it any more
@@ -183,5 +191,8 @@ void device_busvca_reset(PatchHandle& h);    // every state fresh, before the ne
 // The bus shapers: one call's work enqueued on `stream` (allocating and uploading the table when it is missing or changed).
 int device_buses_shaper(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream);
 void device_busshaper_changed(PatchHandle& h);  // constants or modes were replaced: the next call uploads the table
+// The bus meters: one call's kernel enqueued on `stream`; d_levels or d_totals may be null, not both.
+int device_buses_meter(PatchHandle& h, uint64_t first_sample, uint32_t n_samples, const float* d_rows, uint32_t row_channels, uint32_t window,
+                       double* d_levels, uint32_t n_windows, double* d_totals, void* stream);
 
 }  // namespace srack

@@ -102,4 +102,7 @@ void launch_bus_vca(const BusVcaArgs& a, hipStream_t st);
 // ---- the bus shapers (busshape.hip): a wave per stretch of kBusShaperStretch samples of a bus, a.n_units of them, four to a workgroup ----
 void launch_bus_shaper(const BusShaperArgs& a, hipStream_t st);
 
+// ---- the bus meters (busmeter.hip): a lane per (bus, channel) row, a wave per workgroup; reads a.rows, continues a.levels and a.totals ----
+void launch_bus_meter(const BusMeterArgs& a, hipStream_t st);
+
 }  // namespace srack

@@ -135,4 +135,17 @@ struct BusShaperArgs {
     uint32_t used;              // min(row_channels, 2): the channels that are processed
 };
 
+// One srack_buses_meter call (busmeter.hip.h).  A read-only tap: rows in, records and totals continued where they stand.
+struct BusMeterArgs {
+    const float* rows;          // [n_buses][row_channels][n]
+    double* levels;             // [n_windows][SRACK_STAT_COUNT][n_buses][2] or null
+    double* totals;             // [SRACK_STAT_COUNT][n_buses][2] or null
+    uint64_t first;             // the stream position of sample 0 (levels only)
+    uint32_t window;            // samples per record (levels only)
+    uint32_t n;                 // samples
+    uint32_t n_buses;
+    uint32_t row_channels;
+    uint32_t used;              // min(row_channels, 2): the channels that are metered
+};
+
 }  // namespace srack

@@ -50,7 +50,7 @@ struct PatchHandle {
     std::vector<float> bus_gain;
     BusPlan bus_plan;
     uint64_t bus_revision = 0;
-    Console console;                // the six stages behind the mixer (console.hpp); dropped with the table (srack_voices_configure, another n_buses)
+    Console console;                // the seven stages behind the mixer (console.hpp); dropped with the table (srack_voices_configure, another n_buses)
     bool timing_armed = false;      // srack_render_kernel_ms has been called: renders bracket the dominant kernel with HIP events
 
     ~PatchHandle();

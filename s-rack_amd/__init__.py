@@ -201,6 +201,62 @@ def _check(rc):
     return rc
 
 
+def _opt(a, dtype, shape):
+    """An optional array argument -> (the contiguous array of `dtype` or None, its ctypes pointer or None); the shape is asserted.
+    The pointer keeps a reference to the array (numpy's data_as), so a caller may hold on to the pointer alone."""
+    if a is None:
+        return None, None
+    a = np.ascontiguousarray(a, dtype=dtype)
+    assert a.shape == shape, a.shape
+    return a, a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype)))
+
+
+def _truth(a):
+    """an optional array of flags -> where it is not 0, or None"""
+    return None if a is None else np.asarray(a) != 0
+
+
+class DeviceScope:
+    """Device buffers for the length of a `with` block (srack_device_*): the one place where a buffer's lifetime is decided.  Addresses
+    are plain integers.  Leaving the block normally waits for `stream` and frees everything; leaving it by an exception frees everything
+    without a wait.  What srack_device_free says is ignored."""
+
+    def __init__(self, stream=None):
+        self.stream, self._owned = stream, []
+
+    def __enter__(self):
+        return self
+
+    def alloc(self, nbytes, offset=0):
+        """-> the address of nbytes (8 at the least) of device memory, `offset` 4-byte words into an allocation that much larger"""
+        d = C.c_void_p()
+        _check(lib.srack_device_alloc(C.byref(d), max(8, nbytes) + 4 * offset))
+        self._owned.append(d)
+        return d.value + 4 * offset
+
+    def upload(self, a, offset=0, stream=None):
+        """alloc for the contiguous array `a`, its bytes sent up on `stream` (nothing is sent for 0 bytes) -> the address"""
+        d = self.alloc(a.nbytes, offset)
+        if a.nbytes:
+            _check(lib.srack_device_from_host(d, a.ctypes.data_as(C.c_void_p), a.nbytes, stream))
+        return d
+
+    def download(self, a, d):
+        """the contiguous array `a` filled from address d on the scope's stream (nothing is fetched for 0 bytes); complete behind the block"""
+        if a.nbytes:
+            _check(lib.srack_device_to_host(a.ctypes.data_as(C.c_void_p), d, a.nbytes, self.stream))
+
+    def __exit__(self, exc_type, exc, tb):
+        try:
+            if exc_type is None:
+                _check(lib.srack_device_sync(self.stream))
+        finally:
+            for d in self._owned:
+                lib.srack_device_free(d)
+            self._owned = []
+        return False
+
+
 def device_count():
     n = C.c_int(0)
     lib.srack_device_count(C.byref(n))
@@ -402,12 +458,8 @@ class Patch:
 
     def set_voice_waves(self, module, idx):
         """Which wave of the bank every voice plays (srack_voices_set_waves): idx[v] in [0, n_waves) or WAVE_OWN; None clears."""
-        if idx is None:
-            _check(lib.srack_voices_set_waves(self.h, module, None))
-            return
-        a = np.ascontiguousarray(idx, dtype=np.intc)
-        assert a.shape == (self.n_voices,), a.shape
-        _check(lib.srack_voices_set_waves(self.h, module, a.ctypes.data_as(C.POINTER(C.c_int))))
+        _, a = _opt(idx, np.intc, (self.n_voices,))
+        _check(lib.srack_voices_set_waves(self.h, module, a))
 
     def get_voice_waves(self, module):
         """-> int32 [V], or None when no assignment is set"""
@@ -442,12 +494,8 @@ class Patch:
 
     def set_voice_sequences(self, module, idx):
         """Which sequence of the bank every voice plays (srack_voices_set_sequences): idx[v] in [0, n_sequences) or SEQ_OWN; None clears."""
-        if idx is None:
-            _check(lib.srack_voices_set_sequences(self.h, module, None))
-            return
-        a = np.ascontiguousarray(idx, dtype=np.intc)
-        assert a.shape == (self.n_voices,), a.shape
-        _check(lib.srack_voices_set_sequences(self.h, module, a.ctypes.data_as(C.POINTER(C.c_int))))
+        _, a = _opt(idx, np.intc, (self.n_voices,))
+        _check(lib.srack_voices_set_sequences(self.h, module, a))
 
     def get_voice_sequences(self, module):
         """-> int32 [V], or None when no assignment is set"""
@@ -508,19 +556,17 @@ class Patch:
     def set_buses(self, n_buses, bus=None, gain=None):
         """The mix table (srack_voices_set_buses): bus[v] in [0, n_buses) or BUS_NONE (None: every voice in bus 0), gain[v] any f32
         (None: 1.0).  Not part of the program: changing it between renders restarts nothing."""
-        b = g = None
-        if bus is not None:
-            b = np.ascontiguousarray(bus, dtype=np.intc)
-            assert b.shape == (self.n_voices,), b.shape
-        if gain is not None:
-            g = np.ascontiguousarray(gain, dtype=np.float32)
-            assert g.shape == (self.n_voices,), g.shape
-        _check(lib.srack_voices_set_buses(self.h, n_buses, None if b is None else b.ctypes.data_as(C.POINTER(C.c_int)),
-                                          None if g is None else g.ctypes.data_as(C.POINTER(C.c_float))))
+        _, b = _opt(bus, np.intc, (self.n_voices,))
+        _, g = _opt(gain, np.float32, (self.n_voices,))
+        _check(lib.srack_voices_set_buses(self.h, n_buses, b, g))
+
+    def n_buses(self):
+        """The number of mix buses of the table set with set_buses; 0 when none is set."""
+        return _check(lib.srack_voices_get_buses(self.h, None, None, 0))
 
     def get_buses(self):
         """-> (n_buses, bus int32 [V], gain f32 [V]); (0, None, None) when no table is set"""
-        n = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        n = self.n_buses()
         if n == 0:
             return 0, None, None
         b, g = np.empty(self.n_voices, dtype=np.intc), np.empty(self.n_voices, dtype=np.float32)
@@ -540,16 +586,10 @@ class Patch:
         """srack_buses_set_reverb: params f64 [n_buses][6] in FreeverbModule's field order (FREEVERB_DAMPENING, _FREEZE, _WET, _WIDTH,
         _ROOM_SIZE, _DRY; None: the module's defaults), enabled [n_buses] (None: every bus).  Calling it again is the slider: the
         coefficients change, the tails stay.  Not part of the program: restarts nothing."""
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
-        a = e = None
-        if params is not None:
-            a = np.ascontiguousarray(params, dtype=np.float64)
-            assert a.shape == (n_buses, 6), a.shape
-        if enabled is not None:
-            e = np.ascontiguousarray(np.asarray(enabled) != 0, dtype=np.intc)
-            assert e.shape == (n_buses,), e.shape
-        _check(lib.srack_buses_set_reverb(self.h, None if a is None else a.ctypes.data_as(C.POINTER(C.c_double)),
-                                          None if e is None else e.ctypes.data_as(C.POINTER(C.c_int))))
+        n_buses = self.n_buses()
+        _, a = _opt(params, np.float64, (n_buses, 6))
+        _, e = _opt(_truth(enabled), np.intc, (n_buses,))
+        _check(lib.srack_buses_set_reverb(self.h, a, e))
 
     def get_bus_reverbs(self):
         """-> (n_buses, params f64 [n_buses][6], enabled int32 [n_buses]); (0, None, None) when no reverbs are set"""
@@ -577,35 +617,21 @@ class Patch:
     def bus_reverb(self, bus_mix):
         """Convenience for tests: bus_mix f32 [n_buses][channels][T] from the host through the reverbs -> fx f32 [n_buses][2][T]."""
         bm = np.ascontiguousarray(bus_mix, dtype=np.float32)
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        n_buses = self.n_buses()
         assert bm.shape[:2] == (n_buses, self.channels), bm.shape
         T = bm.shape[2]
         fx = np.empty((n_buses, 2, T), dtype=np.float32)
-        d_in, d_out = C.c_void_p(), C.c_void_p()
-        try:
-            _check(lib.srack_device_alloc(C.byref(d_in), max(4, bm.nbytes)))
-            _check(lib.srack_device_alloc(C.byref(d_out), max(4, fx.nbytes)))
-            if bm.nbytes:
-                _check(lib.srack_device_from_host(d_in, bm.ctypes.data_as(C.c_void_p), bm.nbytes, None))
+        with DeviceScope() as dev:
+            d_in, d_out = dev.upload(bm), dev.alloc(fx.nbytes)
             self.bus_reverb_raw(T, d_in, d_out, None)
-            if fx.nbytes:
-                _check(lib.srack_device_to_host(fx.ctypes.data_as(C.c_void_p), d_out, fx.nbytes, None))
-            _check(lib.srack_device_sync(None))
-            return fx
-        finally:
-            for d in (d_in, d_out):
-                if d.value:
-                    lib.srack_device_free(d)
+            dev.download(fx, d_out)
+        return fx
 
     # ---- master section: a gain per bus and channel, the buses summed to one stereo pair ---------------
     def set_master(self, gain=None):
         """srack_buses_set_master: gain f32 [n_buses][2], any f32 (None: 1.0 everywhere).  Not part of the program: restarts nothing."""
-        g = None
-        if gain is not None:
-            n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
-            g = np.ascontiguousarray(gain, dtype=np.float32)
-            assert g.shape == (n_buses, 2), g.shape
-        _check(lib.srack_buses_set_master(self.h, None if g is None else g.ctypes.data_as(C.POINTER(C.c_float))))
+        g = None if gain is None else _opt(gain, np.float32, (self.n_buses(), 2))[1]
+        _check(lib.srack_buses_set_master(self.h, g))
 
     def get_master(self):
         """-> gain f32 [n_buses][2], or None when no gains are set"""
@@ -625,31 +651,18 @@ class Patch:
         """Convenience for tests: rows f32 [n_buses][row_channels][T] from the host through the master -> (master f32 [2][T], stats).
         stats: f64 [2][STAT_COUNT] to continue from (a copy comes back), or None for no statistics."""
         x = np.ascontiguousarray(rows, dtype=np.float32)
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
-        assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
+        assert x.ndim == 3 and x.shape[0] == self.n_buses(), x.shape
         T = x.shape[2]
         out = np.empty((2, T), dtype=np.float32)
         st = None if stats is None else np.array(stats, dtype=np.float64).reshape(2, STAT_COUNT)
-        d_in, d_out, d_st = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        try:
-            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
-            _check(lib.srack_device_alloc(C.byref(d_out), max(4, out.nbytes)))
-            if x.nbytes:
-                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
+        with DeviceScope() as dev:
+            d_in, d_out = dev.upload(x), dev.alloc(out.nbytes)
+            d_st = None if st is None else dev.upload(st)
+            self.master_raw(T, d_in, x.shape[1], d_out, d_st, None)
+            dev.download(out, d_out)
             if st is not None:
-                _check(lib.srack_device_alloc(C.byref(d_st), st.nbytes))
-                _check(lib.srack_device_from_host(d_st, st.ctypes.data_as(C.c_void_p), st.nbytes, None))
-            self.master_raw(T, d_in, x.shape[1], d_out, d_st if st is not None else None, None)
-            if out.nbytes:
-                _check(lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), d_out, out.nbytes, None))
-            if st is not None:
-                _check(lib.srack_device_to_host(st.ctypes.data_as(C.c_void_p), d_st, st.nbytes, None))
-            _check(lib.srack_device_sync(None))
-            return out, st
-        finally:
-            for d in (d_in, d_out, d_st):
-                if d.value:
-                    lib.srack_device_free(d)
+                dev.download(st, d_st)
+        return out, st
 
     # ---- bus sends: aux sends from bus to bus, a gather-sum per destination bus -------------------------
     def set_sends(self, src, dst, gain=None, through=None):
@@ -657,24 +670,17 @@ class Patch:
         f32.  An empty list removes the sends.  Not part of the program: restarts nothing."""
         s, d = np.ascontiguousarray(src, dtype=np.intc), np.ascontiguousarray(dst, dtype=np.intc)
         assert s.ndim == 1 and s.shape == d.shape, (s.shape, d.shape)
-        g = t = None
-        if gain is not None:
-            g = np.ascontiguousarray(gain, dtype=np.float32)
-            assert g.shape == (len(s), 2), g.shape
-        if through is not None:
-            n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
-            t = np.ascontiguousarray(through, dtype=np.float32)
-            assert t.shape == (n_buses, 2), t.shape
-        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
-        _check(lib.srack_buses_set_sends(self.h, len(s), s.ctypes.data_as(ip), d.ctypes.data_as(ip), None if g is None else g.ctypes.data_as(fp),
-                                         None if t is None else t.ctypes.data_as(fp)))
+        _, g = _opt(gain, np.float32, (len(s), 2))
+        t = None if through is None else _opt(through, np.float32, (self.n_buses(), 2))[1]
+        ip = C.POINTER(C.c_int)
+        _check(lib.srack_buses_set_sends(self.h, len(s), s.ctypes.data_as(ip), d.ctypes.data_as(ip), g, t))
 
     def get_sends(self):
         """-> (src int32 [n_sends], dst int32 [n_sends], gain f32 [n_sends][2], through f32 [n_buses][2]), or None when no sends are set"""
         n = _check(lib.srack_buses_get_sends(self.h, None, None, None, 0, None, 0))
         if n == 0:
             return None
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        n_buses = self.n_buses()
         s, d = np.empty(n, dtype=np.intc), np.empty(n, dtype=np.intc)
         g, t = np.empty((n, 2), dtype=np.float32), np.empty((n_buses, 2), dtype=np.float32)
         ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
@@ -687,7 +693,7 @@ class Patch:
         n = _check(lib.srack_buses_get_sends(self.h, None, None, None, 0, None, 0))
         if n == 0:
             return None
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        n_buses = self.n_buses()
         nt, order = np.zeros(n_buses, dtype=np.intc), np.zeros(n, dtype=np.intc)
         ip = C.POINTER(C.c_int)
         runs = _check(lib.srack_buses_send_plan(self.h, nt.ctypes.data_as(ip), n_buses, order.ctypes.data_as(ip), n))
@@ -701,45 +707,24 @@ class Patch:
         """Convenience for tests: rows f32 [n_buses][row_channels][T] from the host through the sends -> f32 of the same shape
         (channels beyond the second are not written: they come back as zeros, which is what the output buffer is filled with)."""
         x = np.ascontiguousarray(rows, dtype=np.float32)
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
-        assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
+        assert x.ndim == 3 and x.shape[0] == self.n_buses(), x.shape
         out = np.zeros_like(x)
-        d_in, d_out = C.c_void_p(), C.c_void_p()
-        try:
-            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
-            _check(lib.srack_device_alloc(C.byref(d_out), max(4, out.nbytes)))
-            if x.nbytes:
-                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
-                _check(lib.srack_device_from_host(d_out, out.ctypes.data_as(C.c_void_p), out.nbytes, None))
+        with DeviceScope() as dev:
+            d_in, d_out = dev.upload(x), dev.upload(out)
             self.send_raw(x.shape[2], d_in, x.shape[1], d_out, None)
-            if out.nbytes:
-                _check(lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), d_out, out.nbytes, None))
-            _check(lib.srack_device_sync(None))
-            return out
-        finally:
-            for d in (d_in, d_out):
-                if d.value:
-                    lib.srack_device_free(d)
+            dev.download(out, d_out)
+        return out
 
     # ---- bus filters: a Moog ladder per mix bus, behind the mixer -----------------------------------------
     def set_bus_filter(self, params=None, port=None, enabled=None):
         """srack_buses_set_filter: params f32 [n_buses][3] = FREQ, RES, EXP_AMT, any f32 (None: the module's defaults), port int [n_buses]
         VCF_OUT_* (None: lowpass), enabled [n_buses] (None: every bus).  Calling it again is the slider: parameters change, state stays.
         Not part of the program: restarts nothing."""
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
-        a = po = e = None
-        if params is not None:
-            a = np.ascontiguousarray(params, dtype=np.float32)
-            assert a.shape == (n_buses, BUS_FILTER_NPARAMS), a.shape
-        if port is not None:
-            po = np.ascontiguousarray(port, dtype=np.intc)
-            assert po.shape == (n_buses,), po.shape
-        if enabled is not None:
-            e = np.ascontiguousarray(np.asarray(enabled) != 0, dtype=np.intc)
-            assert e.shape == (n_buses,), e.shape
-        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
-        _check(lib.srack_buses_set_filter(self.h, None if a is None else a.ctypes.data_as(fp), None if po is None else po.ctypes.data_as(ip),
-                                          None if e is None else e.ctypes.data_as(ip)))
+        n_buses = self.n_buses()
+        _, a = _opt(params, np.float32, (n_buses, BUS_FILTER_NPARAMS))
+        _, po = _opt(port, np.intc, (n_buses,))
+        _, e = _opt(_truth(enabled), np.intc, (n_buses,))
+        _check(lib.srack_buses_set_filter(self.h, a, po, e))
 
     def get_bus_filter(self):
         """-> (n_buses, params f32 [n_buses][3], port int32 [n_buses], enabled int32 [n_buses]); (0, None, None, None) when no filters are set"""
@@ -772,57 +757,41 @@ class Patch:
         """Convenience for tests: rows f32 [n_buses][row_channels][T] (and cv f32 [n_buses][T]) from the host through the filters -> f32 of
         the shape of rows.  Out of place the output buffer starts as zeros, which is what channels beyond the second come back as; in
         place they come back as they went in."""
+        return self._bus_stage(self.bus_filter_raw, rows, cv, in_place)[0]
+
+    def _bus_stage(self, raw, rows, side, in_place, env=None):
+        """The filters', the VCAs' and the shapers' convenience call: rows, the optional `side` row (a CV, a control) and, where env is
+        not None, the stage's extra output row (fetched when env is true) through `raw` -> (out, the extra row or None).  Both outputs
+        start as zeros on the device."""
         x = np.ascontiguousarray(rows, dtype=np.float32)
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        n_buses = self.n_buses()
         assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
-        c = None
-        if cv is not None:
-            c = np.ascontiguousarray(cv, dtype=np.float32)
-            assert c.shape == (n_buses, x.shape[2]), c.shape
+        T = x.shape[2]
+        c, _ = _opt(side, np.float32, (n_buses, T))
         out = np.zeros_like(x)
-        d_in, d_out, d_cv = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        try:
-            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
-            if not in_place:
-                _check(lib.srack_device_alloc(C.byref(d_out), max(4, out.nbytes)))
-            if c is not None:
-                _check(lib.srack_device_alloc(C.byref(d_cv), max(4, c.nbytes)))
-            if x.nbytes:
-                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
-                if not in_place:
-                    _check(lib.srack_device_from_host(d_out, out.ctypes.data_as(C.c_void_p), out.nbytes, None))
-                if c is not None:
-                    _check(lib.srack_device_from_host(d_cv, c.ctypes.data_as(C.c_void_p), c.nbytes, None))
-            to = d_in if in_place else d_out
-            self.bus_filter_raw(x.shape[2], d_in, x.shape[1], d_cv if c is not None else None, to, None)
-            if out.nbytes:
-                _check(lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), to, out.nbytes, None))
-            _check(lib.srack_device_sync(None))
-            return out
-        finally:
-            for d in (d_in, d_out, d_cv):
-                if d.value:
-                    lib.srack_device_free(d)
+        extra = np.zeros((n_buses, T), dtype=np.float32) if env else None
+        with DeviceScope() as dev:
+            d_in = dev.upload(x)
+            d_out = d_in if in_place else dev.upload(out)
+            d_side = None if c is None else dev.upload(c)
+            d_extra = None if extra is None else dev.upload(extra)
+            tail = () if env is None else (d_extra,)
+            raw(T, d_in, x.shape[1], d_side, d_out, *tail, None)
+            dev.download(out, d_out)
+            if extra is not None:
+                dev.download(extra, d_extra)
+        return out, extra
 
     # ---- bus VCAs: an ADSR and a VCA per mix bus, behind the mixer ------------------------------------------
     def set_bus_vca(self, params=None, mode=None, negative=None):
         """srack_buses_set_vca: params f32 [n_buses][4] = A_SEC, D_SEC, S_VAL, R_SEC, any f32 (None: the module's defaults), mode int
         [n_buses] BUS_VCA_OFF / _CV / _GATE (None: every bus GATE), negative [n_buses] (None: false).  Calling it again is the slider:
         sliders change, state stays; a bus that becomes GATE starts fresh.  Not part of the program: restarts nothing."""
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
-        a = mo = ng = None
-        if params is not None:
-            a = np.ascontiguousarray(params, dtype=np.float32)
-            assert a.shape == (n_buses, BUS_VCA_NPARAMS), a.shape
-        if mode is not None:
-            mo = np.ascontiguousarray(mode, dtype=np.intc)
-            assert mo.shape == (n_buses,), mo.shape
-        if negative is not None:
-            ng = np.ascontiguousarray(np.asarray(negative) != 0, dtype=np.intc)
-            assert ng.shape == (n_buses,), ng.shape
-        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
-        _check(lib.srack_buses_set_vca(self.h, None if a is None else a.ctypes.data_as(fp), None if mo is None else mo.ctypes.data_as(ip),
-                                       None if ng is None else ng.ctypes.data_as(ip)))
+        n_buses = self.n_buses()
+        _, a = _opt(params, np.float32, (n_buses, BUS_VCA_NPARAMS))
+        _, mo = _opt(mode, np.intc, (n_buses,))
+        _, ng = _opt(_truth(negative), np.intc, (n_buses,))
+        _check(lib.srack_buses_set_vca(self.h, a, mo, ng))
 
     def get_bus_vca(self):
         """-> (n_buses, params f32 [n_buses][4], mode int32 [n_buses], negative int32 [n_buses]); (0, None, None, None) when no VCAs are set"""
@@ -855,60 +824,18 @@ class Patch:
         """Convenience for tests: rows f32 [n_buses][row_channels][T] (and ctl f32 [n_buses][T]) from the host through the VCAs -> f32 of
         the shape of rows, or (that, env f32 [n_buses][T]) when want_env.  Out of place the output buffer starts as zeros, which is what
         channels beyond the second come back as; in place they come back as they went in."""
-        x = np.ascontiguousarray(rows, dtype=np.float32)
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
-        assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
-        c = None
-        if ctl is not None:
-            c = np.ascontiguousarray(ctl, dtype=np.float32)
-            assert c.shape == (n_buses, x.shape[2]), c.shape
-        out = np.zeros_like(x)
-        env = np.zeros((n_buses, x.shape[2]), dtype=np.float32)
-        d_in, d_out, d_ctl, d_env = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-        try:
-            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
-            if not in_place:
-                _check(lib.srack_device_alloc(C.byref(d_out), max(4, out.nbytes)))
-            if c is not None:
-                _check(lib.srack_device_alloc(C.byref(d_ctl), max(4, c.nbytes)))
-            if want_env:
-                _check(lib.srack_device_alloc(C.byref(d_env), max(4, env.nbytes)))
-            if x.nbytes:
-                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
-                if not in_place:
-                    _check(lib.srack_device_from_host(d_out, out.ctypes.data_as(C.c_void_p), out.nbytes, None))
-                if c is not None:
-                    _check(lib.srack_device_from_host(d_ctl, c.ctypes.data_as(C.c_void_p), c.nbytes, None))
-                if want_env:
-                    _check(lib.srack_device_from_host(d_env, env.ctypes.data_as(C.c_void_p), env.nbytes, None))
-            to = d_in if in_place else d_out
-            self.bus_vca_raw(x.shape[2], d_in, x.shape[1], d_ctl if c is not None else None, to, d_env if want_env else None, None)
-            if out.nbytes:
-                _check(lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), to, out.nbytes, None))
-                if want_env:
-                    _check(lib.srack_device_to_host(env.ctypes.data_as(C.c_void_p), d_env, env.nbytes, None))
-            _check(lib.srack_device_sync(None))
-            return (out, env) if want_env else out
-        finally:
-            for d in (d_in, d_out, d_ctl, d_env):
-                if d.value:
-                    lib.srack_device_free(d)
+        out, env = self._bus_stage(self.bus_vca_raw, rows, ctl, in_place, env=bool(want_env))
+        return (out, env) if want_env else out
 
     # ---- bus shapers: a drive, a waveshaper and a make-up gain per mix bus, behind the mixer ----------------
     def set_bus_shaper(self, params=None, mode=None):
         """srack_buses_set_shaper: params f32 [n_buses][3] = PRE, EXPONENT, POST, any f32 (None: 1, 1, 1), mode int [n_buses]
         BUS_SHAPER_OFF / _CONST / _CV (None: every bus CONST).  Calling it again is the slider; there is no state.  Not part of the
         program: restarts nothing."""
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
-        a = mo = None
-        if params is not None:
-            a = np.ascontiguousarray(params, dtype=np.float32)
-            assert a.shape == (n_buses, BUS_SHAPER_NPARAMS), a.shape
-        if mode is not None:
-            mo = np.ascontiguousarray(mode, dtype=np.intc)
-            assert mo.shape == (n_buses,), mo.shape
-        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
-        _check(lib.srack_buses_set_shaper(self.h, None if a is None else a.ctypes.data_as(fp), None if mo is None else mo.ctypes.data_as(ip)))
+        n_buses = self.n_buses()
+        _, a = _opt(params, np.float32, (n_buses, BUS_SHAPER_NPARAMS))
+        _, mo = _opt(mode, np.intc, (n_buses,))
+        _check(lib.srack_buses_set_shaper(self.h, a, mo))
 
     def get_bus_shaper(self):
         """-> (n_buses, params f32 [n_buses][3], mode int32 [n_buses]); (0, None, None) when no shapers are set"""
@@ -929,37 +856,7 @@ class Patch:
         """Convenience for tests: rows f32 [n_buses][row_channels][T] (and cv f32 [n_buses][T]) from the host through the shapers -> f32 of
         the shape of rows.  Out of place the output buffer starts as zeros, which is what channels beyond the second come back as; in
         place they come back as they went in."""
-        x = np.ascontiguousarray(rows, dtype=np.float32)
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
-        assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
-        c = None
-        if cv is not None:
-            c = np.ascontiguousarray(cv, dtype=np.float32)
-            assert c.shape == (n_buses, x.shape[2]), c.shape
-        out = np.zeros_like(x)
-        d_in, d_out, d_cv = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        try:
-            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
-            if not in_place:
-                _check(lib.srack_device_alloc(C.byref(d_out), max(4, out.nbytes)))
-            if c is not None:
-                _check(lib.srack_device_alloc(C.byref(d_cv), max(4, c.nbytes)))
-            if x.nbytes:
-                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
-                if not in_place:
-                    _check(lib.srack_device_from_host(d_out, out.ctypes.data_as(C.c_void_p), out.nbytes, None))
-                if c is not None:
-                    _check(lib.srack_device_from_host(d_cv, c.ctypes.data_as(C.c_void_p), c.nbytes, None))
-            to = d_in if in_place else d_out
-            self.bus_shaper_raw(x.shape[2], d_in, x.shape[1], d_cv if c is not None else None, to, None)
-            if out.nbytes:
-                _check(lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), to, out.nbytes, None))
-            _check(lib.srack_device_sync(None))
-            return out
-        finally:
-            for d in (d_in, d_out, d_cv):
-                if d.value:
-                    lib.srack_device_free(d)
+        return self._bus_stage(self.bus_shaper_raw, rows, cv, in_place)[0]
 
     # ---- bus meters: windowed level tracks and totals per mix bus, a read-only tap on bus rows ---------------
     def bus_meter_raw(self, first_sample, n_samples, d_rows, row_channels, window, d_levels, n_windows, d_totals, stream=None):
@@ -973,7 +870,7 @@ class Patch:
         continue from (a copy comes back), None for zeros over ceil((first_sample + T) / window) windows.  totals f64
         [STAT_COUNT][n_buses][2] to continue from, None for zeros, False for no totals (None comes back)."""
         x = np.ascontiguousarray(rows, dtype=np.float32)
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        n_buses = self.n_buses()
         assert x.ndim == 3 and x.shape[0] == n_buses, x.shape
         T = x.shape[2]
         lv = tt = None
@@ -985,26 +882,14 @@ class Patch:
         if totals is not False:
             tt = np.zeros((STAT_COUNT, n_buses, 2)) if totals is None else np.array(totals, dtype=np.float64, order="C", copy=True)
             assert tt.shape == (STAT_COUNT, n_buses, 2), tt.shape
-        d_in, d_lv, d_tt = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        try:
-            _check(lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes)))
-            if x.nbytes:
-                _check(lib.srack_device_from_host(d_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None))
+        with DeviceScope() as dev:
+            d_in = dev.upload(x)
+            d_lv, d_tt = (None if a is None else dev.upload(a) for a in (lv, tt))
+            self.bus_meter_raw(first_sample, T, d_in, x.shape[1], 0 if lv is None else window, d_lv, 0 if lv is None else lv.shape[0], d_tt, None)
             for a, d in ((lv, d_lv), (tt, d_tt)):
                 if a is not None:
-                    _check(lib.srack_device_alloc(C.byref(d), a.nbytes))
-                    _check(lib.srack_device_from_host(d, a.ctypes.data_as(C.c_void_p), a.nbytes, None))
-            self.bus_meter_raw(first_sample, T, d_in, x.shape[1], 0 if lv is None else window, d_lv if lv is not None else None,
-                               0 if lv is None else lv.shape[0], d_tt if tt is not None else None, None)
-            for a, d in ((lv, d_lv), (tt, d_tt)):
-                if a is not None:
-                    _check(lib.srack_device_to_host(a.ctypes.data_as(C.c_void_p), d, a.nbytes, None))
-            _check(lib.srack_device_sync(None))
-            return lv, tt
-        finally:
-            for d in (d_in, d_lv, d_tt):
-                if d.value:
-                    lib.srack_device_free(d)
+                    dev.download(a, d)
+        return lv, tt
 
     def get_voice_field(self, module, field):
         out = np.empty(self.n_voices, dtype=np.float64)
@@ -1060,30 +945,28 @@ class Patch:
         renders, copies back.  -> (frames [planes][T][V] f32 or None, mix [C][T] f32 or None)."""
         if self.n_voices == 0:
             self.configure_voices(1)
+        return self._render(n_samples, frames, mix, flags)[:2]
+
+    def _render(self, n_samples, frames, mix, flags, st=None, bm=None):
+        """render, render_stats and render_buses: the frames and the mix where asked for, the statistics `st` to continue from (they are
+        written) and the bus mixes into `bm`, each where given -> (frames or None, mix or None, st, bm)"""
         n_planes, _ = self.planes()
         V, T, Cn = self.n_voices, n_samples, self.channels
-        d_fr, d_mx = C.c_void_p(), C.c_void_p()
-        try:
-            if frames and n_planes > 0:
-                _check(lib.srack_device_alloc(C.byref(d_fr), max(1, n_planes * T * V * 4)))
-            if mix:
-                _check(lib.srack_device_alloc(C.byref(d_mx), max(1, Cn * T * 4)))
-            self.render_raw(T, d_fr if d_fr.value else None, d_mx if d_mx.value else None, flags, None)
-            fr = mx = None
-            if frames:
-                fr = np.zeros((n_planes, T, V), dtype=np.float32)
-                if d_fr.value:
-                    _check(lib.srack_device_to_host(fr.ctypes.data_as(C.c_void_p), d_fr, fr.nbytes, None))
-            if mix:
-                mx = np.empty((Cn, T), dtype=np.float32)
-                _check(lib.srack_device_to_host(mx.ctypes.data_as(C.c_void_p), d_mx, mx.nbytes, None))
-            _check(lib.srack_device_sync(None))
-            return fr, mx
-        finally:
-            if d_fr.value:
-                lib.srack_device_free(d_fr)
-            if d_mx.value:
-                lib.srack_device_free(d_mx)
+        fr = np.zeros((n_planes, T, V), dtype=np.float32) if frames else None
+        mx = np.empty((Cn, T), dtype=np.float32) if mix else None
+        with DeviceScope() as dev:
+            d_fr = dev.alloc(fr.nbytes) if frames and n_planes > 0 else None   # (without planes there is nothing to write: zeros come back)
+            d_mx = dev.alloc(mx.nbytes) if mix else None
+            d_st = None if st is None else dev.upload(st)
+            d_bm = None if bm is None else dev.alloc(bm.nbytes)
+            if bm is None:
+                self.render_raw(T, d_fr, d_mx, flags, None, d_st)
+            else:
+                self.render_buses_raw(T, d_bm, d_fr, d_mx, d_st, flags, None)
+            for a, d in ((fr, d_fr), (mx, d_mx), (st, d_st), (bm, d_bm)):
+                if d is not None:
+                    dev.download(a, d)
+        return fr, mx, st, bm
 
     def render_stats(self, n_samples, frames=False, mix=False, flags=0, stats=None):
         """render() plus per-voice statistics of every plane -> (frames or None, mix or None, stats f64 [planes][STAT_COUNT][V]).
@@ -1091,74 +974,19 @@ class Patch:
         STAT_NONFINITE, STAT_CLIPPED (include/srack_hip.h)."""
         if self.n_voices == 0:
             self.configure_voices(1)
-        n_planes, _ = self.planes()
-        V, T, Cn = self.n_voices, n_samples, self.channels
-        st = np.zeros((n_planes, STAT_COUNT, V)) if stats is None else np.array(stats, dtype=np.float64, order="C", copy=True)
-        assert st.shape == (n_planes, STAT_COUNT, V), st.shape
-        d_fr, d_mx, d_st = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        try:
-            if frames and n_planes > 0:
-                _check(lib.srack_device_alloc(C.byref(d_fr), max(1, n_planes * T * V * 4)))
-            if mix:
-                _check(lib.srack_device_alloc(C.byref(d_mx), max(1, Cn * T * 4)))
-            _check(lib.srack_device_alloc(C.byref(d_st), max(8, st.nbytes)))
-            _check(lib.srack_device_from_host(d_st, st.ctypes.data_as(C.c_void_p), st.nbytes, None))
-            self.render_raw(T, d_fr if d_fr.value else None, d_mx if d_mx.value else None, flags, None, d_st)
-            fr = mx = None
-            if frames:
-                fr = np.zeros((n_planes, T, V), dtype=np.float32)
-                if d_fr.value:
-                    _check(lib.srack_device_to_host(fr.ctypes.data_as(C.c_void_p), d_fr, fr.nbytes, None))
-            if mix:
-                mx = np.empty((Cn, T), dtype=np.float32)
-                _check(lib.srack_device_to_host(mx.ctypes.data_as(C.c_void_p), d_mx, mx.nbytes, None))
-            _check(lib.srack_device_to_host(st.ctypes.data_as(C.c_void_p), d_st, st.nbytes, None))
-            _check(lib.srack_device_sync(None))
-            return fr, mx, st
-        finally:
-            for d in (d_fr, d_mx, d_st):
-                if d.value:
-                    lib.srack_device_free(d)
+        shape = (self.planes()[0], STAT_COUNT, self.n_voices)
+        st = np.zeros(shape) if stats is None else np.array(stats, dtype=np.float64, order="C", copy=True)
+        assert st.shape == shape, st.shape
+        return self._render(n_samples, frames, mix, flags, st)[:3]
 
     def render_buses(self, n_samples, frames=False, mix=False, stats=False, flags=0):
         """render_stats() plus the bus mixes of the table set with set_buses -> (frames or None, mix or None, stats or None — from zeros —,
         bus_mix f32 [n_buses][channels][T])."""
-        n_buses = _check(lib.srack_voices_get_buses(self.h, None, None, 0))
+        n_buses = self.n_buses()
         if n_buses == 0:
             raise SrackError(ERR_STATE, "render_buses: no mix table set (set_buses)")
-        n_planes, _ = self.planes()
-        V, T, Cn = self.n_voices, n_samples, self.channels
-        bm = np.empty((n_buses, Cn, T), dtype=np.float32)
-        st = np.zeros((n_planes, STAT_COUNT, V)) if stats else None
-        d_fr, d_mx, d_st, d_bm = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-        try:
-            if frames and n_planes > 0:
-                _check(lib.srack_device_alloc(C.byref(d_fr), max(1, n_planes * T * V * 4)))
-            if mix:
-                _check(lib.srack_device_alloc(C.byref(d_mx), max(1, Cn * T * 4)))
-            if stats:
-                _check(lib.srack_device_alloc(C.byref(d_st), max(8, st.nbytes)))
-                _check(lib.srack_device_from_host(d_st, st.ctypes.data_as(C.c_void_p), st.nbytes, None))
-            _check(lib.srack_device_alloc(C.byref(d_bm), max(4, bm.nbytes)))
-            self.render_buses_raw(T, d_bm, d_fr if d_fr.value else None, d_mx if d_mx.value else None, d_st if d_st.value else None, flags, None)
-            fr = mx = None
-            if frames:
-                fr = np.zeros((n_planes, T, V), dtype=np.float32)
-                if d_fr.value:
-                    _check(lib.srack_device_to_host(fr.ctypes.data_as(C.c_void_p), d_fr, fr.nbytes, None))
-            if mix:
-                mx = np.empty((Cn, T), dtype=np.float32)
-                _check(lib.srack_device_to_host(mx.ctypes.data_as(C.c_void_p), d_mx, mx.nbytes, None))
-            if stats:
-                _check(lib.srack_device_to_host(st.ctypes.data_as(C.c_void_p), d_st, st.nbytes, None))
-            if bm.nbytes:
-                _check(lib.srack_device_to_host(bm.ctypes.data_as(C.c_void_p), d_bm, bm.nbytes, None))
-            _check(lib.srack_device_sync(None))
-            return fr, mx, st, bm
-        finally:
-            for d in (d_fr, d_mx, d_st, d_bm):
-                if d.value:
-                    lib.srack_device_free(d)
+        st = np.zeros((self.planes()[0], STAT_COUNT, self.n_voices)) if stats else None
+        return self._render(n_samples, frames, mix, flags, st, np.empty((n_buses, self.channels, n_samples), dtype=np.float32))
 
     def render_channels(self, n_samples, flags=0):
         """-> [channels][T][V] f32 (planes expanded to channels, silence for unconnected ones)."""

@@ -855,6 +855,22 @@ static int need_rows(const char* who, const void* d_rows, const void* d_out, con
 // do na bytes at a and nb bytes at b overlap
 static bool meet(const void* a, uint64_t na, const void* b, uint64_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
 
+// a stage that may work in place: its d_out is d_rows itself or disjoint from it
+static int need_in_place_or_apart(const char* who, const void* d_rows, const void* d_out, uint64_t bytes)
+{
+    if (d_rows == d_out || !meet(d_rows, bytes, d_out, bytes)) return SRACK_OK;
+    set_error(std::string(who) + ": d_out overlaps d_rows in part: it must be d_rows itself or disjoint from it");
+    return SRACK_ERR_INVALID;
+}
+
+// the buffers `a` and `b` of a stage, either of which may be absent: "<a> overlaps <b>"
+static int need_apart(const char* who, const char* a_name, const void* a, uint64_t na, const char* b_name, const void* b, uint64_t nb)
+{
+    if (!a || !b || !meet(a, na, b, nb)) return SRACK_OK;
+    set_error(std::string(who) + ": " + a_name + " overlaps " + b_name);
+    return SRACK_ERR_INVALID;
+}
+
 // ---- the bus reverbs ---------------------------------------------------------------------------------------------
 static const double kFvDefaults[SRACK_FREEVERB__NFIELDS] = {0.5, 0.0, 1.0, 0.5, 0.5, 0.0};  // FreeverbModule::new (freeverb.rs:36-60), in field order
 
@@ -1248,14 +1264,8 @@ int srack_buses_filter(srack_patch* p, uint32_t n_samples, const float* d_rows, 
         if (n_samples == 0) return SRACK_OK;
         if ((rc = need_rows("buses_filter", d_rows, d_out, "d_out", row_channels)) != SRACK_OK) return rc;
         const uint64_t bytes = 4ull * h.n_buses * row_channels * n_samples, cv_bytes = 4ull * h.n_buses * n_samples;
-        if (d_rows != d_out && meet(d_rows, bytes, d_out, bytes)) {
-            set_error("buses_filter: d_out overlaps d_rows in part: it must be d_rows itself or disjoint from it");
-            return SRACK_ERR_INVALID;
-        }
-        if (d_cv && meet(d_cv, cv_bytes, d_out, bytes)) {
-            set_error("buses_filter: d_cv overlaps d_out");
-            return SRACK_ERR_INVALID;
-        }
+        if ((rc = need_in_place_or_apart("buses_filter", d_rows, d_out, bytes)) != SRACK_OK) return rc;
+        if ((rc = need_apart("buses_filter", "d_cv", d_cv, cv_bytes, "d_out", d_out, bytes)) != SRACK_OK) return rc;
         return device_buses_filter(h, n_samples, d_rows, row_channels, d_cv, d_out, stream);
     });
 }
@@ -1346,22 +1356,11 @@ int srack_buses_vca(srack_patch* p, uint32_t n_samples, const float* d_rows, uin
         if (n_samples == 0) return SRACK_OK;
         if ((rc = need_rows("buses_vca", d_rows, d_out, "d_out", row_channels)) != SRACK_OK) return rc;
         const uint64_t bytes = 4ull * h.n_buses * row_channels * n_samples, row_bytes = 4ull * h.n_buses * n_samples;
-        if (d_rows != d_out && meet(d_rows, bytes, d_out, bytes)) {
-            set_error("buses_vca: d_out overlaps d_rows in part: it must be d_rows itself or disjoint from it");
-            return SRACK_ERR_INVALID;
-        }
-        if (d_ctl && meet(d_ctl, row_bytes, d_out, bytes)) {
-            set_error("buses_vca: d_ctl overlaps d_out");
-            return SRACK_ERR_INVALID;
-        }
-        if (d_env && (meet(d_env, row_bytes, d_out, bytes) || meet(d_env, row_bytes, d_rows, bytes))) {
-            set_error(std::string("buses_vca: d_env overlaps ") + (meet(d_env, row_bytes, d_out, bytes) ? "d_out" : "d_rows"));
-            return SRACK_ERR_INVALID;
-        }
-        if (d_env && d_ctl && meet(d_env, row_bytes, d_ctl, row_bytes)) {
-            set_error("buses_vca: d_env overlaps d_ctl");
-            return SRACK_ERR_INVALID;
-        }
+        if ((rc = need_in_place_or_apart("buses_vca", d_rows, d_out, bytes)) != SRACK_OK) return rc;
+        if ((rc = need_apart("buses_vca", "d_ctl", d_ctl, row_bytes, "d_out", d_out, bytes)) != SRACK_OK) return rc;
+        if ((rc = need_apart("buses_vca", "d_env", d_env, row_bytes, "d_out", d_out, bytes)) != SRACK_OK) return rc;
+        if ((rc = need_apart("buses_vca", "d_env", d_env, row_bytes, "d_rows", d_rows, bytes)) != SRACK_OK) return rc;
+        if ((rc = need_apart("buses_vca", "d_env", d_env, row_bytes, "d_ctl", d_ctl, row_bytes)) != SRACK_OK) return rc;
         return device_buses_vca(h, n_samples, d_rows, row_channels, d_ctl, d_out, d_env, stream);
     });
 }
@@ -1423,14 +1422,8 @@ int srack_buses_shaper(srack_patch* p, uint32_t n_samples, const float* d_rows, 
         if (n_samples == 0) return SRACK_OK;
         if ((rc = need_rows("buses_shaper", d_rows, d_out, "d_out", row_channels)) != SRACK_OK) return rc;
         const uint64_t bytes = 4ull * h.n_buses * row_channels * n_samples, cv_bytes = 4ull * h.n_buses * n_samples;
-        if (d_rows != d_out && meet(d_rows, bytes, d_out, bytes)) {
-            set_error("buses_shaper: d_out overlaps d_rows in part: it must be d_rows itself or disjoint from it");
-            return SRACK_ERR_INVALID;
-        }
-        if (d_cv && meet(d_cv, cv_bytes, d_out, bytes)) {
-            set_error("buses_shaper: d_cv overlaps d_out");
-            return SRACK_ERR_INVALID;
-        }
+        if ((rc = need_in_place_or_apart("buses_shaper", d_rows, d_out, bytes)) != SRACK_OK) return rc;
+        if ((rc = need_apart("buses_shaper", "d_cv", d_cv, cv_bytes, "d_out", d_out, bytes)) != SRACK_OK) return rc;
         return device_buses_shaper(h, n_samples, d_rows, row_channels, d_cv, d_out, stream);
     });
 }

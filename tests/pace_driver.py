@@ -4,7 +4,6 @@ The test compares the .npz of SRACK_PACE=1 with that of SRACK_PACE=0 bit for bit
 
     python tests/pace_driver.py <case> <flags> <out.npz>
 """
-import ctypes as C
 import os
 import sys
 
@@ -60,19 +59,13 @@ def main():
     if case == "grid":
         from tests.test_gpu_parity import read_plane
         p, ids, V = patches[0]
-        d_fr, d_mx = C.c_void_p(), C.c_void_p()
-        assert S.lib.srack_device_alloc(C.byref(d_fr), T * V * 4) == 0
-        assert S.lib.srack_device_alloc(C.byref(d_mx), 2 * T * 4) == 0
-        try:
-            p.render_raw(T, d_fr.value, d_mx.value, flags, None)
+        mix = np.empty((2, T), np.float32)
+        with S.DeviceScope() as dev:
+            d_fr, d_mx = dev.alloc(T * V * 4), dev.alloc(mix.nbytes)
+            p.render_raw(T, d_fr, d_mx, flags, None)
             assert S.lib.srack_device_sync(None) == 0
-            got, own, scale = read_plane(S, d_fr.value, T, V, grid_pick(V))
-            mix = np.empty((2, T), np.float32)
-            assert S.lib.srack_device_to_host(mix.ctypes.data_as(C.c_void_p), d_mx, mix.nbytes, None) == 0
-            assert S.lib.srack_device_sync(None) == 0
-        finally:
-            S.lib.srack_device_free(d_fr)
-            S.lib.srack_device_free(d_mx)
+            got, own, scale = read_plane(S, d_fr, T, V, grid_pick(V))
+            dev.download(mix, d_mx)
         out.update(p0_fr0=got, p0_own0=own, p0_scale0=scale, p0_mx0=mix)
         infos.append(p.info())
     else:

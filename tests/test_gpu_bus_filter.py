@@ -84,37 +84,22 @@ def run_raw(S, p, rows, cv=None, in_place=False, off_rows=0, off_cv=0, off_out=0
     """srack_buses_filter with d_rows, d_cv and d_out `off_*` floats into their allocations.  Out of place d_out holds SENTINEL beforehand
     (it comes back wherever the call did not write); one GUARD float lies behind the output either way.
     -> (out of rows' shape, the guard as it came back)"""
-    lib = S.lib
     x = np.ascontiguousarray(rows, dtype=np.float32)
     buf = np.full(x.size + 1, SENTINEL, dtype=np.float32)
     if in_place:
         buf[:-1] = x.ravel()
     buf[-1] = GUARD
-    d_in, d_out, d_cv = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    try:
-        assert lib.srack_device_alloc(C.byref(d_out), buf.nbytes + 4 * off_out) == 0
-        a_out = d_out.value + 4 * off_out
-        assert lib.srack_device_from_host(a_out, buf.ctypes.data_as(C.c_void_p), buf.nbytes, None) == 0
-        a_in = a_out
-        if not in_place:
-            assert lib.srack_device_alloc(C.byref(d_in), x.nbytes + 4 * off_rows) == 0
-            a_in = d_in.value + 4 * off_rows
-            assert lib.srack_device_from_host(a_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None) == 0
-        a_cv = None
-        if cv is not None:
-            c = np.ascontiguousarray(cv, dtype=np.float32)
-            assert c.shape == (x.shape[0], x.shape[2])
-            assert lib.srack_device_alloc(C.byref(d_cv), c.nbytes + 4 * off_cv) == 0
-            a_cv = d_cv.value + 4 * off_cv
-            assert lib.srack_device_from_host(a_cv, c.ctypes.data_as(C.c_void_p), c.nbytes, None) == 0
+    c = None
+    if cv is not None:
+        c = np.ascontiguousarray(cv, dtype=np.float32)
+        assert c.shape == (x.shape[0], x.shape[2])
+    with S.DeviceScope() as dev:
+        a_out = dev.upload(buf, off_out)
+        a_in = a_out if in_place else dev.upload(x, off_rows)
+        a_cv = None if c is None else dev.upload(c, off_cv)
         p.bus_filter_raw(x.shape[2], a_in, x.shape[1], a_cv, a_out, None)
-        assert lib.srack_device_to_host(buf.ctypes.data_as(C.c_void_p), a_out, buf.nbytes, None) == 0
-        assert lib.srack_device_sync(None) == 0
-        return buf[:-1].reshape(x.shape), buf[-1]
-    finally:
-        for d in (d_in, d_out, d_cv):
-            if d.value:
-                lib.srack_device_free(d)
+        dev.download(buf, a_out)
+    return buf[:-1].reshape(x.shape), buf[-1]
 
 
 # ---- 1. against the reference: partial and full waves and tiles ---------------------------------------------------------------------------
@@ -216,11 +201,10 @@ def test_overlaps_are_refused(S):
     n_buses, T = 3, 16
     p = host(S, n_buses)
     p.set_bus_filter()
-    d = C.c_void_p()
     nbytes, cvbytes = n_buses * 2 * T * 4, n_buses * T * 4
-    assert S.lib.srack_device_alloc(C.byref(d), 4 * nbytes) == 0
-    try:
-        base = d.value + nbytes
+    with S.DeviceScope() as dev:
+        d = dev.alloc(4 * nbytes)
+        base = d + nbytes
         for d_out in (base + 4, base - 4, base + nbytes - 4, base - nbytes + 4):
             assert S.lib.srack_buses_filter(p.h, T, base, 2, None, d_out, None) == S.ERR_INVALID, d_out - base
         for d_cv in (base, base + nbytes - 4, base - cvbytes + 4):
@@ -228,11 +212,8 @@ def test_overlaps_are_refused(S):
             assert S.lib.srack_buses_filter(p.h, T, base + 2 * nbytes, 2, d_cv, base, None) == S.ERR_INVALID, d_cv - base
         assert "busvcf" not in p.info() and (p.bus_filter_state() == 0).all()   # nothing ran
         # neighbours are fine: d_out right behind d_rows, d_cv right behind d_out
-        assert S.lib.srack_device_from_host(d.value, np.zeros(nbytes, dtype=np.float32).ctypes.data_as(C.c_void_p), 4 * nbytes, None) == 0
-        assert S.lib.srack_buses_filter(p.h, T, d.value, 2, d.value + 2 * nbytes, d.value + nbytes, None) == S.OK
-        assert S.lib.srack_device_sync(None) == 0
-    finally:
-        S.lib.srack_device_free(d)
+        assert S.lib.srack_device_from_host(d, np.zeros(nbytes, dtype=np.float32).ctypes.data_as(C.c_void_p), 4 * nbytes, None) == 0
+        assert S.lib.srack_buses_filter(p.h, T, d, 2, d + 2 * nbytes, d + nbytes, None) == S.OK
 
 
 # ---- 6. special values are ordinary floats --------------------------------------------------------------------------------------------------

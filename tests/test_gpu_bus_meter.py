@@ -89,16 +89,10 @@ def start(n_windows, n_buses, seed, how):
 
 
 class Device:
-    """buffers of the library's own allocator"""
+    """buffers of a staging scope (S.DeviceScope, which frees them), sent and fetched at once, guard words behind them"""
 
-    def __init__(self, S):
-        self.lib, self.held = S.lib, []
-
-    def alloc(self, nbytes):
-        d = C.c_void_p()
-        assert self.lib.srack_device_alloc(C.byref(d), max(8, nbytes)) == 0
-        self.held.append(d)
-        return d.value
+    def __init__(self, S, scope):
+        self.lib, self.alloc = S.lib, scope.alloc
 
     def up(self, d, a, stream=None):
         a = np.ascontiguousarray(a)
@@ -125,11 +119,6 @@ class Device:
         assert (a[-4:].view(np.uint64) == np.full(4, GUARD).view(np.uint64)).all(), "a word behind the buffer was written"
         return a[:-4].reshape(shape)
 
-    def free(self):
-        for d in self.held:
-            self.lib.srack_device_free(d)
-        self.held = []
-
 
 def run(S, p, rows, window=None, first=0, levels=None, totals=None, cuts=None, off=0):
     """srack_buses_meter on `rows` in calls of `cuts` samples (None: one call), each call's rows an allocation of its own, `off` floats
@@ -137,8 +126,8 @@ def run(S, p, rows, window=None, first=0, levels=None, totals=None, cuts=None, o
     back.  Asserts that the rows come back unchanged and that the guard words behind both buffers stand."""
     x = np.ascontiguousarray(rows, dtype=np.float32)
     nb, rc, n = x.shape
-    dev = Device(S)
-    try:
+    with S.DeviceScope() as scope:
+        dev = Device(S, scope)
         d_lv = None if levels is None else dev.guarded(levels)
         d_tt = None if totals is None else dev.guarded(totals)
         at = 0
@@ -152,8 +141,6 @@ def run(S, p, rows, window=None, first=0, levels=None, totals=None, cuts=None, o
             at += m
         assert at == n
         return (None if levels is None else dev.back(d_lv, levels.shape)), (None if totals is None else dev.back(d_tt, totals.shape))
-    finally:
-        dev.free()
 
 
 def check(S, rows, window, first, how, n_extra=0, what="", cuts=None, off=0, outputs="both", seed=0):
@@ -295,21 +282,21 @@ def test_taps_around_a_shaper_on_one_stream(S):
     p = host(S, n_buses)
     p.set_bus_shaper(params, mode)
     hip, st = _stream()
-    dev = Device(S)
     try:
-        d_rows = dev.alloc(rows.nbytes)
-        dev.up(d_rows, rows, st)
-        d = [(dev.guarded(zl), dev.guarded(zt)) for _ in range(2)]
-        p.bus_meter_raw(0, n, d_rows, 2, WINDOW, d[0][0], n_windows, d[0][1], st)
-        p.bus_shaper_raw(n, d_rows, 2, None, d_rows, st)
-        p.bus_meter_raw(0, n, d_rows, 2, WINDOW, d[1][0], n_windows, d[1][1], st)
-        assert S.lib.srack_device_sync(st) == 0
-        for k, name in enumerate(("before the shaper", "behind the shaper")):
-            assert_same_words(dev.back(d[k][0], zl.shape), want[k][0], name + ": levels")
-            assert_same_words(dev.back(d[k][1], zt.shape), want[k][1], name + ": totals")
-        assert RSH.same_bits(dev.down(d_rows, rows.shape), shaped).all()   # the shaper's bits are what they are without the taps
+        with S.DeviceScope() as scope:
+            dev = Device(S, scope)
+            d_rows = dev.alloc(rows.nbytes)
+            dev.up(d_rows, rows, st)
+            d = [(dev.guarded(zl), dev.guarded(zt)) for _ in range(2)]
+            p.bus_meter_raw(0, n, d_rows, 2, WINDOW, d[0][0], n_windows, d[0][1], st)
+            p.bus_shaper_raw(n, d_rows, 2, None, d_rows, st)
+            p.bus_meter_raw(0, n, d_rows, 2, WINDOW, d[1][0], n_windows, d[1][1], st)
+            assert S.lib.srack_device_sync(st) == 0
+            for k, name in enumerate(("before the shaper", "behind the shaper")):
+                assert_same_words(dev.back(d[k][0], zl.shape), want[k][0], name + ": levels")
+                assert_same_words(dev.back(d[k][1], zt.shape), want[k][1], name + ": totals")
+            assert RSH.same_bits(dev.down(d_rows, rows.shape), shaped).all()   # the shaper's bits are what they are without the taps
     finally:
-        dev.free()
         assert hip.hipStreamDestroy(st) == 0
 
 
@@ -342,30 +329,30 @@ def test_a_tap_behind_every_stage_of_the_chain(S):
     p = CR.host(S, s)
     p.set_bus_shaper(spar, np.full(nb, RSH.CONST, dtype=np.intc))
     hip, st = _stream()
-    dev = Device(S)
     try:
-        d_rows, d_buf, d_fx, d_ctl = dev.alloc(rows.nbytes), dev.alloc(rows.nbytes), dev.alloc(rows.nbytes), dev.alloc(ctl.nbytes)
-        dev.up(d_rows, rows, st)
-        dev.up(d_ctl, ctl, st)
-        taps = [(dev.guarded(zl), dev.guarded(zt)) for _ in stages]
-        tap = lambda k, d: p.bus_meter_raw(first, n, d, 2, window, taps[k][0], n_windows, taps[k][1], st)
-        p.send_raw(n, d_rows, 2, d_buf, st)
-        tap(0, d_buf)
-        p.bus_filter_raw(n, d_buf, 2, d_ctl, d_buf, st)
-        tap(1, d_buf)
-        p.bus_vca_raw(n, d_buf, 2, d_ctl, d_buf, None, st)
-        tap(2, d_buf)
-        p.bus_shaper_raw(n, d_buf, 2, None, d_buf, st)
-        tap(3, d_buf)
-        p.bus_reverb_raw(n, d_buf, d_fx, st)
-        tap(4, d_fx)
-        assert S.lib.srack_device_sync(st) == 0
-        assert CR.same_bits(dev.down(d_fx, rows.shape), stages[-1]).all(), "the chain itself"
-        for k, name in enumerate(names):
-            assert_same_words(dev.back(taps[k][0], zl.shape), want[k][0], f"behind the {name}: levels")
-            assert_same_words(dev.back(taps[k][1], zt.shape), want[k][1], f"behind the {name}: totals")
+        with S.DeviceScope() as scope:
+            dev = Device(S, scope)
+            d_rows, d_buf, d_fx, d_ctl = dev.alloc(rows.nbytes), dev.alloc(rows.nbytes), dev.alloc(rows.nbytes), dev.alloc(ctl.nbytes)
+            dev.up(d_rows, rows, st)
+            dev.up(d_ctl, ctl, st)
+            taps = [(dev.guarded(zl), dev.guarded(zt)) for _ in stages]
+            tap = lambda k, d: p.bus_meter_raw(first, n, d, 2, window, taps[k][0], n_windows, taps[k][1], st)
+            p.send_raw(n, d_rows, 2, d_buf, st)
+            tap(0, d_buf)
+            p.bus_filter_raw(n, d_buf, 2, d_ctl, d_buf, st)
+            tap(1, d_buf)
+            p.bus_vca_raw(n, d_buf, 2, d_ctl, d_buf, None, st)
+            tap(2, d_buf)
+            p.bus_shaper_raw(n, d_buf, 2, None, d_buf, st)
+            tap(3, d_buf)
+            p.bus_reverb_raw(n, d_buf, d_fx, st)
+            tap(4, d_fx)
+            assert S.lib.srack_device_sync(st) == 0
+            assert CR.same_bits(dev.down(d_fx, rows.shape), stages[-1]).all(), "the chain itself"
+            for k, name in enumerate(names):
+                assert_same_words(dev.back(taps[k][0], zl.shape), want[k][0], f"behind the {name}: levels")
+                assert_same_words(dev.back(taps[k][1], zt.shape), want[k][1], f"behind the {name}: totals")
     finally:
-        dev.free()
         assert hip.hipStreamDestroy(st) == 0
 
 

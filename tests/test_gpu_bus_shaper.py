@@ -93,34 +93,18 @@ def run_raw(S, p, rows, cv=None, in_place=False, off_rows=0, off_cv=0, off_out=0
     if in_place:
         buf[:-1] = x.ravel()
     buf[-1] = GUARD
-    d_in, d_out, d_cv = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    try:
-        assert lib.srack_device_alloc(C.byref(d_out), buf.nbytes + 4 * off_out) == 0
-        a_out = d_out.value + 4 * off_out
-        assert lib.srack_device_from_host(a_out, buf.ctypes.data_as(C.c_void_p), buf.nbytes, None) == 0
-        a_in = a_out
-        if not in_place:
-            assert lib.srack_device_alloc(C.byref(d_in), max(4, x.nbytes) + 4 * off_rows) == 0
-            a_in = d_in.value + 4 * off_rows
-            if x.nbytes:
-                assert lib.srack_device_from_host(a_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None) == 0
-        a_cv = None
-        if cv is not None:
-            c = np.ascontiguousarray(cv, dtype=np.float32)
-            assert c.shape == (x.shape[0], x.shape[2])
-            assert lib.srack_device_alloc(C.byref(d_cv), max(4, c.nbytes) + 4 * off_cv) == 0
-            a_cv = d_cv.value + 4 * off_cv
-            if c.nbytes:
-                assert lib.srack_device_from_host(a_cv, c.ctypes.data_as(C.c_void_p), c.nbytes, None) == 0
+    c = None
+    if cv is not None:
+        c = np.ascontiguousarray(cv, dtype=np.float32)
+        assert c.shape == (x.shape[0], x.shape[2])
+    with S.DeviceScope(stream) as dev:
+        a_out = dev.upload(buf, off_out)
+        a_in = a_out if in_place else dev.upload(x, off_rows)
+        a_cv = None if c is None else dev.upload(c, off_cv)
         assert lib.srack_device_sync(None) == 0
         p.bus_shaper_raw(x.shape[2], a_in, x.shape[1], a_cv, a_out, stream)
-        assert lib.srack_device_to_host(buf.ctypes.data_as(C.c_void_p), a_out, buf.nbytes, stream) == 0
-        assert lib.srack_device_sync(stream) == 0
-        return buf[:-1].reshape(x.shape), buf[-1]
-    finally:
-        for d in (d_in, d_out, d_cv):
-            if d.value:
-                lib.srack_device_free(d)
+        dev.download(buf, a_out)
+    return buf[:-1].reshape(x.shape), buf[-1]
 
 
 def check_both_ways(S, rows, cv, params, mode, ref, what, off=0):
@@ -312,24 +296,17 @@ def test_set_shaper_between_calls_on_a_stream(S):
     assert all(np.isfinite(r).all() for r in refs) and all(np.count_nonzero(refs[k] != refs[k + 1]) > refs[k].size // 2 for k in range(7))
     lib, st = S.lib, C.c_void_p()
     assert hip.hipStreamCreateWithFlags(C.byref(st), 1) == 0   # hipStreamNonBlocking
-    d_in, d_cv, d_out = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    got = np.empty((8,) + rows.shape, dtype=np.float32)
     try:
-        assert lib.srack_device_alloc(C.byref(d_in), rows.nbytes) == 0 and lib.srack_device_alloc(C.byref(d_cv), cv.nbytes) == 0
-        assert lib.srack_device_alloc(C.byref(d_out), 8 * rows.nbytes) == 0
-        assert lib.srack_device_from_host(d_in, rows.ctypes.data_as(C.c_void_p), rows.nbytes, None) == 0
-        assert lib.srack_device_from_host(d_cv, cv.ctypes.data_as(C.c_void_p), cv.nbytes, None) == 0
-        assert lib.srack_device_sync(None) == 0
-        p = host(S, NB)
-        for k, (par, mo) in enumerate(settings):
-            p.set_bus_shaper(par, mo)
-            p.bus_shaper_raw(T, d_in, 2, d_cv, d_out.value + k * rows.nbytes, st)
-        got = np.empty((8,) + rows.shape, dtype=np.float32)
-        assert lib.srack_device_to_host(got.ctypes.data_as(C.c_void_p), d_out, got.nbytes, st) == 0
-        assert lib.srack_device_sync(st) == 0
+        with S.DeviceScope(st) as dev:
+            d_in, d_cv, d_out = dev.upload(rows), dev.upload(cv), dev.alloc(got.nbytes)
+            assert lib.srack_device_sync(None) == 0
+            p = host(S, NB)
+            for k, (par, mo) in enumerate(settings):
+                p.set_bus_shaper(par, mo)
+                p.bus_shaper_raw(T, d_in, 2, d_cv, d_out + k * rows.nbytes, st)
+            dev.download(got, d_out)
     finally:
-        for d in (d_in, d_cv, d_out):
-            if d.value:
-                lib.srack_device_free(d)
         assert hip.hipStreamDestroy(st) == 0
     for k in range(8):
         assert_same_bits(got[k], refs[k], f"call {k}")
@@ -385,31 +362,24 @@ def test_the_chain_on_one_stream(S):
     hip = C.CDLL("libamdhip64.so")
     hip.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
     hip.hipStreamDestroy.argtypes = [C.c_void_p]
-    lib, st = S.lib, C.c_void_p()
+    st = C.c_void_p()
     assert hip.hipStreamCreateWithFlags(C.byref(st), 1) == 0
     p = host(S, n_buses)
     p.set_bus_filter(fpar, port, enabled)
     p.set_bus_shaper(params, mode)
     p.set_bus_vca(None, vmode, negative)
     p.set_master(gain)
-    d = [C.c_void_p() for _ in range(4)]   # rows (processed in place), ctl, cv, master
+    got, mid = np.empty_like(want), np.empty_like(rows)
     try:
-        for x, size in zip(d, (rows.nbytes, ctl.nbytes, cv.nbytes, want.nbytes)):
-            assert lib.srack_device_alloc(C.byref(x), size) == 0
-        for x, a in zip(d, (rows, ctl, cv)):
-            assert lib.srack_device_from_host(x, a.ctypes.data_as(C.c_void_p), a.nbytes, st) == 0
-        p.bus_filter_raw(n, d[0], 2, d[1], d[0], st)
-        p.bus_shaper_raw(n, d[0], 2, d[2], d[0], st)
-        p.bus_vca_raw(n, d[0], 2, d[1], d[0], None, st)
-        p.master_raw(n, d[0], 2, d[3], None, st)
-        got, mid = np.empty_like(want), np.empty_like(rows)
-        assert lib.srack_device_to_host(got.ctypes.data_as(C.c_void_p), d[3], got.nbytes, st) == 0
-        assert lib.srack_device_to_host(mid.ctypes.data_as(C.c_void_p), d[0], mid.nbytes, st) == 0
-        assert lib.srack_device_sync(st) == 0
+        with S.DeviceScope(st) as dev:
+            d = [dev.upload(a, stream=st) for a in (rows, ctl, cv)] + [dev.alloc(want.nbytes)]   # rows (processed in place), ctl, cv, master
+            p.bus_filter_raw(n, d[0], 2, d[1], d[0], st)
+            p.bus_shaper_raw(n, d[0], 2, d[2], d[0], st)
+            p.bus_vca_raw(n, d[0], 2, d[1], d[0], None, st)
+            p.master_raw(n, d[0], 2, d[3], None, st)
+            dev.download(got, d[3])
+            dev.download(mid, d[0])
     finally:
-        for x in d:
-            if x.value:
-                lib.srack_device_free(x)
         assert hip.hipStreamDestroy(st) == 0
     assert_same_bits(mid, amped, "filter, shaper, VCA")
     assert_same_bits(got, want, "filter, shaper, VCA, master")

@@ -134,7 +134,6 @@ def assert_worth_comparing(rows, ctl, params, mode, negative, rate, ref_out, wha
 def run_raw(S, p, rows, ctl=None, in_place=False, want_env=False, off_rows=0, off_ctl=0, off_out=0, off_env=0):
     """srack_buses_vca with its four pointers `off_*` floats into their allocations.  Out of place d_out holds SENTINEL beforehand, and so
     does d_env; one GUARD float lies behind each.  -> (out of rows' shape, env [n_buses][n] or None, the guards as they came back)"""
-    lib = S.lib
     x = np.ascontiguousarray(rows, dtype=np.float32)
     buf = np.full(x.size + 1, SENTINEL, dtype=np.float32)
     if in_place:
@@ -142,37 +141,20 @@ def run_raw(S, p, rows, ctl=None, in_place=False, want_env=False, off_rows=0, of
     buf[-1] = GUARD
     ebuf = np.full(x.shape[0] * x.shape[2] + 1, SENTINEL, dtype=np.float32)
     ebuf[-1] = GUARD
-    d_in, d_out, d_ctl, d_env = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-    try:
-        assert lib.srack_device_alloc(C.byref(d_out), buf.nbytes + 4 * off_out) == 0
-        a_out = d_out.value + 4 * off_out
-        assert lib.srack_device_from_host(a_out, buf.ctypes.data_as(C.c_void_p), buf.nbytes, None) == 0
-        a_in = a_out
-        if not in_place:
-            assert lib.srack_device_alloc(C.byref(d_in), x.nbytes + 4 * off_rows) == 0
-            a_in = d_in.value + 4 * off_rows
-            assert lib.srack_device_from_host(a_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None) == 0
-        a_ctl = a_env = None
-        if ctl is not None:
-            c = np.ascontiguousarray(ctl, dtype=np.float32)
-            assert c.shape == (x.shape[0], x.shape[2])
-            assert lib.srack_device_alloc(C.byref(d_ctl), c.nbytes + 4 * off_ctl) == 0
-            a_ctl = d_ctl.value + 4 * off_ctl
-            assert lib.srack_device_from_host(a_ctl, c.ctypes.data_as(C.c_void_p), c.nbytes, None) == 0
-        if want_env:
-            assert lib.srack_device_alloc(C.byref(d_env), ebuf.nbytes + 4 * off_env) == 0
-            a_env = d_env.value + 4 * off_env
-            assert lib.srack_device_from_host(a_env, ebuf.ctypes.data_as(C.c_void_p), ebuf.nbytes, None) == 0
+    c = None
+    if ctl is not None:
+        c = np.ascontiguousarray(ctl, dtype=np.float32)
+        assert c.shape == (x.shape[0], x.shape[2])
+    with S.DeviceScope() as dev:
+        a_out = dev.upload(buf, off_out)
+        a_in = a_out if in_place else dev.upload(x, off_rows)
+        a_ctl = None if c is None else dev.upload(c, off_ctl)
+        a_env = dev.upload(ebuf, off_env) if want_env else None
         p.bus_vca_raw(x.shape[2], a_in, x.shape[1], a_ctl, a_out, a_env, None)
-        assert lib.srack_device_to_host(buf.ctypes.data_as(C.c_void_p), a_out, buf.nbytes, None) == 0
+        dev.download(buf, a_out)
         if want_env:
-            assert lib.srack_device_to_host(ebuf.ctypes.data_as(C.c_void_p), a_env, ebuf.nbytes, None) == 0
-        assert lib.srack_device_sync(None) == 0
-        return buf[:-1].reshape(x.shape), (ebuf[:-1].reshape(x.shape[0], x.shape[2]) if want_env else None), (buf[-1], ebuf[-1])
-    finally:
-        for d in (d_in, d_out, d_ctl, d_env):
-            if d.value:
-                lib.srack_device_free(d)
+            dev.download(ebuf, a_env)
+    return buf[:-1].reshape(x.shape), (ebuf[:-1].reshape(x.shape[0], x.shape[2]) if want_env else None), (buf[-1], ebuf[-1])
 
 
 # ---- 1. shapes: partial and full groups of buses, partial and full tiles, row_channels 1, 2, 3 ------------------------------------------
@@ -471,11 +453,10 @@ def test_overlaps_are_refused(S):
     n_buses, n = 3, 16
     p = host(S, n_buses)
     p.set_bus_vca()
-    d = C.c_void_p()
     nbytes, rowbytes = n_buses * 2 * n * 4, n_buses * n * 4
-    assert S.lib.srack_device_alloc(C.byref(d), 8 * nbytes) == 0
-    try:
-        base, far, farther = d.value + nbytes, d.value + 4 * nbytes, d.value + 6 * nbytes
+    with S.DeviceScope() as dev:
+        d = dev.alloc(8 * nbytes)
+        base, far, farther = d + nbytes, d + 4 * nbytes, d + 6 * nbytes
         run = S.lib.srack_buses_vca
         for d_out in (base + 4, base - 4, base + nbytes - 4, base - nbytes + 4):
             assert run(p.h, n, base, 2, None, d_out, None, None) == S.ERR_INVALID, d_out - base
@@ -489,12 +470,9 @@ def test_overlaps_are_refused(S):
             assert run(p.h, n, base, 2, farther, far, d_env, None) == S.ERR_INVALID                   # d_env on d_ctl
         assert "busvca" not in p.info() and p.bus_vca_state().tolist() == [[0.0, 4.0, 0.0, 0.0, 48000.0, 1.0]] * n_buses   # nothing ran
         # neighbours are fine: d_out right behind d_rows, d_ctl right behind d_out, d_env right behind d_ctl; d_ctl may lie on d_rows
-        assert S.lib.srack_device_from_host(d.value, np.zeros(2 * nbytes, dtype=np.float32).ctypes.data_as(C.c_void_p), 8 * nbytes, None) == 0
-        assert run(p.h, n, d.value, 2, d.value + 2 * nbytes, d.value + nbytes, d.value + 2 * nbytes + rowbytes, None) == S.OK
-        assert run(p.h, n, d.value, 2, d.value, d.value + nbytes, None, None) == S.OK
-        assert S.lib.srack_device_sync(None) == 0
-    finally:
-        S.lib.srack_device_free(d)
+        assert S.lib.srack_device_from_host(d, np.zeros(2 * nbytes, dtype=np.float32).ctypes.data_as(C.c_void_p), 8 * nbytes, None) == 0
+        assert run(p.h, n, d, 2, d + 2 * nbytes, d + nbytes, d + 2 * nbytes + rowbytes, None) == S.OK
+        assert run(p.h, n, d, 2, d, d + nbytes, None, None) == S.OK
 
 
 @pytest.mark.parametrize("off_rows,off_ctl,off_out,off_env", [(1, 2, 3, 1), (2, 3, 1, 3), (3, 1, 2, 2), (1, 0, 0, 0), (0, 0, 0, 1)])
@@ -543,20 +521,10 @@ def test_the_envelope_drives_the_bus_filter(S):
     p = host(S, n_buses)
     p.set_bus_vca(params, mode, negative)
     p.set_bus_filter(fpar, port, enabled)
-    nbytes, rowbytes = rows.nbytes, ctl.nbytes
-    d = [C.c_void_p() for _ in range(4)]   # rows (processed in place), ctl, env, filtered
-    try:
-        for x, size in zip(d, (nbytes, rowbytes, rowbytes, nbytes)):
-            assert S.lib.srack_device_alloc(C.byref(x), size) == 0
-        assert S.lib.srack_device_from_host(d[0], rows.ctypes.data_as(C.c_void_p), nbytes, None) == 0
-        assert S.lib.srack_device_from_host(d[1], ctl.ctypes.data_as(C.c_void_p), rowbytes, None) == 0
+    got = np.empty_like(want)
+    with S.DeviceScope() as dev:
+        d = [dev.upload(rows), dev.upload(ctl), dev.alloc(ctl.nbytes), dev.alloc(rows.nbytes)]   # rows (processed in place), ctl, env, filtered
         p.bus_vca_raw(n, d[0], 2, d[1], d[0], d[2])
         p.bus_filter_raw(n, d[0], 2, d[2], d[3])
-        got = np.empty_like(want)
-        assert S.lib.srack_device_to_host(got.ctypes.data_as(C.c_void_p), d[3], nbytes, None) == 0
-        assert S.lib.srack_device_sync(None) == 0
-    finally:
-        for x in d:
-            if x.value:
-                S.lib.srack_device_free(x)
+        dev.download(got, d[3])
     assert_same_bits(got, want, "VCA, then the filter swept by the VCA's envelope")

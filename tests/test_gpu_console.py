@@ -64,16 +64,10 @@ def reference(n_buses=70, channels=2, T=3000, seed=CR.SEED, n_aux=4, rate=48000,
 
 
 class Device:
-    """buffers of the library's own allocator, copied synchronously on the null stream"""
+    """buffers of a staging scope (S.DeviceScope, which frees them), copied synchronously on the null stream"""
 
-    def __init__(self, S):
-        self.lib, self.held = S.lib, []
-
-    def alloc(self, nbytes):
-        d = C.c_void_p()
-        assert self.lib.srack_device_alloc(C.byref(d), max(4, nbytes)) == 0
-        self.held.append(d)
-        return d
+    def __init__(self, S, scope):
+        self.lib, self.alloc = S.lib, scope.alloc
 
     def up(self, d, a):
         a = np.ascontiguousarray(a)
@@ -87,19 +81,14 @@ class Device:
         assert self.lib.srack_device_sync(None) == 0
         return a
 
-    def free(self):
-        for d in self.held:
-            self.lib.srack_device_free(d)
-        self.held = []
-
 
 def run_chain(S, p, rows, ctl, cuts, render=None):
     """The chain on the null stream in calls of `cuts` samples, every intermediate read back between the stages.  render(n, d_rows):
     where the rows come from when not from `rows` (test 4)."""
     nb, ch, T = rows.shape
-    dev = Device(S)
     parts, at = {k: [] for k in CR.KEYS}, 0
-    try:
+    with S.DeviceScope() as scope:
+        dev = Device(S, scope)
         d_stats = dev.alloc(8 * 2 * S.STAT_COUNT)
         dev.up(d_stats, np.zeros((2, S.STAT_COUNT)))
         for n in cuts:
@@ -125,8 +114,6 @@ def run_chain(S, p, rows, ctl, cuts, render=None):
         out = {k: np.concatenate(v, axis=-1) for k, v in parts.items()}
         out["stats"] = dev.down(d_stats, (2, S.STAT_COUNT), np.float64)
         return out
-    finally:
-        dev.free()
 
 
 # ---- 1, 2. the chain in one call and in the cuts ------------------------------------------------------------------------------------------------

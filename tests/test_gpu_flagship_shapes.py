@@ -10,7 +10,6 @@ What the shape could get wrong, and what holds it here against the CPU oracle:
     call's first full chunk (a 4096-sample latency chain);
   * exact mode bit for bit (the reference's arithmetic), default mode within the suite's tolerance, the mix against the frames.
 """
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -110,22 +109,16 @@ def test_full_grid_and_a_partial_wave(S, oracle, flags):
     p = gpu_patch(S, V)
     n_planes, _ = p.planes()
     assert n_planes == 1
-    d_fr, d_mx = C.c_void_p(), C.c_void_p()
-    assert S.lib.srack_device_alloc(C.byref(d_fr), T * V * 4) == 0
-    assert S.lib.srack_device_alloc(C.byref(d_mx), 2 * T * 4) == 0
-    try:
-        p.render_raw(T, d_fr.value, d_mx.value, flags, None)
+    mix = np.empty((2, T), np.float32)
+    with S.DeviceScope() as dev:
+        d_fr, d_mx = dev.alloc(T * V * 4), dev.alloc(mix.nbytes)
+        p.render_raw(T, d_fr, d_mx, flags, None)
         assert S.lib.srack_device_sync(None) == 0
         assert "kernel=render_voice_chain_track" in p.info(), p.info()
         pick = np.unique(np.array([0, 1, 63, 64, 255, 256, 4095 * 64 - 1, 4096 * 64 - 1, 4096 * 64, 4097 * 64 - 1, 4097 * 64, V - 2, V - 1]
                                   + list(np.random.default_rng(7).integers(0, V, 19))))
-        got, own, scale = read_plane(S, d_fr.value, T, V, pick)
-        mix = np.empty((2, T), np.float32)
-        assert S.lib.srack_device_to_host(mix.ctypes.data_as(C.c_void_p), d_mx, mix.nbytes, None) == 0
-        assert S.lib.srack_device_sync(None) == 0
-    finally:
-        S.lib.srack_device_free(d_fr)
-        S.lib.srack_device_free(d_mx)
+        got, own, scale = read_plane(S, d_fr, T, V, pick)
+        dev.download(mix, d_mx)
     o = oracle.OraclePatch(48000, 1024, 2)
     ids = S.build_p1(o, adsr="finite", lfo_val=-4.0)
     det, cut = S.p1_voice_params(V)

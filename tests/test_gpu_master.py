@@ -7,7 +7,6 @@ NumPy (f32 arrays vectorised over time, Python loops over buses, runs and blocks
 is built with -ffp-contract=off), and the statistics the same f64 operations in sample order.  No tolerance anywhere in this file.
 Every case asserts that what it compares is not silent, and from 66 buses on that the reference tree's bits differ from the plain
 sequential sum's: a kernel that adds in another order cannot pass."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -80,32 +79,18 @@ def run_offset(S, p, rows, offset, stats=None):
     lib = S.lib
     x = np.ascontiguousarray(rows, dtype=np.float32)
     T = x.shape[2]
-    out = np.empty((2, T), dtype=np.float32)
+    buf = np.zeros(2 * T + 1, dtype=np.float32)
+    buf[-1] = 12345.0  # one float behind the master: the call must not write it
     st = None if stats is None else np.array(stats, dtype=np.float64)
-    d_in, d_out, d_st = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    try:
-        assert lib.srack_device_alloc(C.byref(d_in), x.nbytes + 4 * offset) == 0
-        assert lib.srack_device_alloc(C.byref(d_out), out.nbytes + 4 * offset + 4) == 0
-        guard = np.array([12345.0], dtype=np.float32)  # one float behind the master: the call must not write it
-        a_in, a_out = d_in.value + 4 * offset, d_out.value + 4 * offset
-        assert lib.srack_device_from_host(a_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None) == 0
-        assert lib.srack_device_from_host(a_out + out.nbytes, guard.ctypes.data_as(C.c_void_p), 4, None) == 0
+    with S.DeviceScope() as dev:
+        a_in, a_out = dev.upload(x, offset), dev.upload(buf, offset)
+        d_st = None if st is None else dev.upload(st)
+        p.master_raw(T, a_in, x.shape[1], a_out, d_st, None)
+        dev.download(buf, a_out)
         if st is not None:
-            assert lib.srack_device_alloc(C.byref(d_st), st.nbytes) == 0
-            assert lib.srack_device_from_host(d_st, st.ctypes.data_as(C.c_void_p), st.nbytes, None) == 0
-        p.master_raw(T, a_in, x.shape[1], a_out, d_st if st is not None else None, None)
-        assert lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), a_out, out.nbytes, None) == 0
-        back = np.zeros(1, dtype=np.float32)
-        assert lib.srack_device_to_host(back.ctypes.data_as(C.c_void_p), a_out + out.nbytes, 4, None) == 0
-        if st is not None:
-            assert lib.srack_device_to_host(st.ctypes.data_as(C.c_void_p), d_st, st.nbytes, None) == 0
-        assert lib.srack_device_sync(None) == 0
-        assert back[0] == 12345.0, "the call wrote past d_master"
-        return out, st
-    finally:
-        for d in (d_in, d_out, d_st):
-            if d.value:
-                lib.srack_device_free(d)
+            dev.download(st, d_st)
+    assert buf[-1] == 12345.0, "the call wrote past d_master"
+    return buf[:-1].reshape(2, T), st
 
 
 START = np.array([[1.5, 2.25, 0.75, 0.125, 3.0, 2.0], [-0.5, 10.0, 0.0, 1.25, 0.0, 7.0]])  # a statistics buffer that is not zeros

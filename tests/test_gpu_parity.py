@@ -666,9 +666,9 @@ def test_two_million_voices_on_one_gpu(S, oracle):
     p.configure_voices(V)
     p.set_voice_field(ids["osc_a"], S.OSC_VAL, det)
     p.set_voice_field(ids["vcf"], S.VCF_FREQ, cut)
-    d_fr, d_mx = C.c_void_p(), C.c_void_p()
-    assert S.lib.srack_device_alloc(C.byref(d_fr), T * V * 4) == 0 and S.lib.srack_device_alloc(C.byref(d_mx), 2 * T * 4) == 0
-    try:
+    mix = np.empty((2, T), dtype=np.float32)
+    with S.DeviceScope() as dev:
+        d_fr, d_mx = dev.alloc(T * V * 4), dev.alloc(mix.nbytes)
         p.render_raw(T, d_fr, d_mx, 0, None)
         assert S.lib.srack_device_sync(None) == 0
         assert "kernel=render_voice_chain_track" in p.info()
@@ -677,13 +677,9 @@ def test_two_million_voices_on_one_gpu(S, oracle):
         row = np.empty(V, dtype=np.float32)
         got, own, scale = np.empty((len(ts), len(pick)), dtype=np.float32), np.empty(len(ts)), np.empty(len(ts))
         for k, t in enumerate(ts):
-            assert S.lib.srack_device_to_host(row.ctypes.data_as(C.c_void_p), C.c_void_p(d_fr.value + int(t) * V * 4), V * 4, None) == 0
+            assert S.lib.srack_device_to_host(row.ctypes.data_as(C.c_void_p), C.c_void_p(d_fr + int(t) * V * 4), V * 4, None) == 0
             got[k], own[k], scale[k] = row[pick], row.sum(dtype=np.float64), np.abs(row).sum(dtype=np.float64)
-        mix = np.empty((2, T), dtype=np.float32)
-        assert S.lib.srack_device_to_host(mix.ctypes.data_as(C.c_void_p), d_mx, mix.nbytes, None) == 0 and S.lib.srack_device_sync(None) == 0
-    finally:
-        S.lib.srack_device_free(d_fr)
-        S.lib.srack_device_free(d_mx)
+        dev.download(mix, d_mx)
     o = oracle.OraclePatch(48000, 1024, 2)
     S.build_p1(o, adsr="finite", lfo_val=-2.0)
     ref, _ = o.render_batch(len(pick), T, [(ids["osc_a"], S.OSC_VAL, det[pick]), (ids["vcf"], S.VCF_FREQ, cut[pick])], threads=8)
@@ -712,38 +708,32 @@ def test_cfg3_ticked_as_benchmarked(S):
         p.set_voice_field(ids["vcf"], S.VCF_FREQ, cut)
         return p
 
-    bufs = [C.c_void_p() for _ in range(4)]
-    for b, n in zip(bufs, (T * V * 4, T * V * 4, 2 * T * 4, 2 * T * 4)):
-        assert S.lib.srack_device_alloc(C.byref(b), n) == 0
-    fr_one, fr_tick, mx_one, mx_tick = bufs
-    try:
+    m1, m2 = np.empty((2, T), dtype=np.float32), np.empty(2 * T, dtype=np.float32)
+    with S.DeviceScope() as dev:
+        fr_one, fr_tick, mx_one, mx_tick = (dev.alloc(n) for n in (T * V * 4, T * V * 4, m1.nbytes, m2.nbytes))
         one = patch()
         one.render_raw(T, fr_one, mx_one, 0, None)
         tick = patch()
         for t in range(0, T, L):   # a call's mix is [2][n] of its own: at 2 t floats into the buffer
             n = min(L, T - t)
-            tick.render_raw(n, C.c_void_p(fr_tick.value + t * V * 4), C.c_void_p(mx_tick.value + 2 * t * 4), 0, None)
+            tick.render_raw(n, C.c_void_p(fr_tick + t * V * 4), C.c_void_p(mx_tick + 2 * t * 4), 0, None)
         assert S.lib.srack_device_sync(None) == 0
         assert "kernel=render_voice_chain_track" in tick.info()
         a, b = np.empty(V, dtype=np.float32), np.empty(V, dtype=np.float32)
         loud = 0.0
         for t in list(range(0, T, 89)) + [1023, 1024, 1025, T - 897, T - 896, T - 1]:
             for dst, src in ((a, fr_one), (b, fr_tick)):
-                assert S.lib.srack_device_to_host(dst.ctypes.data_as(C.c_void_p), C.c_void_p(src.value + t * V * 4), V * 4, None) == 0
+                assert S.lib.srack_device_to_host(dst.ctypes.data_as(C.c_void_p), C.c_void_p(src + t * V * 4), V * 4, None) == 0
             assert S.lib.srack_device_sync(None) == 0
             np.testing.assert_array_equal(bits(a), bits(b), err_msg=f"row {t}")
             loud = max(loud, float(np.abs(a).max()))
         assert loud > 0.05
-        m1, m2 = np.empty((2, T), dtype=np.float32), np.empty(2 * T, dtype=np.float32)
-        assert S.lib.srack_device_to_host(m1.ctypes.data_as(C.c_void_p), mx_one, m1.nbytes, None) == 0
-        assert S.lib.srack_device_to_host(m2.ctypes.data_as(C.c_void_p), mx_tick, m2.nbytes, None) == 0 and S.lib.srack_device_sync(None) == 0
-        for t in range(0, T, L):
-            n = min(L, T - t)
-            blk = m2[2 * t:2 * t + 2 * n].reshape(2, n)
-            np.testing.assert_array_equal(bits(blk), bits(m1[:, t:t + n]), err_msg=f"mix of the call at {t}")
-    finally:
-        for b in bufs:
-            S.lib.srack_device_free(b)
+        dev.download(m1, mx_one)
+        dev.download(m2, mx_tick)
+    for t in range(0, T, L):
+        n = min(L, T - t)
+        blk = m2[2 * t:2 * t + 2 * n].reshape(2, n)
+        np.testing.assert_array_equal(bits(blk), bits(m1[:, t:t + n]), err_msg=f"mix of the call at {t}")
 
 
 def test_cfg3_exactly_as_benchmarked(S, oracle):
@@ -758,19 +748,15 @@ def test_cfg3_exactly_as_benchmarked(S, oracle):
     p.configure_voices(V)
     p.set_voice_field(ids["osc_a"], S.OSC_VAL, det)
     p.set_voice_field(ids["vcf"], S.VCF_FREQ, cut)
-    d_fr, d_mx = C.c_void_p(), C.c_void_p()
-    assert S.lib.srack_device_alloc(C.byref(d_fr), T * V * 4) == 0 and S.lib.srack_device_alloc(C.byref(d_mx), 2 * T * 4) == 0
-    try:
+    mix = np.empty((2, T), dtype=np.float32)
+    with S.DeviceScope() as dev:
+        d_fr, d_mx = dev.alloc(T * V * 4), dev.alloc(mix.nbytes)
         p.render_raw(T, d_fr, d_mx, 0, None)
         assert S.lib.srack_device_sync(None) == 0
         assert "kernel=render_voice_chain_track" in p.info()
         pick = np.unique(np.concatenate([np.arange(0, V, 4099), [0, 63, 64, V - 65, V - 64, V - 1]]))
-        got, own, scale = read_plane(S, d_fr.value, T, V, pick)
-        mix = np.empty((2, T), dtype=np.float32)
-        assert S.lib.srack_device_to_host(mix.ctypes.data_as(C.c_void_p), d_mx, mix.nbytes, None) == 0 and S.lib.srack_device_sync(None) == 0
-    finally:
-        S.lib.srack_device_free(d_fr)
-        S.lib.srack_device_free(d_mx)
+        got, own, scale = read_plane(S, d_fr, T, V, pick)
+        dev.download(mix, d_mx)
     o = oracle.OraclePatch(48000, 1024, 2)
     S.build_p1(o)
     ref, _ = o.render_batch(len(pick), T, [(ids["osc_a"], S.OSC_VAL, det[pick]), (ids["vcf"], S.VCF_FREQ, cut[pick])], threads=8)
@@ -792,19 +778,15 @@ def test_cfg3_poly_exactly_as_benchmarked(S, oracle):
     p.configure_voices(V)
     for m, f, v in S.p1_poly_overrides(ids, pv):
         p.set_voice_field(m, f, v)
-    d_fr, d_mx = C.c_void_p(), C.c_void_p()
-    assert S.lib.srack_device_alloc(C.byref(d_fr), T * V * 4) == 0 and S.lib.srack_device_alloc(C.byref(d_mx), 2 * T * 4) == 0
-    try:
+    mix = np.empty((2, T), dtype=np.float32)
+    with S.DeviceScope() as dev:
+        d_fr, d_mx = dev.alloc(T * V * 4), dev.alloc(mix.nbytes)
         p.render_raw(T, d_fr, d_mx, 0, None)
         assert S.lib.srack_device_sync(None) == 0
         assert "kernel=render_specialized" in p.info() and "ctl[" not in p.info(), p.info()   # nothing hoisted: no control program
         pick = np.unique(np.concatenate([np.arange(0, V, 2731), [0, 63, 64, V - 65, V - 64, V - 1]]))
-        got, own, scale = read_plane(S, d_fr.value, T, V, pick)
-        mix = np.empty((2, T), dtype=np.float32)
-        assert S.lib.srack_device_to_host(mix.ctypes.data_as(C.c_void_p), d_mx, mix.nbytes, None) == 0 and S.lib.srack_device_sync(None) == 0
-    finally:
-        S.lib.srack_device_free(d_fr)
-        S.lib.srack_device_free(d_mx)
+        got, own, scale = read_plane(S, d_fr, T, V, pick)
+        dev.download(mix, d_mx)
     o = oracle.OraclePatch(48000, 1024, 2)
     S.build_p1(o)
     ref, _ = o.render_batch(len(pick), T, [(m, f, v[pick]) for m, f, v in S.p1_poly_overrides(ids, pv)], threads=8)
@@ -873,19 +855,15 @@ def test_cfg4_exactly_as_benchmarked(S, oracle, B, flags, kernel):
     p.configure_voices(V)
     p.set_voice_field(ids["mul_fb"], S.MATH_CONSTANT, beta)
     p.set_voice_field(ids["mul_idx"], S.MATH_CONSTANT, index)
-    d_fr, d_mx = C.c_void_p(), C.c_void_p()
-    assert S.lib.srack_device_alloc(C.byref(d_fr), T * V * 4) == 0 and S.lib.srack_device_alloc(C.byref(d_mx), 2 * T * 4) == 0
-    try:
+    mix = np.empty((2, T), dtype=np.float32)
+    with S.DeviceScope() as dev:
+        d_fr, d_mx = dev.alloc(T * V * 4), dev.alloc(mix.nbytes)
         p.render_raw(T, d_fr, d_mx, flags, None)
         assert S.lib.srack_device_sync(None) == 0
         assert "kernel=" + kernel in p.info() and ("approx[kept default" if flags else "; exact osc 0]") in p.info(), p.info()
         pick = np.unique(np.concatenate([np.arange(0, V, 2113), [0, 63, 64, V - 65, V - 64, V - 1]]))
-        got, own, scale = read_plane(S, d_fr.value, T, V, pick)
-        mix = np.empty((2, T), dtype=np.float32)
-        assert S.lib.srack_device_to_host(mix.ctypes.data_as(C.c_void_p), d_mx, mix.nbytes, None) == 0 and S.lib.srack_device_sync(None) == 0
-    finally:
-        S.lib.srack_device_free(d_fr)
-        S.lib.srack_device_free(d_mx)
+        got, own, scale = read_plane(S, d_fr, T, V, pick)
+        dev.download(mix, d_mx)
     o = oracle.OraclePatch(48000, B, 2)
     S.build_p2(o)
     ref, _ = o.render_batch(len(pick), T, [(ids["mul_fb"], S.MATH_CONSTANT, beta[pick]), (ids["mul_idx"], S.MATH_CONSTANT, index[pick])], threads=8)
@@ -1037,27 +1015,23 @@ def test_p3_exactly_as_benchmarked(S, oracle):
     p.set_voice_field(ids["transpose"], S.MATH_CONSTANT, transpose)
     p.set_voice_field(ids["vcf"], S.VCF_FREQ, cut)
     assert p.planes() == (2, [0, 1])
-    d_fr, d_mx = C.c_void_p(), C.c_void_p()
-    assert S.lib.srack_device_alloc(C.byref(d_fr), 2 * T * V * 4) == 0 and S.lib.srack_device_alloc(C.byref(d_mx), 2 * T * 4) == 0
-    try:
+    mix = np.empty((2, T), dtype=np.float32)
+    with S.DeviceScope() as dev:
+        d_fr, d_mx = dev.alloc(2 * T * V * 4), dev.alloc(mix.nbytes)
         p.render_raw(T, d_fr, d_mx, 0, None)
         assert S.lib.srack_device_sync(None) == 0
         assert "kernel=render_specialized" in p.info() and p.info().count("ctl[") == 5
         pick = np.unique(np.concatenate([np.arange(0, V, 8209), [0, 63, 64, V - 65, V - 64, V - 1]]))
         got = np.empty((2, T, len(pick)), dtype=np.float32)
         # plane 0 in full (50 GB over PCIe), plane 1 (every voice the same gate) at the sampled voices
-        got[0], own, scale = read_plane(S, d_fr.value, T, V, pick)
+        got[0], own, scale = read_plane(S, d_fr, T, V, pick)
         row = np.empty(V, dtype=np.float32)
         for t in range(0, T, 997):   # plane 1: whole rows at a stride (every voice must carry the same gate)
-            assert S.lib.srack_device_to_host(row.ctypes.data_as(C.c_void_p), C.c_void_p(d_fr.value + ((T + t) * V) * 4), V * 4, None) == 0
+            assert S.lib.srack_device_to_host(row.ctypes.data_as(C.c_void_p), C.c_void_p(d_fr + ((T + t) * V) * 4), V * 4, None) == 0
             assert S.lib.srack_device_sync(None) == 0
             assert (row == row[0]).all(), t
             got[1, t] = row[pick]
-        mix = np.empty((2, T), dtype=np.float32)
-        assert S.lib.srack_device_to_host(mix.ctypes.data_as(C.c_void_p), d_mx, mix.nbytes, None) == 0 and S.lib.srack_device_sync(None) == 0
-    finally:
-        S.lib.srack_device_free(d_fr)
-        S.lib.srack_device_free(d_mx)
+        dev.download(mix, d_mx)
     o = oracle.OraclePatch(48000, 1024, 2)
     S.build_p3(o)
     ref, _ = o.render_batch(len(pick), T, [(ids["transpose"], S.MATH_CONSTANT, transpose[pick]), (ids["vcf"], S.VCF_FREQ, cut[pick])], threads=8)
@@ -1209,9 +1183,9 @@ def test_p4_exactly_as_benchmarked(S, oracle):
     p.set_voice_field(ids["depth"], S.MATH_CONSTANT, depth)
     p.set_voice_field(ids["shaper"], S.NONLIN_CONSTANT, expo)
     assert p.planes() == (2, [0, 1])
-    d_fr, d_mx = C.c_void_p(), C.c_void_p()
-    assert S.lib.srack_device_alloc(C.byref(d_fr), 2 * T * V * 4) == 0 and S.lib.srack_device_alloc(C.byref(d_mx), 2 * T * 4) == 0
-    try:
+    mix = np.empty((2, T), dtype=np.float32)
+    with S.DeviceScope() as dev:
+        d_fr, d_mx = dev.alloc(2 * T * V * 4), dev.alloc(mix.nbytes)
         p.render_raw(T, d_fr, d_mx, 0, None)
         assert S.lib.srack_device_sync(None) == 0
         assert "kernel=render_specialized" in p.info()
@@ -1221,12 +1195,8 @@ def test_p4_exactly_as_benchmarked(S, oracle):
         got = np.empty((2, T, len(pick)), dtype=np.float32)
         own, scale = np.empty((2, T)), np.empty((2, T))
         for plane in range(2):
-            got[plane], own[plane], scale[plane] = read_plane(S, d_fr.value + plane * T * V * 4, T, V, pick)
-        mix = np.empty((2, T), dtype=np.float32)
-        assert S.lib.srack_device_to_host(mix.ctypes.data_as(C.c_void_p), d_mx, mix.nbytes, None) == 0 and S.lib.srack_device_sync(None) == 0
-    finally:
-        S.lib.srack_device_free(d_fr)
-        S.lib.srack_device_free(d_mx)
+            got[plane], own[plane], scale[plane] = read_plane(S, d_fr + plane * T * V * 4, T, V, pick)
+        dev.download(mix, d_mx)
     o = oracle.OraclePatch(48000, 1024, 2)
     S.build_p4(o)
     ref, _ = o.render_batch(len(pick), T, [(ids["depth"], S.MATH_CONSTANT, depth[pick]), (ids["shaper"], S.NONLIN_CONSTANT, expo[pick])], threads=8)
@@ -1438,13 +1408,12 @@ def test_dist_reduce_mix_through_rccl(S):
         q = S.Patch(48000, 64, 2)
         S.build_p1(q, adsr="finite", lfo_val=2.0)
         q.configure_voices(100)
-        d_mix = C.c_void_p()
-        assert S.lib.srack_device_alloc(C.byref(d_mix), 2 * T * 4) == 0
-        q.render_raw(T, None, d_mix, 0, None)
-        assert S.lib.srack_dist_reduce_mix(comm, d_mix, 2 * T, 0, None) == 0, S.lib.srack_last_error()
         got = np.empty((2, T), dtype=np.float32)
-        assert S.lib.srack_device_to_host(got.ctypes.data_as(C.c_void_p), d_mix, got.nbytes, None) == 0 and S.lib.srack_device_sync(None) == 0
-        S.lib.srack_device_free(d_mix)
+        with S.DeviceScope() as dev:
+            d_mix = dev.alloc(got.nbytes)
+            q.render_raw(T, None, d_mix, 0, None)
+            assert S.lib.srack_dist_reduce_mix(comm, d_mix, 2 * T, 0, None) == 0, S.lib.srack_last_error()
+            dev.download(got, d_mix)
         np.testing.assert_array_equal(got, want)
         assert S.lib.srack_dist_reduce_mix(None, d_mix, 1, 0, None) == S.ERR_INVALID
     finally:
@@ -2225,9 +2194,8 @@ def test_read_backs_from_several_host_threads_at_once(S):
     p.configure_voices(V)
     p.set_voice_field(ids["osc_a"], S.OSC_VAL, det)
     p.set_voice_field(ids["vcf"], S.VCF_FREQ, cut)
-    d_fr = C.c_void_p()
-    assert S.lib.srack_device_alloc(C.byref(d_fr), T * V * 4) == 0
-    try:
+    with S.DeviceScope() as dev:
+        d_fr = dev.alloc(T * V * 4)
         p.render_raw(T, d_fr, None, 0, None)
         assert S.lib.srack_device_sync(None) == 0
         whole = np.empty(T * V, dtype=np.float32)
@@ -2239,7 +2207,7 @@ def test_read_backs_from_several_host_threads_at_once(S):
         def read(w):
             off, n = w
             out = np.empty(n // 4, dtype=np.float32)
-            rc = S.lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), C.c_void_p(d_fr.value + off), n, None)
+            rc = S.lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), C.c_void_p(d_fr + off), n, None)
             return rc, out
 
         for _ in range(2):
@@ -2248,5 +2216,3 @@ def test_read_backs_from_several_host_threads_at_once(S):
             for (off, n), (rc, out) in zip(windows, got):
                 assert rc == 0
                 np.testing.assert_array_equal(out, whole[off // 4:(off + n) // 4])
-    finally:
-        S.lib.srack_device_free(d_fr)

@@ -7,7 +7,6 @@ NaN) — derived, not measured: both sides perform the same single-rounded IEEE 
 library is built with -ffp-contract=off).  No tolerance anywhere in this file.  Every case asserts that what it compares is not
 silent, and from 66 terms on that the reference tree's bits differ from the plain sequential sum's: a kernel that adds in another
 order cannot pass."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -70,22 +69,12 @@ def run_raw(S, p, rows, offset_in=0, offset_out=None):
     x = np.ascontiguousarray(rows, dtype=np.float32)
     out = np.full(x.size + 1, SENTINEL, dtype=np.float32)
     out[-1] = GUARD
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    try:
-        assert lib.srack_device_alloc(C.byref(d_in), x.nbytes + 4 * offset_in) == 0
-        assert lib.srack_device_alloc(C.byref(d_out), out.nbytes + 4 * offset_out) == 0
-        a_in, a_out = d_in.value + 4 * offset_in, d_out.value + 4 * offset_out
-        assert lib.srack_device_from_host(a_in, x.ctypes.data_as(C.c_void_p), x.nbytes, None) == 0
-        assert lib.srack_device_from_host(a_out, out.ctypes.data_as(C.c_void_p), out.nbytes, None) == 0
+    with S.DeviceScope() as dev:
+        a_in, a_out = dev.upload(x, offset_in), dev.upload(out, offset_out)
         p.send_raw(x.shape[2], a_in, x.shape[1], a_out, None)
-        assert lib.srack_device_to_host(out.ctypes.data_as(C.c_void_p), a_out, out.nbytes, None) == 0
-        assert lib.srack_device_sync(None) == 0
-        assert out[-1] == GUARD, "the call wrote past d_out"
-        return out[:-1].reshape(x.shape)
-    finally:
-        for d in (d_in, d_out):
-            if d.value:
-                lib.srack_device_free(d)
+        dev.download(out, a_out)
+    assert out[-1] == GUARD, "the call wrote past d_out"
+    return out[:-1].reshape(x.shape)
 
 
 def run_cut(p, rows, cuts):

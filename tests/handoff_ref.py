@@ -148,7 +148,7 @@ def kernel_name(patch, B, n_voices, flags, n_samples, edited=False):
         return "render_specialized" if special and not exact else "render_fm_pair"
     if B < 32:
         return "render_specialized" if special else "render_interp"
-    return "render_fm_pair_block" if blk and B >= 64 else "render_fm_pair_ring"
+    return "render_fm_pair_block" if blk and B >= 256 else "render_fm_pair_ring"   # (launch_types.hpp, kBlkChunk: the time-parallel pair's chunk is 256 samples)
 
 
 # ---- cases -----------------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@ import numpy as np
 from oracle import srack_numpy as N
 
 _OSC = {0: "val", 1: "antialiasing", 2: "pos"}
-_VCF = {0: "freq", 1: "res", 2: "exp_amt"}
+_VCF = {0: "freq", 1: "res", 2: "exp_amt", 3: "f", 4: "p", 5: "q", 11: "sfreq", 12: "sres"}   # (6 ... 10: the ladder's b[0 ... 4])
 _ADSR = {0: "a_sec", 1: "d_sec", 2: "s_val", 3: "r_sec", 4: "phase", 5: "mode", 6: "r_val", 7: "from_a_val", 8: "sample_rate"}
 
 
@@ -36,7 +36,10 @@ class NumpyGraph:
             else:
                 m.val = np.float32(value)
         elif isinstance(m, N.MoogFilter):
-            setattr(m, _VCF[field], np.float32(value))
+            if 6 <= field <= 10:   # SRACK_VCF_ST_B0 ... _B4
+                m.b[field - 6] = np.float32(value)
+            else:
+                setattr(m, _VCF[field], np.float32(value))
         elif isinstance(m, N.ADSR):
             if field == 5:
                 m.mode = int(value)
@@ -109,6 +112,13 @@ class NumpyGraph:
 
     def set_wave(self, module, samples, sample_rate):
         self.modules[module].load(samples, sample_rate)
+
+    def set_output_buffer(self, module, port, samples):
+        """the block a port holds before the first tick (a loaded rack file's): what the sink of a broken feedback edge reads first"""
+        out = self.modules[module].outs[port]
+        a = np.asarray(samples, dtype=np.float32)
+        assert a.shape == out.shape
+        out[:] = a
 
     def plan(self):
         output = next(m for m in self.modules if isinstance(m, N.Output))

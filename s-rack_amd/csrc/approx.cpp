@@ -164,6 +164,7 @@ struct Analysis {
         Range r;
         if (!hit || hit->values.empty()) {
             r.lo = r.hi = (double)(float)g.modules[(size_t)module].fields[(size_t)f];
+            if (!(std::fabs(r.lo) < kInf)) r.lo = -kInf, r.hi = kInf;  // (an infinity or a NaN at patch level: like one in an override)
             return r;
         }
         r.lo = kInf, r.hi = -kInf;
@@ -198,6 +199,36 @@ struct Analysis {
         const double cv = connected(k, SRACK_OSC_IN_CV) ? in_mag(k, SRACK_OSC_IN_CV) : 0.0;
         if (!(cv < 64.0)) return kInf;
         return 440.0 * std::exp2(field(k, SRACK_OSC_VAL).hi + cv) / sr;
+    }
+    double osc_delta_min(int k) const  // ... and its infimum, over every voice (0: none above zero can be claimed)
+    {
+        const double cv = connected(k, SRACK_OSC_IN_CV) ? in_mag(k, SRACK_OSC_IN_CV) : 0.0;
+        if (!(cv < 64.0)) return 0.0;
+        return 440.0 * std::exp2(field(k, SRACK_OSC_VAL).lo - cv) / sr;
+    }
+    // The f32 forms take dt and 1 / dt as f32 (modules.hip.h, inv_dt_f32; the fixed-point phase's increment is dt x 2^64): an increment that is
+    // no normal f32 rounds to a subnormal or to 0 and its inverse to infinity — at OSC_VAL = -150 the carried-phase saw is a NaN on every sample
+    // where the reference, whose increment is an f64, renders a finite ramp.  Such an oscillator keeps the f64 PolyBLEP and the f64 phase.
+    bool osc_dt_is_normal_f32(int k) const { return osc_delta_min(k) >= (double)std::numeric_limits<float>::min(); }
+
+    // Does an envelope's time make its ramp run backwards?  adsr.rs:150-190 as restated in oracle/srack_oracle.c: the phase moves by the f32
+    // 1 / (sample_rate * sec) per sample and a stage ends at phase >= 1.  A time of 0 is an increment of +inf (the stage ends at once), a huge
+    // one an increment of +-0 (the stage stands still: bounded); a NEGATIVE time — -0.0 included: 1 / -0 = -inf — or a NaN never reaches 1, and
+    // the stage's line, r_val + (1 - r_val) phase and its like, is followed for as long as the gate leaves it alone: no bound.
+    bool adsr_time_runs_backwards(int k, int f) const
+    {
+        auto backwards = [&](double sec) {
+            const float inc = 1.0f / ((float)g.modules[(size_t)k].fields[SRACK_ADSR_SAMPLE_RATE] * (float)sec);
+            return !(inc >= 0.0f);
+        };
+        const VoiceOverride* hit = nullptr;
+        for (const auto& o : ov)
+            if (o.module == k && (o.field == f || o.field == SRACK_ADSR_SAMPLE_RATE)) hit = &o;
+        if (!hit || hit->values.empty()) return backwards(g.modules[(size_t)k].fields[(size_t)f]);
+        if (hit->field == SRACK_ADSR_SAMPLE_RATE) return true;  // (a sample rate per voice: nothing is claimed)
+        for (double v : hit->values)
+            if (backwards(v)) return true;
+        return false;
     }
 
     Range nonlin_exponent(int k) const
@@ -310,13 +341,18 @@ struct Analysis {
             mv = {a, a, a};
             break;
         }
-        case SRACK_MOD_ADSR:
-            o = {std::max(1.0, field(m, SRACK_ADSR_S_VAL).abs_max())};
+        case SRACK_MOD_ADSR: {
+            // every stage with a time >= 0 is a line between two of 0, 1, the sustain level and the value the envelope had when the stage began:
+            // sup = max(1, |S_VAL|).  A stage whose time runs backwards (above) is a ramp that never ends: unbounded — measured on the oracle,
+            // a 55 Hz square on the gate: A_SEC = -0.01 at -836 after 6 000 samples and falling.
+            const bool unbounded = adsr_time_runs_backwards(m, SRACK_ADSR_A_SEC) || adsr_time_runs_backwards(m, SRACK_ADSR_D_SEC) || adsr_time_runs_backwards(m, SRACK_ADSR_R_SEC);
+            o = {unbounded ? kInf : std::max(1.0, field(m, SRACK_ADSR_S_VAL).abs_max())};
             // an envelope moves now and then — as often as its gate opens: gated by something that moves at audio rate (an oscillator above LFO
             // rate, noise) it restarts every few samples (tools/cpu_soak.py, noise family, seed 277445: white noise on an envelope's gate, the
             // envelope on a cutoff: the contracted lowpass at 1.0e-5 where the bound said 3e-6)
             mv = {(in_motion(m, 0) & (kJumpAudio | kJumpNoise)) ? (uint32_t)kJumpAudio : (uint32_t)kJumpRare};
             break;
+        }
         case SRACK_MOD_VCA:
             o = {connected(m, 0) && connected(m, 1) ? in_mag(m, 0) * in_mag(m, 1) : 0.0};
             mv = {any_motion()};
@@ -365,12 +401,14 @@ struct Analysis {
         }
         case SRACK_MOD_GRID_SEQUENCER: {
             double note = std::fabs(mod.fields[SRACK_GRIDSEQ_LAST]);
-            const double spo = std::max(1.0, field(m, SRACK_GRIDSEQ_STEPS_PER_OCTAVE).lo);
+            // sequencer.rs:237: val * (1.0 / steps_per_octave), a u16 — at 0 an infinity, or a NaN for note 0: no bound where a cell is on
+            const double spo = field(m, SRACK_GRIDSEQ_STEPS_PER_OCTAVE).lo;
+            const double inv = spo >= 1.0 ? 1.0 / spo : kInf;
             for (uint32_t c : mod.cells)
-                if (c >> 31) note = std::max(note, (double)(c & 0xffffu) / spo);
+                if (c >> 31) note = std::max(note, inv == kInf ? kInf : (double)(c & 0xffffu) * inv);
             if (!mod.voice_seq.empty() && mod.seq_bank)  // voices play sequences of the bank: the highest note of any of them
                 for (uint32_t c : *mod.seq_bank)
-                    if (c >> 31) note = std::max(note, (double)(c & 0xffffu) / spo);
+                    if (c >> 31) note = std::max(note, inv == kInf ? kInf : (double)(c & 0xffffu) * inv);
             const double gate = std::max(1.0, connected(m, SRACK_SEQ_IN_STEP) ? in_mag(m, SRACK_SEQ_IN_STEP) : 0.0);
             o = {note, gate, 1.0};
             const uint32_t clocked = clock_motion(m);  // (a sequencer steps as often as its clock ticks)
@@ -808,14 +846,16 @@ ApproxPlan plan_approximations(const Graph& g, const std::vector<char>& live, co
         if (mod.type == SRACK_MOD_OSCILLATOR) {
             const bool aa = mod.fields[SRACK_OSC_ANTIALIASING] != 0.0;
             const bool saw = A.port_is_live(m, SRACK_OSC_OUT_SAW), square = A.port_is_live(m, SRACK_OSC_OUT_SQUARE), sine = A.port_is_live(m, SRACK_OSC_OUT_SINE);
-            if (aa && (saw || square))
+            const bool f32_dt = A.osc_dt_is_normal_f32(m);  // (else: neither the f32 PolyBLEP nor the fixed-point phase is on offer)
+            P.exact_blep[(size_t)m] = aa && (saw || square) && !f32_dt;
+            if (aa && (saw || square) && f32_dt)
                 add(kBlep, m, [&](int c) {
                     double v = saw ? times(kEpsBlep, gw(c, m, SRACK_OSC_OUT_SAW)) : 0.0;
                     if (square) v += times(kEpsBlep, A.pure_square_gain(G[(size_t)c], m, SRACK_OSC_OUT_SQUARE, c, 0));
                     return v;
                 });
             if (sine) add(kSine, m, [&](int c) { return times(kEpsSine, gw(c, m, SRACK_OSC_OUT_SINE)); });
-            if (saw && !square && !sine && mod.in[SRACK_OSC_IN_CV].src < 0) {
+            if (saw && !square && !sine && mod.in[SRACK_OSC_IN_CV].src < 0 && f32_dt) {
                 const double dt_min = 440.0 * std::exp2(A.field(m, SRACK_OSC_VAL).lo) / A.sr;  // (no CV: the pitch is val alone, per voice)
                 const double eps = dt_min > 0.0 ? kEpsFixed + kEpsFixedWindow / dt_min : kInf;
                 add(kFixed, m, [&](int c) { return times(eps, gw(c, m, SRACK_OSC_OUT_SAW)); });

@@ -1534,8 +1534,11 @@ SRK_DEV void adsr_seg_enter(const AdsrRegs& s, const AdsrConst& c, AdsrSeg& g)
     g.k0 = a ? 0.0f : 1.0f;
     g.k1 = a ? 1.0f : -1.0f;
     g.inc = a ? c.inc_a : (d ? c.inc_d : (r ? c.inc_r : 0.0f));
-    g.c0 = a ? s.r_val : ((d || su) ? c.s_val : 0.0f);
-    g.c1 = a ? 1.0f - s.r_val : (d ? 1.0f - c.s_val : (r ? c.s_val : 0.0f));
+    // (the terms a mode does not have are -0.0, the identity of the f32 sum, not +0.0: Release is s_val * u and Sustain s_val, and with
+    // +0.0 in their place a sustain level of -0.0 — valid like any f32 — came out as +0.0 where the reference holds -0.0: -0 + +0 = +0.
+    // Sustain's u is 1 - 0; None stays 0 + 0 * u.)
+    g.c0 = a ? s.r_val : ((d || su) ? c.s_val : (r ? -0.0f : 0.0f));
+    g.c1 = a ? 1.0f - s.r_val : (d ? 1.0f - c.s_val : (r ? c.s_val : (su ? -0.0f : 0.0f)));
     g.attack = __builtin_amdgcn_ballot_w64(a);
     g.on_high = __builtin_amdgcn_ballot_w64(!(a || d || su));  // None, Release: a high gate starts an attack
     g.on_low = __builtin_amdgcn_ballot_w64(su);                // Sustain: gate low starts the release

@@ -2,8 +2,10 @@
 // analysis as JSON.  tests/test_approx.py drives it, one case per structure the error budget has to get right.
 //   cfg <sample_rate> <buffer_size> <channels> | mod <type> | field <m> <f> <value> | ov <m> <f> <n> <v...> | step <m> <ch> <i> <state> <value>
 //   wave <m> <n> <v...> | conn <src> <port> <sink> <port> | exact
+// Values are read with strtod: "inf", "-inf" and "nan" (Python's repr of them) are values like any other — operator>> refuses them.
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <iostream>
 #include <sstream>
 #include <string>
@@ -19,6 +21,13 @@ static void num(std::ostream& o, double x)
     else o << x;
 }
 
+static double real(std::istream& in)
+{
+    std::string t;
+    in >> t;
+    return std::strtod(t.c_str(), nullptr);
+}
+
 int main()
 {
     Graph g;
@@ -31,10 +40,10 @@ int main()
         if (!(in >> op)) continue;
         if (op == "cfg") in >> g.cfg.sample_rate >> g.cfg.buffer_size >> g.cfg.channels;
         else if (op == "mod") { int t; in >> t; if (g.add_module(t) < 0) { std::fprintf(stderr, "add_module: %s\n", last_error()); return 2; } }
-        else if (op == "field") { int m, f; double v; in >> m >> f >> v; if (g.set_field(m, f, v) < 0) { std::fprintf(stderr, "set_field: %s\n", last_error()); return 2; } }
-        else if (op == "ov") { VoiceOverride o; size_t n; in >> o.module >> o.field >> n; o.values.resize(n); for (double& v : o.values) in >> v; ov.push_back(o); }
+        else if (op == "field") { int m, f; in >> m >> f; const double v = real(in); if (g.set_field(m, f, v) < 0) { std::fprintf(stderr, "set_field: %s\n", last_error()); return 2; } }
+        else if (op == "ov") { VoiceOverride o; size_t n; in >> o.module >> o.field >> n; o.values.resize(n); for (double& v : o.values) v = real(in); ov.push_back(o); }
         else if (op == "step") { int m, ch, i, st, v; in >> m >> ch >> i >> st >> v; g.set_step(m, ch, i, st, v); }
-        else if (op == "wave") { int m; size_t n; in >> m >> n; std::vector<float> w(n); for (float& v : w) in >> v; g.set_wave(m, w.data(), (uint32_t)n, 48000.0f); }
+        else if (op == "wave") { int m; size_t n; in >> m >> n; std::vector<float> w(n); for (float& v : w) v = (float)real(in); g.set_wave(m, w.data(), (uint32_t)n, 48000.0f); }
         else if (op == "conn") { int a, ap, b, bp; in >> a >> ap >> b >> bp; if (g.connect(a, ap, b, bp) < 0) { std::fprintf(stderr, "connect: %s\n", last_error()); return 2; } }
         else if (op == "exact") exact = true;
     }

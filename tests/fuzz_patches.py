@@ -281,3 +281,201 @@ def random_banked_patch(seed):
             if t == SMP and rng.random() < 0.35:   # honoured by the voices on the own wave, ignored by the banked ones
                 overrides.append((m, W.SAMPLE_WAVE_SAMPLE_RATE, lambda V, r=np.random.default_rng((seed, 0xBA2C, m, 3)): r.choice(BANK_RATES + [12345.0, 32000.0], V).astype(np.float32)))
     return B, build, overrides, banks, assignments
+
+
+# ---- the wide family: settings beyond the sliders (tests/test_gpu_wide_fuzz.py, tests/test_wide_fuzz_host.py, tools/cpu_soak.py --family wide) ----
+# Nothing in the library clamps a field: every value below is valid for the ABI.  Each module is *wide* with probability one half and draws
+# from the table; the others draw as random_patch does, so wide values meet ordinary neighbours.
+WIDE_OSC_ODD = [-1100.0, -150.0, -130.0, -113.0, 130.0, 1100.0]   # (below about -119.2 the increment 440 x 2^val / 48 000 is no normal f32)
+WIDE_OSC_UNDERFLOW = -119.0
+WIDE_ADSR_TIMES = [0.0, -0.01, 1e-6, 1e-4, 0.02, 30.0]
+WIDE_SPO = [0, 1, 5, 19, 65535]
+WIDE_SPO_P = [0.4, 0.15, 0.15, 0.15, 0.15]   # (0 is the value that has no bound: drawn more often than the others)
+WIDE_WAVE_RATES = [1.0, 100.0, 384000.0, 3e6]
+WIDE_SPECIALS = [np.inf, -np.inf, np.nan, 1e-40, -0.0, 3e38, -3e38]
+WIDE_CLASSES = ("osc", "vcf", "adsr", "gain", "nonlin", "spo", "smp", "verb")          # the table's rows ...
+WIDE_SUBCLASSES = ("adsr_neg", "osc_underflow", "spo0")                                    # ... and three kinds of value inside them
+# the RNG streams, one per sub-family: chosen so that the pinned seeds meet the guards' bars (tests/test_wide_fuzz_host.py; notes/r28.md R28.3 has the search)
+WIDE_STREAMS = {"plain": 123, "noise": 89, "nonlin": 4982, "special": 25}
+
+
+def _wide_tags(cls, f, v):
+    tags = {cls}
+    if cls == "adsr" and f != W.ADSR_S_VAL and v < 0:
+        tags.add("adsr_neg")
+    if cls == "osc" and v < WIDE_OSC_UNDERFLOW:
+        tags.add("osc_underflow")
+    if cls == "spo" and v == 0:
+        tags.add("spo0")
+    return tags
+
+
+def random_wide_patch(seed, noise=False, special=False, clamp=()):
+    """-> (B, build(g) -> ids, overrides): random_patch's graph draw (types, wiring rule, cycles, the OutputModule anywhere; FUZZ_NONLIN as
+    there) from streams of its own, with half of the modules *wide* (the table in notes/r28.md).  Per-voice overrides by random_patch's 0.45
+    rule over more fields; for a wide module voice 0 and every fourth voice draw from today's range and the rest from the wide one.
+    special: each float setting (patch level, or one voice of an override) is replaced with probability 0.06 by one of WIDE_SPECIALS.
+    clamp: names out of WIDE_CLASSES / WIDE_SUBCLASSES — the wide values of that kind are clamped back into today's range (the guards'
+    "is this class heard" question); the rest of the patch keeps its draw.  build.types / .wide ({m: class}) / .kinds (the kinds of wide value at patch level) describe the patch."""
+    stream = WIDE_STREAMS["noise" if noise else "special" if special else "nonlin" if os.environ.get("FUZZ_NONLIN") else "plain"]
+    tag = (seed, 0x51DE, stream, int(noise), int(special))
+    rng, wr, sr_ = np.random.default_rng(tag), np.random.default_rng(tag + (1,)), np.random.default_rng(tag + (2,))
+    clamp = set(clamp)
+    f32 = lambda v: float(np.float32(v))
+    B = int(rng.choice([1, 3, 16, 64, 1024]))
+    n = int(rng.integers(4, 11))
+    types = [OSC, OSC] + [int(rng.choice([OSC, VCF, ADSR, VCA, MIX, MATH, GRID, PAT, SMP], p=[.2, .15, .12, .13, .1, .15, .05, .05, .05])) for _ in range(n - 2)]
+    rng.shuffle(types)
+    if noise:
+        types = [NOISE if u < 0.2 else VERB if u < 0.3 else t for t, u in zip(types, rng.random(n))]
+        if NOISE not in types:
+            types[int(rng.integers(0, n))] = NOISE
+    if os.environ.get("FUZZ_NONLIN"):
+        r3 = np.random.default_rng(tag + (9,))
+        types = [NONLIN if t == MATH and r3.random() < 0.5 else t for t in types]
+    is_wide = [bool(u < 0.5) for u in wr.random(n)]
+    fields, steps, conns, waves, wide, kinds = [], [], [], [], {}, set()
+
+    def put(m, f, today, wide_value, cls, lo, hi):
+        """one float setting: today's draw, or (wide module) the wide one — clamped into today's [lo, hi] where `clamp` names its kind"""
+        v = today
+        if is_wide[m]:
+            v, wide[m] = f32(wide_value), cls
+            kinds.update(_wide_tags(cls, f, v))
+            if _wide_tags(cls, f, v) & clamp:
+                v = min(max(v, lo), hi)
+        fields.append((m, f, f32(v)))
+
+    for m, t in enumerate(types):
+        if t == OSC:
+            odd = wr.random() < 0.1
+            put(m, W.OSC_VAL, rng.uniform(-6, 3), wr.choice(WIDE_OSC_ODD) if odd else wr.uniform(-14, 9), "osc", -6.0, 3.0)
+            if rng.random() < 0.2:
+                fields.append((m, W.OSC_ANTIALIASING, 0))
+        elif t == VCF:
+            put(m, W.VCF_FREQ, rng.uniform(0.02, 0.8), wr.uniform(-0.3, 1.4), "vcf", 0.02, 0.8)
+            put(m, W.VCF_RES, rng.uniform(0, 1), wr.uniform(-0.5, 1.6), "vcf", 0.0, 1.0)
+            put(m, W.VCF_EXP_AMT, rng.uniform(0, 1), wr.uniform(-3, 3), "vcf", 0.0, 1.0)
+        elif t == ADSR:
+            put(m, W.ADSR_A_SEC, rng.choice([0.0, 0.001, 0.004]), wr.choice(WIDE_ADSR_TIMES), "adsr", 0.0, 0.004)
+            put(m, W.ADSR_D_SEC, rng.uniform(0.001, 0.01), wr.choice(WIDE_ADSR_TIMES), "adsr", 0.001, 0.01)
+            put(m, W.ADSR_S_VAL, rng.uniform(0, 1), wr.uniform(-1.5, 2.5), "adsr", 0.0, 1.0)
+            put(m, W.ADSR_R_SEC, rng.uniform(0.001, 0.01), wr.choice(WIDE_ADSR_TIMES), "adsr", 0.001, 0.01)
+        elif t == VCA:
+            fields.append((m, W.VCA_NEGATIVE, int(rng.random() < 0.3)))
+        elif t == MIX:
+            for k in range(4):
+                put(m, W.MIX_GAIN0 + k, rng.uniform(0, 1.2), wr.uniform(-12, 12), "gain", 0.0, 1.2)
+        elif t == MATH:
+            put(m, W.MATH_CONSTANT, rng.uniform(-1, 1), wr.uniform(-12, 12), "gain", -1.0, 1.0)
+            fields.append((m, W.MATH_OPERATION, int(rng.integers(0, 3))))
+        elif t == NONLIN:
+            put(m, W.NONLIN_CONSTANT, rng.choice([0.5, 2.0, 3.0, rng.uniform(0.3, 3.0)]), wr.choice([0.0, 1.0, wr.uniform(-1, 6), wr.uniform(-1, 6)]), "nonlin", 0.3, 3.0)
+        elif t == VERB:
+            for f, lo, hi in ((W.FREEVERB_DAMPENING, 0, 2), (W.FREEVERB_WET, 0, 1), (W.FREEVERB_WIDTH, 0, 1), (W.FREEVERB_ROOM_SIZE, 0, 1), (W.FREEVERB_DRY, 0, 1)):
+                put(m, f, rng.uniform(lo, hi), wr.uniform(-0.5, 2.5), "verb", float(lo), float(hi))
+            fields.append((m, W.FREEVERB_FREEZE, int(rng.random() < 0.2)))
+        elif t == SMP:
+            wave, rate = rng.uniform(-1, 1, int(rng.integers(1, 400))).astype(np.float32), float(rng.choice([8000.0, 44100.0, 48000.0, 96000.0]))
+            if is_wide[m]:
+                wide[m] = "smp"
+                kinds.add("smp")
+                loud, fast = (wave * np.float32(8.0)).astype(np.float32), float(wr.choice(WIDE_WAVE_RATES))
+                if "smp" not in clamp:
+                    wave, rate = loud, fast
+            waves.append((m, wave, rate))
+        elif t in (GRID, PAT):
+            length = int(rng.integers(1, 9))
+            fields.append((m, W.GRIDSEQ_LENGTH if t == GRID else W.PATSEQ_LENGTH, length))
+            for i in range(length):
+                for ch in ([0] if t == GRID else [0, 3, 7]):
+                    steps.append((m, ch, i, int(rng.integers(0, 3)), int(rng.integers(0, 25))))
+            if t == GRID and is_wide[m]:
+                spo, wide[m] = int(wr.choice(WIDE_SPO, p=WIDE_SPO_P)), "spo"
+                kinds.update(_wide_tags("spo", 0, spo))
+                fields.append((m, W.GRIDSEQ_STEPS_PER_OCTAVE, 12 if _wide_tags("spo", 0, spo) & clamp else spo))
+    for m, t in enumerate(types):
+        for k in range(N_IN[t]):
+            if rng.random() < 0.75:
+                src = int(rng.integers(0, n - 1))
+                src += src >= m
+                conns.append((src, int(rng.choice(OUT_PORTS[types[src]])), m, k))
+    # (a NonLinear's exponent is its setting only while nothing is wired to its exponent input: a wide one keeps that input free — the wire
+    # is drawn and dropped, so the rest of the patch keeps its draw.  Without this three in four wide exponents are dead settings.)
+    conns = [c for c in conns if not (types[c[2]] == NONLIN and c[3] == 1 and is_wide[c[2]])]
+    out_src = [int(rng.integers(0, n)) for _ in range(2)]
+    out_conns = [(s, int(rng.choice(OUT_PORTS[types[s]])), c) for c, s in enumerate(out_src) if rng.random() < 0.9]
+    if not out_conns:
+        out_conns = [(out_src[0], OUT_PORTS[types[out_src[0]]][0], 0)]
+    out_pos = int(rng.integers(0, n + 1))
+
+    # ---- per-voice overrides: (field, today's lo, hi, wide draw(r, V) -> values) per type; a module passes the 0.45 rule, then a non-empty subset of its fields ----
+    times = lambda r, V: r.choice(WIDE_ADSR_TIMES, V)
+    table = {OSC: [(W.OSC_VAL, -5.0, 2.0, lambda r, V: np.where(r.random(V) < 0.1, r.choice(WIDE_OSC_ODD, V), r.uniform(-14, 9, V)))],
+             VCF: [(W.VCF_FREQ, 0.03, 0.7, lambda r, V: r.uniform(-0.3, 1.4, V)), (W.VCF_RES, 0.0, 1.0, lambda r, V: r.uniform(-0.5, 1.6, V)),
+                   (W.VCF_EXP_AMT, 0.0, 1.0, lambda r, V: r.uniform(-3, 3, V))],
+             ADSR: [(W.ADSR_A_SEC, 0.0, 0.004, times), (W.ADSR_D_SEC, 0.001, 0.01, times), (W.ADSR_S_VAL, 0.0, 1.0, lambda r, V: r.uniform(-1.5, 2.5, V)),
+                    (W.ADSR_R_SEC, 0.001, 0.01, times)],
+             MIX: [(W.MIX_GAIN0 + 1, 0.0, 1.0, lambda r, V: r.uniform(-12, 12, V))],
+             MATH: [(W.MATH_CONSTANT, -1.0, 1.0, lambda r, V: r.uniform(-12, 12, V))],
+             NONLIN: [(W.NONLIN_CONSTANT, 0.3, 3.0, lambda r, V: np.where(r.random(V) < 0.2, r.choice([0.0, 1.0], V), r.uniform(-1, 6, V)))],
+             GRID: [(W.GRIDSEQ_STEPS_PER_OCTAVE, 12, 12, lambda r, V: r.choice(WIDE_SPO, V, p=WIDE_SPO_P))]}
+    cls_of = {OSC: "osc", VCF: "vcf", ADSR: "adsr", MIX: "gain", MATH: "gain", NONLIN: "nonlin", GRID: "spo"}
+    overrides = []
+    for m, t in enumerate(types):
+        if rng.random() < 0.45 and t in table and not (t == GRID and not is_wide[m]):   # (an ordinary sequencer keeps its 12 steps per octave)
+            rows = table[t]
+            picked = [rows[k] for k in range(len(rows)) if len(rows) == 1 or rng.random() < 0.5] or [rows[int(rng.integers(0, len(rows)))]]
+            for f, lo, hi, draw in picked:
+                def values(V, m=m, f=f, lo=lo, hi=hi, draw=draw, cls=cls_of[t]):
+                    r = np.random.default_rng(tag + (3, m, f))
+                    integer = f == W.GRIDSEQ_STEPS_PER_OCTAVE and t == GRID
+                    today = np.full(V, 12.0) if integer else r.uniform(lo, hi, V)
+                    vals = today.astype(np.float32)
+                    if is_wide[m]:
+                        wv = np.asarray(draw(r, V), dtype=np.float64).astype(np.float32)
+                        keep = np.array([bool(_wide_tags(cls, f, float(x)) & clamp) for x in wv])   # clamped: back into today's range
+                        wv = np.where(keep, np.clip(wv, np.float32(lo), np.float32(hi)), wv).astype(np.float32)
+                        ordinary = np.arange(V) % 4 == 0     # voice 0 and every fourth voice: today's range
+                        vals = np.where(ordinary, vals, wv).astype(np.float32)
+                        if special and not integer:
+                            rs = np.random.default_rng(tag + (4, m, f))
+                            hit = rs.random(V) < 0.06
+                            vals = np.where(hit, rs.choice(WIDE_SPECIALS, V).astype(np.float32), vals).astype(np.float32)
+                    elif special and not integer:
+                        rs = np.random.default_rng(tag + (4, m, f))
+                        hit = rs.random(V) < 0.06
+                        vals = np.where(hit, rs.choice(WIDE_SPECIALS, V).astype(np.float32), vals).astype(np.float32)
+                    return vals
+                overrides.append((m, f, values))
+                if is_wide[m]:
+                    wide[m] = cls_of[t]
+    if special:   # patch level: every float setting (the integer-typed fields keep integers of their type)
+        ints = {(OSC, W.OSC_ANTIALIASING), (VCA, W.VCA_NEGATIVE), (MATH, W.MATH_OPERATION), (VERB, W.FREEVERB_FREEZE), (GRID, W.GRIDSEQ_LENGTH),
+                (GRID, W.GRIDSEQ_STEPS_PER_OCTAVE), (PAT, W.PATSEQ_LENGTH)}
+        fields = [(m, f, v) if (types[m], f) in ints or sr_.random() >= 0.06 else (m, f, float(np.float32(sr_.choice(WIDE_SPECIALS)))) for m, f, v in fields]
+
+    def build(g):
+        ids = []
+        for i, t in enumerate(types):
+            if i == out_pos:
+                build.out = g.add_module(0)
+            ids.append(g.add_module(t))
+        if out_pos == n:
+            build.out = g.add_module(0)
+        for m, f, v in fields:
+            g.set_field(ids[m], f, v)
+        for m, ch, i, st, val in steps:
+            g.set_step(ids[m], ch, i, st, val)
+        for m, wave, rate in waves:
+            g.set_wave(ids[m], wave, rate)
+        for s, sp, k, kp in conns:
+            g.connect(ids[s], sp, ids[k], kp)
+        for s, sp, c in out_conns:
+            g.connect(ids[s], sp, build.out, c)
+        if noise:
+            g.set_noise_seed(seed * 7919 + 1, 1000 * seed)
+        return ids
+
+    build.types, build.wide, build.kinds, build.fields, build.conns, build.out_conns = list(types), dict(wide), set(kinds), list(fields), list(conns), list(out_conns)
+    return B, build, overrides

@@ -448,6 +448,104 @@ def test_a_shaper_behind_an_unbounded_gain_loses_its_f32_form_only(probe):
     assert r["bound"] == pytest.approx(4e-6 * max(1.0, r["mag"][second][0]) if r["nonlin_loose"][second] else 0.0, rel=1e-3)
 
 
+# ---- settings beyond the sliders: nothing clamps a field, so the magnitudes have to follow what the reference does with them ---------------------
+def test_an_envelope_with_a_time_that_runs_backwards_has_no_bound(probe):
+    """adsr.rs:150-190: the phase moves by 1 / (sample_rate * sec) and a stage ends at phase >= 1.  A negative time — -0.0 included — or a NaN
+    never gets there: the stage's line is followed for as long as the gate leaves it alone (the oracle, a 55 Hz square on the gate, A_SEC =
+    -0.01: -836 after 6 000 samples and falling).  The wide fuzz family's find: such an envelope (A -0.01, S 1.25) on a ladder's audio input,
+    the ladder left contracted with a bound of 4.2e-6 and the emulated form at 3.0e-5.  Zero, tiny and huge times are bounded: the real
+    supremum, max(1, |S_VAL|)."""
+    def patch(field, value, s_val=0.5, per_voice=None):
+        g, (lfo, env, vcf, out) = chain(OSC, ADSR, VCF)
+        g.set_field(lfo, W.OSC_VAL, -3.0)
+        g.set_field(env, W.ADSR_S_VAL, s_val)
+        g.set_field(env, field, value)
+        if per_voice is not None:
+            g.override(env, field, per_voice)
+        g.connect(lfo, SQUARE, env, 0)
+        g.connect(env, 0, vcf, 0)
+        g.connect(vcf, 1, out, 0)
+        return g, env, vcf
+    for field in (W.ADSR_A_SEC, W.ADSR_D_SEC, W.ADSR_R_SEC):
+        for value in (-0.01, -0.0, float("nan"), -1e-30):
+            g, env, vcf = patch(field, value)
+            r = g.run(probe)
+            assert r["mag"][env][0] == float("inf") and r["exact_patch"] and "unbounded values" in r["why"], (field, value)
+        for value in (0.0, 1e-6, 1e-40, 30.0, 3e38, float("inf"), float("-inf")):   # (an infinite time of either sign: an increment of +-0, the stage stands still)
+            g, env, vcf = patch(field, value, s_val=1.25)
+            r = g.run(probe)
+            assert r["mag"][env][0] == 1.25 and not r["exact_patch"] and r["literal"][vcf] == 0, (field, value)
+        g, env, vcf = patch(field, 0.004, per_voice=[0.004, 0.001, -0.01, 0.002])   # one voice is enough, and it is neither the first nor the last
+        assert g.run(probe)["mag"][env][0] == float("inf")
+        g, env, vcf = patch(field, -0.01, per_voice=[0.004, 0.001, 0.002])          # the patch's value is nobody's once every voice has its own
+        assert g.run(probe)["mag"][env][0] == 1.0
+    g, env, vcf = patch(W.ADSR_S_VAL, -1.5)        # a sustain level outside 0 ... 1 is bounded: by itself
+    r = g.run(probe)
+    assert r["mag"][env][0] == 1.5 and not r["exact_patch"]
+    g, env, vcf = patch(W.ADSR_S_VAL, float("nan"))   # ... and one that is no number is not (at patch level as in an override)
+    assert g.run(probe)["mag"][env][0] == float("inf")
+
+
+def test_an_increment_that_is_no_normal_f32_keeps_the_f64_forms(probe):
+    """The f32 PolyBLEP takes dt and 1 / dt as f32 and the fixed-point phase dt x 2^64: at OSC_VAL = -150 (dt = 6e-48) dt rounds to 0, 1 / dt to
+    infinity, and the carried-phase saw is a NaN on every sample where the reference renders a finite ramp; at -130 dt is a subnormal and 1 / dt
+    infinite.  The smallest increment any voice has must be a normal f32 (440 x 2^val / 48 000 >= 2^-126: val >= -119.23)."""
+    for val, per_voice, f32_forms in ((-113.0, None, True), (-119.0, None, True), (-119.5, None, False), (-130.0, None, False), (-150.0, None, False), (-1100.0, None, False),
+                                      (float("-inf"), None, False), (float("nan"), None, False), (0.0, [0.0, -150.0, 2.0], False), (-150.0, [0.0, -3.0], True), (130.0, None, True)):
+        for port in (SAW, SQUARE):
+            g, (osc, out) = chain(OSC)
+            g.set_field(osc, W.OSC_VAL, val)
+            if per_voice is not None:
+                g.override(osc, W.OSC_VAL, per_voice)
+            g.connect(osc, port, out, 0)
+            r = g.run(probe)
+            assert r["exact_blep"][osc] == (0 if f32_forms else 1) and not r["exact_patch"], (val, per_voice, port, r)
+            if not f32_forms:
+                assert r["saw_fixed"][osc] == 0 and r["bound"] == 0.0
+    # a pitch CV lowers the smallest increment by its magnitude: a unit sine on the pitch of an oscillator at -119 passes the limit
+    g, (lfo, osc, out) = chain(OSC, OSC)
+    g.set_field(lfo, W.OSC_VAL, -8.0)
+    g.set_field(osc, W.OSC_VAL, -119.0)
+    g.connect(lfo, SINE, osc, 0)
+    g.connect(osc, SAW, out, 0)
+    assert g.run(probe)["exact_blep"][osc] == 1
+    g.lines = [l.replace(f"field {osc} {W.OSC_VAL} -119.0", f"field {osc} {W.OSC_VAL} -6.0") for l in g.lines]
+    assert g.run(probe)["exact_blep"][osc] == 0
+
+
+def test_a_grid_note_is_divided_by_the_real_steps_per_octave(probe):
+    """sequencer.rs:236: val * (1.0 / steps_per_octave).  12 by default; the rack file's reader admits 0 ... 65535.  At 0 the note is an
+    infinity (a NaN for note 0): no bound — until the wide fuzz family the analysis divided by max(1, spo)."""
+    def patch(spo, per_voice=None, note=24, on=True):
+        g, (clock, seq, osc, out) = chain(OSC, GRID, OSC)
+        g.set_field(clock, W.OSC_VAL, -6.0)
+        g.set_field(seq, W.GRIDSEQ_STEPS_PER_OCTAVE, spo)
+        if per_voice is not None:
+            g.override(seq, W.GRIDSEQ_STEPS_PER_OCTAVE, per_voice)
+        if on:
+            g.set_step(seq, 0, 0, W.STEP_ON, note)
+        g.connect(clock, SQUARE, seq, 0)
+        g.connect(seq, W.GRIDSEQ_OUT_CV, osc, 0)
+        g.connect(osc, SAW, out, 0)
+        return g, seq
+    for spo, mag in ((12, 2.0), (1, 24.0), (5, 4.8), (19, 24 / 19), (65535, 24 / 65535)):
+        g, seq = patch(spo)
+        r = g.run(probe)
+        assert r["mag"][seq][0] == pytest.approx(mag) and not r["exact_patch"], spo
+    g, seq = patch(0)
+    r = g.run(probe)
+    assert r["mag"][seq][0] == float("inf") and r["exact_patch"] and "unbounded values" in r["why"]
+    g, seq = patch(12, per_voice=[12, 5, 0, 19])    # one voice is enough
+    assert g.run(probe)["mag"][seq][0] == float("inf")
+    g, seq = patch(12, per_voice=[12, 5, 1, 19])    # ... and the smallest of the others decides
+    assert g.run(probe)["mag"][seq][0] == pytest.approx(24.0)
+    g, seq = patch(0, note=0)                        # 0 x inf: a NaN
+    assert g.run(probe)["mag"][seq][0] == float("inf")
+    g, seq = patch(0, on=False)                      # no cell is on: the held CV, 0
+    r = g.run(probe)
+    assert r["mag"][seq][0] == 0.0 and not r["exact_patch"]
+
+
 # ---- the budget is shared ----------------------------------------------------------------------------------------------------------------------
 def test_forms_are_denied_largest_first_until_the_channel_fits(probe):
     g, (osc, vcf, out) = chain(OSC, VCF)

@@ -1,1911 +1,17 @@
-// jit.cpp — the general path's fast half: a voice kernel SPECIALISED for one flattened program.
-//
-// The hand-matched fused kernels (fused.hip.h, seq.hip.h, fm_pair.hip.h, fm_block.hip.h) cover five patch shapes; the tile interpreter (interp.hip.h) covers everything
-// but pays for its generality — every wire makes a round trip through LDS, every module is a call with its state loaded and
-// stored per tile (P1 through it: 0.21 of the HBM roofline where the fused kernel reaches 0.57).  Here the flattened op list is
-// turned into ONE straight-line HIP kernel over the very same per-module device functions (modules.hip.h): wires are
-// registers, module state lives in registers for the whole launch, control tracks arrive through scalar loads, frames leave
-// through buffer stores, the mix-down goes through the same LDS transpose tile as in the fused kernels (wave.hip.h).  The
-// source is compiled for the device's architecture with hiprtc the first time a program STRUCTURE is seen (op kinds, flags,
-// wiring, which parameters are per-voice rows; parameter values are read from the op list at run time) and cached.
-//
-// Reference semantics held: one calc() per planned module per sample in plan order (src/synth.rs:97-101); a broken feedback
-// edge is a buffer_size-sample delay.  What the generator does not cover falls back to the interpreter
-// (jit_supported): FreeverbModule (its 24 delay lines per voice live in HBM and have their own tile function).
+// jit.cpp — the loaded kernel of the general path's fast half: a generated source (jit_gen.cpp) is fetched as a code object
+// (jit_cache.cpp), loaded as a module on the current device and launched.  The only part of the three that needs a device.
 #include "jit.hpp"
 
-#include <dirent.h>
-#include <dlfcn.h>
-#include <fcntl.h>
 #include <hip/hip_runtime.h>
-#include <sys/file.h>
-#include <sys/stat.h>
-#include <sys/time.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <array>
-#include <cerrno>
-#include <chrono>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <future>
-#include <list>
-#include <map>
 #include <memory>
-#include <set>
-#include <mutex>
-#include <sstream>
 #include <string>
 #include <vector>
 
-#include "jit_headers.inc"  // generated by the Makefile: the device headers as string literals (kJitHeaderNames / kJitHeaderBodies)
-
 namespace srack {
-
-namespace {
-
-// ---- code generation ---------------------------------------------------------------------------------------------------
-
-struct Gen {
-    const FlatProgram& P;
-    int out_mode;  // 1 frames, 2 mix, 3 both, 4 neither (the render only advances the voice state)
-    std::ostringstream lds_rings, pro, tile_begin, body, tile_end, epi;
-    bool needs_sync = false;     // LDS arrays filled in the prologue are read by other lanes
-    int want_waves = 0;          // waves per SIMD the render has for this kernel (0: unknown) — what LDS beyond the mix tile it may spend
-    int smp_lds_bytes = 0;       // LDS the sample players of this kernel have taken for staged waves so far (gen_sample)
-    bool lds_tables = false;     // the pow tables of NonLinear / the sample player are in LDS (declared once per function)
-    bool uses_ring_pos = false;  // some ring is addressed by the running position (n0 + t) mod buffer_size
-    std::map<int, std::string> slot;  // wire slot -> the expression that currently holds it
-    std::vector<int> tracks_used;
-    // further per-sample values that are fetched a group of samples ahead and handed to the sample function as arguments:
-    // (name, expression in terms of the sample index `i`)
-    std::vector<std::pair<std::string, std::string>> sample_args;
-    // Wave-uniform conditions the sample loop is versioned on: when all of them hold (the common case) a copy of the loop runs in
-    // which each is a constant — (condition, the declaration that shadows it inside that copy).  The other copy keeps every arm.
-    std::vector<std::pair<std::string, std::string>> fast_conds;
-    // wire slot -> the tracks its value is a pure function of (with launch / per-voice constants): outputs of the stateless
-    // arithmetic modules fed by such values.  Absent: the value has a history (an oscillator, a filter, an envelope, a delay ...).
-    std::map<int, std::set<int>> pure_of, pure_in;
-    bool pure_deps(int s, std::set<int>& deps)
-    {
-        if (s < 0) return true;  // an unconnected input: the constant 0.0
-        if (s >= kTrackSlot) {
-            deps.insert(s - kTrackSlot);
-            return true;
-        }
-        const auto it = pure_in.find(s);
-        if (it == pure_in.end()) return false;
-        deps.insert(it->second.begin(), it->second.end());
-        return true;
-    }
-    std::map<int, std::string> bounded_if, bounded_in;  // wire slot -> wave-uniform condition under which its value is finite and small
-    // Quiet groups (modules.hip.h, cosc_quiet_init): event machines — a gate LFO, the envelope behind it — ask once per group of kQuietGroup
-    // samples whether any lane can have an event within the group; a group without one runs a second copy of the sample function in which
-    // their per-sample questions are gone (`kQuiet`).  group_begin: evaluated at the start of every group (declares the per-group values);
-    // quiet_lane: the per-lane conditions, all of which must hold in every lane; group_end_quiet: after a quiet group's samples.
-    // quiet_of / quiet_in: wire slot -> the expression of its value where that is one constant for a whole quiet group (as pure_of / pure_in).
-    std::ostringstream group_decl, group_begin, group_end_quiet;  // (group_decl: per-group values the sample function reads, declared ahead of it)
-    std::vector<std::string> quiet_lane;
-    // A group that is not quiet as a whole takes the literal per-sample copy (with the modules' cold arms) for all of its samples, unrolled.
-    // MEASURED AND NOT TAKEN (round 6, SRACK_JIT_HALVE=1, tools/): HALVING such a group — its two halves of four samples ask the same question
-    // for themselves, a half that is not quiet its two pairs, a pair its two samples, and only a sample in which some lane really has an
-    // event takes the literal copy (events are single samples of single lanes: seven of the eight samples then run the event-free copy behind
-    // five to seven group questions).  cfg3_poly, one box, alternating: 18.39 / 17.86 ms per step halved against 16.38 / 16.24 unrolled —
-    // every question is a ballot and a branch in a rolled loop, and the literal copy loses its unrolling; the questions cost more than the
-    // literal samples they save (the same verdict as rounds 4 and 5's per-sample "calm" walks, whose generator code is gone).
-    // `{LEN}` / `{LI}` in the per-group texts: the group's length and its index into the per-length guards (8, 4, 2, 1 -> 0 .. 3).
-    std::map<int, std::string> quiet_of, quiet_in;
-    std::map<int, std::string> env_of, env_in;  // wire slot -> the envelope (its variables' prefix) whose quiet form produced it: a VCA behind it decides `cv > 0` per group
-    static bool halve_groups()
-    {
-        static const bool on = [] {
-            const char* e = getenv("SRACK_JIT_HALVE");
-            return e && e[0] == '1';
-        }();
-        return on;
-    }
-    static std::string subst(std::string text, const std::string& len, const std::string& li)
-    {
-        for (const auto& kv : {std::make_pair(std::string("{LEN}"), len), std::make_pair(std::string("{LI}"), li)})
-            for (size_t at = text.find(kv.first); at != std::string::npos; at = text.find(kv.first, at)) text.replace(at, kv.first.size(), kv.second);
-        return text;
-    }
-    static std::string indent(const std::string& text, int by)
-    {
-        std::istringstream in(text);
-        std::string line, out;
-        while (std::getline(in, line)) out += std::string((size_t)by, ' ') + line + "\n";
-        return out;
-    }
-    static int nq_unroll()  // experiment knob (tools/): how far the per-sample copy of a quiet-group kernel is unrolled
-    {
-        const char* e = getenv("SRACK_JIT_NQ_UNROLL");
-        const int v = e ? atoi(e) : 8;
-        return v >= 1 && v <= 8 ? v : 8;
-    }
-    static bool quiet_enabled()  // SRACK_JIT_QUIET=0 (tools/): the per-sample forms only, for A/B runs
-    {
-        static const bool on = [] {
-            const char* e = getenv("SRACK_JIT_QUIET");
-            return !(e && e[0] == '0');
-        }();
-        return on;
-    }
-    std::map<int, bool> ring_declared;
-    int n_mix = 0;
-    bool needs_full_unroll = false;  // a ring prefetch array is indexed by the sample's position in the tile
-    std::string err;
-
-    bool is_ctl = false;      // a unit of the control program (one voice): its planes are tracks, written 32 samples per store
-    // A control unit whose every module has a tile-wise form is evaluated ACROSS LANES: lane j holds sample j of the tile.  Stateless
-    // modules (VCA, mixer, math, waveshaper) simply compute 32 samples with one instruction each; a constant-pitch oscillator runs its
-    // two-instruction phase recurrence and evaluates the outputs per lane (cosc_tile); an envelope takes whole runs of samples between
-    // the events that can end its segment (adsr_seg_tile).  One voice on one wave is a latency chain — ~14 cycles per dependent
-    // instruction, ~40 per branch —, so the sample-by-sample form costs 35 ... 100 ns per sample and module (tools/unit_times.py).
-    bool across_lanes = false;
-    std::string uniq;         // prefix of this function's __shared__ arrays (static LDS names share the kernel's scope)
-
-    // LDS tiles of 32 rows x 64 lanes (wave.hip.h: kMixTile floats).  Every wire-fed output plane owns one for the mix-down; an
-    // exact-mode saw oscillator needs one for its tile-wise evaluation (modules.hip.h, XSaw) and borrows the tile of an output
-    // op that comes LATER in the op list: within a sample its row is read (at the oscillator's position) before the plane's
-    // sample overwrites it (at the output op's position), and the whole tile is written before the sample loop starts.
-    std::map<int, int> tile_of_out;     // OUT op index -> tile (planes fed by a wire, when the mix-down is on)
-    std::map<int, bool> out_tile_lent;  // ... already borrowed by an oscillator
-    int n_tiles = 0;
-    std::vector<std::string> shared_emits;  // the Emit objects of the planes that share the tile, in plane order
-    int rows_per_plane = 0;             // > 0: the planes share tile 0, plane j (tile_of_out's numbering) owns rows [j, j + 1) * rows_per_plane
-
-    // ---- what is known about a wire ahead of time (voice programs): for the oscillators' pitch inputs ----------------------------------
-    // The hand-written FM pair proves, per wave and launch, that its oscillators' CVs are bounded — a sine through a constant gain —
-    // and takes a sample loop without range reduction, with a one-instruction phase wrap and val folded into a per-launch scale
-    // (fm_common.hip.h, fm_facts).  The generator derives the same for ANY program: a magnitude bound per wire as an expression in the
-    // program's parameters (|sine| <= 1, |saw|, |square| <= 2, |lowpass| <= 1, products and sums through Math / VCA / mixer, a delayed
-    // edge inherits its source's), and every oscillator whose CV has one is VERSIONED: the wave votes once per launch (bound classes,
-    // phases in [0, 1), ring contents within their bound) and runs the copy of the sample loop compiled for its classes
-    // (modules.hip.h, fm_class_flags) — or the literal forms when the vote fails.  A launch is proved as a whole or not at all.
-    struct Fact {
-        std::string bound;     // per-lane float expression over parameters: |value| <= bound all launch long, given the vote; "": unknown
-        bool audio = false;    // changes from sample to sample (an oscillator, a filter, an envelope, noise ... somewhere upstream)
-        std::set<int> oscs;    // oscillators (op indices) whose phase must be, and stay, in [0, 1) for the bound to hold
-        std::set<int> rings;   // DELAY_RD ops whose stored values must be within their bound when the launch starts
-        std::set<std::string> also;  // further per-lane conditions of the vote, ready-made (an envelope's increments are not negative ...)
-    };
-    std::vector<Fact> cv_fact;            // per op (OP_OSC): what is known about its CV input
-    std::vector<Fact> rd_fact;            // per op (OP_DELAY_RD): what it hands on
-    std::vector<int> fm_index;            // per op: which versioned oscillator it is (-1: none)
-    std::vector<int> fm_ops;              // the versioned oscillators, in op order
-    std::map<int, std::string> osc_pos, osc_delta;  // per oscillator op: the expressions of its phase / its constant increment ("" = host-proved)
-    std::map<int, std::string> ring_check_of;       // per local ring (first state row): the same, as its declaration spells the ring
-    std::map<int, std::string> ring_check;          // per DELAY_RD op: "every stored value is within `B`" with B to be substituted for @
-    static Fact fact_join(const Fact& a, const Fact& b, const std::string& bound)
-    {
-        Fact f;
-        f.bound = (a.bound.empty() || b.bound.empty()) ? "" : bound;
-        f.audio = a.audio || b.audio;
-        f.oscs = a.oscs;
-        f.oscs.insert(b.oscs.begin(), b.oscs.end());
-        f.rings = a.rings;
-        f.rings.insert(b.rings.begin(), b.rings.end());
-        f.also = a.also;
-        f.also.insert(b.also.begin(), b.also.end());
-        return f;
-    }
-    static bool fm_enabled()  // SRACK_JIT_FM=0 (tools/): every oscillator keeps the literal forms, for A/B runs
-    {
-        static const bool on = [] {
-            const char* e = getenv("SRACK_JIT_FM");
-            return !(e && e[0] == '0');
-        }();
-        return on;
-    }
-    // which op wrote the value wire slot `s` holds when op `at` reads it, and through which port
-    bool producer_of(int s, int at, int& op_out, int& port_out) const
-    {
-        for (int k = at - 1; k >= 0; k--)
-            for (int p = 0; p < kMaxOut; p++)
-                if (P.ops[(size_t)k].out_slot[p] == s) {
-                    op_out = k;
-                    port_out = p;
-                    return true;
-                }
-        return false;
-    }
-    void analyze()
-    {
-        const int n = (int)P.ops.size();
-        cv_fact.assign((size_t)n, Fact{});
-        rd_fact.assign((size_t)n, Fact{});
-        fm_index.assign((size_t)n, -1);
-        fm_ops.clear();
-        if (is_ctl) return;
-        const bool bounds = !(P.render_flags & SRACK_RENDER_EXACT_OSC) && fm_enabled();
-        const int B = P.hdr.buffer_size;
-        std::set<int> distrusted;  // oscillators a delayed edge took for bounded although their own CV is not
-        for (int iter = 0; iter <= n; iter++) {
-            std::map<int, Fact> cur;
-            std::set<int> assumed;
-            auto get = [&](int sl) -> Fact {
-                Fact f;
-                if (sl < 0) {
-                    f.bound = "0.0f";  // an unconnected input reads 0.0
-                    return f;
-                }
-                if (sl >= kTrackSlot) return f;  // a control track: anything (and constant for long stretches more often than not)
-                const auto it = cur.find(sl);
-                return it == cur.end() ? f : it->second;
-            };
-            for (int k = 0; k < n; k++) {
-                const DevOp& op = P.ops[(size_t)k];
-                const std::string m = "m" + std::to_string(k);
-                Fact outs[kMaxOut];
-                auto source = [&](const char* b) {  // a value with a history of its own
-                    Fact f;
-                    f.bound = bounds ? b : "";
-                    f.audio = true;
-                    return f;
-                };
-                switch (op.kind) {
-                case OP_OSC: {
-                    const Fact cv = (op.flags & OSC_HAS_CV) ? get(op.in_slot[0]) : Fact{};
-                    cv_fact[(size_t)k] = cv;
-                    const bool phase_ok = !(op.flags & OSC_EXACT) && (!(op.flags & OSC_HAS_CV) || !cv.bound.empty());
-                    for (int p = 0; p < 3; p++) {
-                        outs[p] = source(phase_ok ? (p == 0 ? "1.0f" : "2.0f") : "");
-                        outs[p].oscs = cv.oscs;
-                        outs[p].rings = cv.rings;
-                        outs[p].also = cv.also;
-                        outs[p].oscs.insert(k);
-                    }
-                    break;
-                }
-                case OP_VCF: {
-                    const Fact a = get(op.in_slot[0]);
-                    outs[0] = source("1.0f");                                                 // b4, clamped to [-1, 1]
-                    outs[1] = source("6.0f");                                                 // 3 (b3 - b4)
-                    outs[2] = fact_join(a, source("1.0f"), "(" + a.bound + " + 6.0f)");        // (in - q b4) - b4, q <= 3.8
-                    outs[2].audio = true;
-                    break;
-                }
-                case OP_NOISE: outs[0] = source("1.0f"); break;
-                case OP_ADSR:  // the hull of {0, 1, s_val, r_val, from_a_val} (modules.hip.h, adsr_bound), given sane time constants
-                    outs[0] = source(("adsr_bound(" + m + ", " + m + "_k)").c_str());
-                    if (bounds) outs[0].also.insert("adsr_tame(" + m + ", " + m + "_k)");
-                    break;
-                case OP_NONLIN:
-                case OP_SAMPLE: outs[0] = source(""); break;
-                case OP_GRIDSEQ:
-                case OP_PATSEQ: break;  // stepwise values of any size
-                case OP_MATH: {
-                    const Fact a = (op.flags & MATH_HAS_IN1) ? get(op.in_slot[0]) : get(-1);
-                    Fact b;
-                    if (op.flags & MATH_HAS_IN2)
-                        b = get(op.in_slot[1]);
-                    else
-                        b.bound = "__builtin_fabsf(" + m + "_c)";
-                    const bool mul = ((op.flags >> MATH_OP_SHIFT) & 3u) == SRACK_MATH_MULTIPLY;
-                    outs[0] = fact_join(a, b, "(" + a.bound + (mul ? " * " : " + ") + b.bound + ")");
-                    break;
-                }
-                case OP_VCA: {
-                    if ((op.flags & (VCA_HAS_AUDIO | VCA_HAS_CV)) != (VCA_HAS_AUDIO | VCA_HAS_CV)) {
-                        outs[0] = get(-1);
-                        break;
-                    }
-                    const Fact a = get(op.in_slot[0]), b = get(op.in_slot[1]);
-                    outs[0] = fact_join(a, b, "(" + a.bound + " * " + b.bound + ")");
-                    break;
-                }
-                case OP_MIX: {
-                    Fact acc = get(-1);
-                    for (int j = 0; j < 4; j++) {
-                        if (!(op.flags & (1u << j))) continue;
-                        const Fact x = get(op.in_slot[j]);
-                        acc = fact_join(acc, x, "(" + acc.bound + " + " + x.bound + " * __builtin_fabsf(" + m + "_g[" + std::to_string(j) + "]))");
-                    }
-                    outs[0] = acc;
-                    break;
-                }
-                case OP_DELAY_RD: {
-                    // what the ring holds was written by the matching DELAY_WR — of an op further down the list, usually: its value's own
-                    // bound is what counts (an oscillator's port, a filter's lowpass / bandpass, noise), given that the stored values
-                    // respect it too when the launch starts
-                    Fact f;
-                    f.audio = true;
-                    const bool global = (op.flags & DELAY_RING_GLOBAL) != 0;
-                    if (bounds && (!global) && B <= 16) {
-                        for (int w = 0; w < n; w++) {
-                            const DevOp& wr = P.ops[(size_t)w];
-                            if (wr.kind != OP_DELAY_WR || wr.aux != op.aux || ((wr.flags & DELAY_RING_GLOBAL) != 0) != global) continue;
-                            int pk = -1, pp = -1;
-                            if (!producer_of(wr.in_slot[0], w, pk, pp)) break;
-                            const DevOp& src = P.ops[(size_t)pk];
-                            if (src.kind == OP_OSC && !(src.flags & OSC_EXACT) && pp < 3 && !distrusted.count(pk)) {
-                                f.bound = pp == 0 ? "1.0f" : "2.0f";
-                                f.oscs.insert(pk);
-                                if (src.flags & OSC_HAS_CV) assumed.insert(pk);
-                            } else if (src.kind == OP_VCF && pp < 2) {
-                                f.bound = pp == 0 ? "1.0f" : "6.0f";
-                            } else if (src.kind == OP_NOISE) {
-                                f.bound = "1.0f";
-                            }
-                            break;
-                        }
-                        if (!f.bound.empty()) f.rings.insert(k);
-                    }
-                    rd_fact[(size_t)k] = f;
-                    outs[0] = f;
-                    break;
-                }
-                default: break;
-                }
-                for (int p = 0; p < kMaxOut; p++)
-                    if (op.out_slot[p] >= 0) cur[op.out_slot[p]] = outs[p];
-            }
-            bool changed = false;
-            for (int k : assumed)
-                if (cv_fact[(size_t)k].bound.empty() && !distrusted.count(k)) {
-                    distrusted.insert(k);
-                    changed = true;
-                }
-            if (!changed) break;
-        }
-        // a bound that rests on an oscillator with an unbounded CV of its own does not hold
-        for (int k = 0; k < n; k++) {
-            Fact& f = cv_fact[(size_t)k];
-            for (int o : std::set<int>(f.oscs))
-                if (o != k && (P.ops[(size_t)o].flags & OSC_HAS_CV) && cv_fact[(size_t)o].bound.empty()) f.bound.clear();
-        }
-        for (int k = 0; k < n && bounds; k++)
-            if (P.ops[(size_t)k].kind == OP_OSC && (P.ops[(size_t)k].flags & OSC_HAS_CV) && (P.ops[(size_t)k].flags & OSC_CV_AUDIO_RATE) && !cv_fact[(size_t)k].bound.empty()) {  // (a CV that holds keeps the literal form: the reference's own increment per held value)
-                fm_index[(size_t)k] = (int)fm_ops.size();
-                fm_ops.push_back(k);
-            }
-        if (fm_ops.size() > 6) {  // (the copies of the sample loop multiply)
-            for (int k : fm_ops) fm_index[(size_t)k] = -1;
-            fm_ops.clear();
-        }
-    }
-    // the classes a versioned oscillator may take, by how many of them share the loop's copies: {1, 2, 3} / {1, 3} / {1}
-    int fm_classes() const { return fm_ops.size() <= 2 ? 3 : fm_ops.size() == 3 ? 2 : 1; }
-
-    static bool across_lanes_enabled()  // SRACK_CTL_ACROSS_LANES=0 (tools/): the sample-by-sample units, for A/B runs
-    {
-        static const bool on = [] {
-            const char* e = getenv("SRACK_CTL_ACROSS_LANES");
-            return !(e && e[0] == '0');
-        }();
-        return on;
-    }
-    bool tile_wise(const DevOp& op) const
-    {
-        const uint32_t fl = op.flags;
-        const uint32_t ports = fl & (OSC_OUT_SINE | OSC_OUT_SQUARE | OSC_OUT_SAW);
-        switch (op.kind) {
-        case OP_VCA:
-        case OP_MIX:
-        case OP_MATH:
-        case OP_NONLIN:
-        case OP_OUT: return true;
-        case OP_ADSR: return (fl & ADSR_HAS_GATE) != 0;
-        case OP_OSC:  // constant pitch, no sync, one live port, increment below 1/4 (host-proved)
-            return ports && !(ports & (ports - 1)) && ((fl & OSC_CONST_FAST) || ((fl & OSC_EXACT) && (fl & OSC_CONST_SMALL)));
-        default: return false;
-        }
-    }
-    explicit Gen(const FlatProgram& p, int om, bool ctl = false, const std::string& u = "") : P(p), out_mode(om), is_ctl(ctl), uniq(u)
-    {
-        if (is_ctl && across_lanes_enabled()) {
-            across_lanes = true;
-            for (const DevOp& op : P.ops) across_lanes = across_lanes && tile_wise(op);
-        }
-        if (!is_ctl && (out_mode & 2))
-            for (int k = 0; k < (int)P.ops.size(); k++)
-                if (P.ops[(size_t)k].kind == OP_OUT && P.ops[(size_t)k].in_slot[0] < kTrackSlot) tile_of_out[k] = n_tiles++;
-        // default mode (no tile-wise exact saw borrows a plane's tile): two or more planes share one tile, 32 / P' rows each (wave.hip.h)
-        // (who borrows: gen_osc's two tile-wise exact saws — an exact oscillator whose only live port is the saw, at a constant pitch or with a CV and no sync; any other exact oscillator,
-        // e.g. in a patch the flattener turned exact because a loop runs through a pitch, leaves the tiles alone)
-        bool borrower = false;
-        for (const DevOp& op : P.ops)
-            borrower = borrower || (op.kind == OP_OSC && (op.flags & OSC_EXACT) && (op.flags & (OSC_OUT_SINE | OSC_OUT_SQUARE | OSC_OUT_SAW)) == OSC_OUT_SAW &&
-                                    ((op.flags & OSC_CONST_SMALL) || (op.flags & (OSC_HAS_CV | OSC_HAS_SYNC | OSC_AA)) == (OSC_HAS_CV | OSC_AA)));  // (a superset of gen_osc's two cases)
-        if (n_tiles >= 2 && !borrower && !getenv("SRACK_TILE_PER_PLANE")) {
-            rows_per_plane = n_tiles <= 2 ? 16 : 8;  // (jit_supported: at most four distinct planes)
-            n_tiles = 1;
-        }
-        analyze();
-    }
-    int borrow_tile(int after_op)
-    {
-        if (rows_per_plane > 0) return n_tiles++;  // (the planes share tile 0 row-wise: nothing to lend — cannot happen, the constructor looks for borrowers first)
-        for (auto& kv : tile_of_out)
-            if (kv.first > after_op && !out_tile_lent[kv.first]) {
-                out_tile_lent[kv.first] = true;
-                return kv.second;
-            }
-        return n_tiles++;
-    }
-
-    static std::string hex(uint32_t v)
-    {
-        char b[16];
-        std::snprintf(b, sizeof b, "0x%xu", v);
-        return b;
-    }
-    std::string in(int s)
-    {
-        if (s < 0) return "zero_in";  // an unconnected input: 0.0, opaque to the optimiser (modules.hip.h, zero_f32)
-        if (s >= kTrackSlot) {
-            const int k = s - kTrackSlot;
-            if (std::find(tracks_used.begin(), tracks_used.end(), k) == tracks_used.end()) tracks_used.push_back(k);
-            // A control unit is ONE wave on a latency chain: a scalar load per sample would put ~200 cycles of memory latency on
-            // every step.  Its input tracks are fetched a 32-sample tile ahead, lane j holding sample j, and read with v_readlane.
-            if (is_ctl && across_lanes) return "trk" + std::to_string(k) + "_t";  // lane j holds sample j of the tile
-            if (is_ctl) return "readlane_f32(trk" + std::to_string(k) + "_t, i)";
-            // A voice wave reads the track through the scalar unit (it is wave-uniform), a group of samples per load: the sample
-            // function receives its value as an argument (emit_function_body).
-            return "tk" + std::to_string(k);
-        }
-        auto it = slot.find(s);
-        if (it == slot.end()) {
-            err = "wire slot read before it was written";
-            return "0.0f";
-        }
-        return it->second;
-    }
-    std::string par(int k, int j)
-    {
-        const DevOp& op = P.ops[(size_t)k];
-        if (op.par_row[j] >= 0) return "rowf(" + std::to_string(op.par_row[j]) + ")";
-        return "a.ops[" + std::to_string(k) + "].par_val[" + std::to_string(j) + "]";
-    }
-
-    void gen_osc(int k, const DevOp& op)
-    {
-        const std::string m = "m" + std::to_string(k);
-        const uint32_t fl = op.flags;
-        const uint32_t ports = fl & (OSC_OUT_SINE | OSC_OUT_SQUARE | OSC_OUT_SAW);
-        const int sr = op.state_row;
-        const std::string pos = "make_f64(row(" + std::to_string(sr) + "), row(" + std::to_string(sr + 1) + "))";
-        const std::string delta = op.delta_row >= 0 ? "make_f64(row(" + std::to_string(op.delta_row) + "), row(" + std::to_string(op.delta_row + 1) + "))"
-                                                     : "a.ops[" + std::to_string(k) + "].delta";
-        const int port_index = (fl & OSC_OUT_SAW) ? 2 : (fl & OSC_OUT_SQUARE) ? 1 : 0;
-        const bool one_port = ports && !(ports & (ports - 1));
-        const bool exact = (fl & OSC_EXACT) != 0;
-        if (across_lanes) {  // (tile_wise(): constant pitch, one port) the phase recurrence per sample, the outputs per lane
-            pro << "    COsc " << m << ";\n    cosc_init(" << m << ", " << pos << ", " << delta << ");\n";
-            body << "        const float " << m << "_y = cosc_tile<" << (exact ? "true" : "false") << ">(" << hex(fl & ~(OSC_CONST_FAST | OSC_CONST_SMALL)) << ", " << m << ", n);\n";
-            slot[op.out_slot[port_index]] = m + "_y";
-            epi << "        put(" << sr << ", f64_lo(" << m << ".pos)); put(" << sr + 1 << ", f64_hi(" << m << ".pos)); put(" << sr + 2 << ", 0u);\n";
-            return;
-        }
-        if ((fl & OSC_CONST_FAST) && (fl & OSC_FIXED_PHASE)) {  // ... its saw with the phase in 2^-64 fixed point (host-set: nothing integrates or thresholds the value)
-            const std::string dlo = op.delta_row >= 0 ? "row(" + std::to_string(op.delta_row) + ")" : "(uint32_t)(uint64_t)__double_as_longlong(a.ops[" + std::to_string(k) + "].delta)";
-            const std::string dhi = op.delta_row >= 0 ? "row(" + std::to_string(op.delta_row + 1) + ")" : "(uint32_t)((uint64_t)__double_as_longlong(a.ops[" + std::to_string(k) + "].delta) >> 32)";
-            osc_pos[k] = "0.0";   // (a fixed-point phase is in [0, 1) by construction)
-            osc_delta[k] = "";
-            pro << "    FOsc " << m << ";\n    fosc_init(" << m << ", row(" << sr << "), row(" << sr + 1 << "), " << dlo << ", " << dhi << ");\n";
-            body << "        const float " << m << "_y = fosc_saw(" << m << ");\n";
-            slot[op.out_slot[2]] = m + "_y";
-            epi << "        put(" << sr << ", " << m << ".lo); put(" << sr + 1 << ", " << m << ".hi); put(" << sr + 2 << ", 0u);\n";
-            return;
-        }
-        if (fl & OSC_CONST_FAST) {  // no CV, no sync, one live port, delta < 0.25 everywhere: the carried-phase oscillator
-            osc_pos[k] = m + ".pos";
-            osc_delta[k] = "";  // host-proved: 0 <= delta < 1/4
-            pro << "    COsc " << m << ";\n    cosc_init(" << m << ", " << pos << ", " << delta << ");\n";
-            if (ports == OSC_OUT_SQUARE && !is_ctl && quiet_enabled()) {
-                // a square at a constant pitch is a gate source more often than not: outside its PolyBLEP windows it is one level for a whole group
-                if (halve_groups())
-                    pro << "    COscQuiet " << m << "_q[4];\n#pragma unroll\n    for (int li = 0; li < 4; li++) cosc_quiet_init(" << m << ", " << m << "_q[li], 8 >> li);\n";
-                else
-                    pro << "    COscQuiet " << m << "_q[1];\n    cosc_quiet_init(" << m << ", " << m << "_q[0], 8);\n";
-                group_decl << "        float " << m << "_lv = 0.0f;\n";
-                group_begin << "                " << m << "_lv = cosc_square_level(" << m << ");\n";
-                quiet_lane.push_back("cosc_square_quiet(" + m + ", " + m + "_q[{LI}])");
-                body << "        float " << m << "_y;\n        if constexpr (kQuiet) {\n            " << m << "_y = " << m << "_lv;\n            cosc_quiet_step(" << m
-                     << ");\n        } else {\n            " << m << "_y = cosc_step<" << hex(ports) << ">(" << m << ");\n        }\n";
-                quiet_of[op.out_slot[port_index]] = m + "_lv";
-            } else {
-                body << "        const float " << m << "_y = cosc_step<" << hex(ports) << ">(" << m << ");\n";
-            }
-            slot[op.out_slot[port_index]] = m + "_y";
-            epi << "        put(" << sr << ", f64_lo(" << m << ".pos)); put(" << sr + 1 << ", f64_hi(" << m << ".pos)); put(" << sr + 2 << ", 0u);\n";
-            return;
-        }
-        if (exact && (fl & OSC_CONST_SMALL) && one_port && (ports == OSC_OUT_SQUARE || (ports == OSC_OUT_SAW && is_ctl))) {
-            // exact mode, constant pitch, where PolyBLEP windows are rare (a square is an LFO / clock more often than not; a control unit
-            // is one voice): the reference's formulas only for the samples with a lane inside a window (modules.hip.h, cosc_exact_step)
-            pro << "    COsc " << m << ";\n    cosc_init(" << m << ", " << pos << ", " << delta << ");\n";
-            body << "        const float " << m << "_y = cosc_exact_step<" << hex(ports) << ">(" << m << ");\n";
-            slot[op.out_slot[port_index]] = m + "_y";
-            epi << "        put(" << sr << ", f64_lo(" << m << ".pos)); put(" << sr + 1 << ", f64_hi(" << m << ".pos)); put(" << sr + 2 << ", 0u);\n";
-            return;
-        }
-        pro << "    OscConst " << m << "_k;\n    " << m << "_k.sr = a.ops[" << k << "].sample_rate;\n    " << m << "_k.val = (double)" << par(k, OSC_P_VAL) << ";\n";
-        if (!(fl & OSC_HAS_CV))
-            pro << "    " << m << "_k.delta = " << delta << ";\n    " << m << "_k.inv_dt = inv_dt_f32(" << m << "_k.delta);\n";
-        else
-            pro << "    " << m << "_k.delta = 0.0;\n    " << m << "_k.inv_dt = 0.0f;\n";
-        if (!exact && (fl & (OSC_HAS_CV | OSC_CV_STEPWISE | OSC_HAS_SYNC | OSC_AA | OSC_EXACT_BLEP)) == (OSC_HAS_CV | OSC_CV_STEPWISE | OSC_AA) && one_port) {
-            osc_pos[k] = m + ".o.pos";
-            pro << "    StepOsc " << m << ";\n    steposc_init(" << m << ", " << pos << ");\n";
-            body << "        const float " << m << "_y = steposc_step<" << hex(ports) << ">(" << m << ", " << m << "_k, " << in(op.in_slot[0]) << ");\n";
-            slot[op.out_slot[port_index]] = m + "_y";
-            epi << "        put(" << sr << ", f64_lo(" << m << ".o.pos)); put(" << sr + 1 << ", f64_hi(" << m << ".o.pos)); put(" << sr + 2 << ", 0u);\n";
-            return;
-        }
-        pro << "    OscRegs " << m << ";\n    " << m << ".pos = " << pos << ";\n    " << m << ".sync_last = row(" << sr + 2 << ") != 0;\n";
-        if (exact && !is_ctl && (fl & OSC_CONST_SMALL) && ports == OSC_OUT_SAW) {
-            // Exact mode, constant pitch, saw: a tile at a time (windowless values, then each lane repairs its own PolyBLEP rows with
-            // the reference's f64 division) instead of paying for the division whenever ANY lane of the wave is inside a window.
-            // Its preconditions are checked once per launch; a wave that fails them takes the literal per-sample form.
-            const int tile = borrow_tile(k);
-            pro << "    XSaw " << m << "_x;\n    const bool " << m << "_xs = xsaw_usable(" << m << ".pos, " << m << "_k.delta);\n";
-            pro << "    if (" << m << "_xs) xsaw_init(" << m << "_x, " << m << ".pos, " << m << "_k.delta);\n";
-            pro << "    float* const " << m << "_xt = mix_tile + " << tile << " * kMixTile + lane;\n";
-            tile_begin << "        if (" << m << "_xs) xsaw_tile(" << m << "_x, " << m << "_xt, kMixPitch, n);\n";
-            // the tile's row of sample i, read ahead of the group of samples it belongs to (before the plane that lent the tile overwrites it)
-            sample_args.emplace_back(m + "_xr", m + "_xs ? " + m + "_xt[(i) * kMixPitch] : 0.0f");
-            bounded_if[op.out_slot[2]] = m + "_xs";  // XSaw's preconditions bound the saw by 2
-            fast_conds.emplace_back(m + "_xs", "constexpr bool " + m + "_xs = true;");
-            body << "        float " << m << "_y2;\n        if (" << m << "_xs) {\n            " << m << "_y2 = " << m << "_xr;\n        } else {\n";
-            body << "            float " << m << "_y0 = 0.0f, " << m << "_y1 = 0.0f;\n            " << m << "_y2 = 0.0f;\n";
-            body << "            osc_step(" << hex(fl) << ", " << m << ", " << m << "_k, zero_in, zero_in, " << m << "_y0, " << m << "_y1, " << m << "_y2);\n        }\n";
-            slot[op.out_slot[2]] = m + "_y2";
-            epi << "        if (" << m << "_xs) { " << m << ".pos = " << m << "_x.pos; " << m << ".sync_last = false; }\n";
-            epi << "        put(" << sr << ", f64_lo(" << m << ".pos)); put(" << sr + 1 << ", f64_hi(" << m << ".pos)); put(" << sr + 2 << ", " << m << ".sync_last ? 1u : 0u);\n";
-            return;
-        }
-        std::set<int> cv_tracks;
-        if (exact && !is_ctl && (fl & (OSC_HAS_CV | OSC_HAS_SYNC | OSC_AA)) == (OSC_HAS_CV | OSC_AA) && ports == OSC_OUT_SAW && pure_deps(op.in_slot[0], cv_tracks)) {
-            // Exact mode, saw, a pitch that is a pure function of control tracks (a sequencer's note, transposed per voice): wherever those
-            // tracks hold one value for a whole tile — decided at the tile's first sample, when the CV of that sample is known — the
-            // increment is the one of that CV and the tile is written by the tile-wise saw (XSaw), as for a constant pitch.  Other tiles
-            // (a note change inside, a glide, the tail of a launch) take the literal per-sample form; the phase is common to both.
-            const int tile = borrow_tile(k);
-            const std::string cv = in(op.in_slot[0]);
-            pro << "    XSaw " << m << "_x;\n    bool " << m << "_flat = false;\n    float* const " << m << "_xt = mix_tile + " << tile << " * kMixTile + lane;\n";
-            body << "        const float " << m << "_cv = " << cv << ";\n";
-            body << "        if (i == 0) {\n            " << m << "_flat = n == kMixRows";
-            for (int tk : cv_tracks) body << " && track_flat(trk" << tk << "_v + t0, lane)";
-            body << ";\n            if (" << m << "_flat) {\n";
-            body << "                if (__builtin_amdgcn_ballot_w64(" << m << "_cv != " << m << ".seen_cv) != 0) {\n";
-            body << "                    " << m << ".seen_delta = 440.0 * exp2_libm((double)" << m << "_cv + " << m << "_k.val) / " << m << "_k.sr;  // osc_step's own, exact flavour\n";
-            body << "                    " << m << ".seen_cv = " << m << "_cv;\n                }\n";
-            body << "                " << m << "_flat = xsaw_usable(" << m << ".pos, " << m << ".seen_delta);\n";
-            body << "                if (" << m << "_flat) {\n                    xsaw_init(" << m << "_x, " << m << ".pos, " << m << ".seen_delta);\n";
-            body << "                    xsaw_tile(" << m << "_x, " << m << "_xt, kMixPitch, kMixRows);\n";
-            body << "                    " << m << ".pos = " << m << "_x.pos;\n                    " << m << ".sync_last = false;\n                }\n            }\n        }\n";
-            body << "        float " << m << "_y2;\n        if (" << m << "_flat) {\n            " << m << "_y2 = " << m << "_xt[i * kMixPitch];\n        } else {\n";
-            body << "            float " << m << "_y0 = 0.0f, " << m << "_y1 = 0.0f;\n            " << m << "_y2 = 0.0f;\n";
-            body << "            osc_step(" << hex(fl) << ", " << m << ", " << m << "_k, " << m << "_cv, zero_in, " << m << "_y0, " << m << "_y1, " << m << "_y2);\n        }\n";
-            slot[op.out_slot[2]] = m + "_y2";
-            bounded_if[op.out_slot[2]] = m + "_flat";  // (per tile, not per launch: a filter behind it tests a scalar instead of its input)
-            epi << "        put(" << sr << ", f64_lo(" << m << ".pos)); put(" << sr + 1 << ", f64_hi(" << m << ".pos)); put(" << sr + 2 << ", " << m << ".sync_last ? 1u : 0u);\n";
-            return;
-        }
-        const std::string cv = in(op.in_slot[0]), sync = in(op.in_slot[1]);
-        osc_pos[k] = m + ".pos";
-        osc_delta[k] = (fl & OSC_HAS_CV) ? "" : m + "_k.delta";
-        // a CV that derives from an oscillator, a filter, an envelope ... changes every sample: no point in comparing it with the last one
-        std::string fx = hex(fl);  // (OSC_CV_AUDIO_RATE is the flattener's: a CV that sweeps, flatten.cpp `sweeps`; an envelope's or a sequencer's holds)
-        if (!is_ctl && fm_index[(size_t)k] >= 0) {  // a bounded CV: the flags of the class its wave voted for (analyze)
-            fx = "(" + fx + " | kFm" + std::to_string(fm_index[(size_t)k]) + ")";
-            pro << "    " << m << "_k.scale = (440.0 / " << m << "_k.sr) * exp2(" << m << "_k.val);  // OSC_VAL_FOLDED: the increment is scale * 2^cv\n";
-        }
-        body << "        float " << m << "_y0 = 0.0f, " << m << "_y1 = 0.0f, " << m << "_y2 = 0.0f;\n";
-        body << "        osc_step(" << fx << ", " << m << ", " << m << "_k, " << cv << ", " << sync << ", " << m << "_y0, " << m << "_y1, " << m << "_y2);\n";
-        for (int p = 0; p < 3; p++)
-            if (op.out_slot[p] >= 0) slot[op.out_slot[p]] = m + "_y" + std::to_string(p);
-        epi << "        put(" << sr << ", f64_lo(" << m << ".pos)); put(" << sr + 1 << ", f64_hi(" << m << ".pos)); put(" << sr + 2 << ", " << m << ".sync_last ? 1u : 0u);\n";
-    }
-
-    void gen_vcf(int k, const DevOp& op)
-    {
-        const std::string m = "m" + std::to_string(k);
-        const int s0 = op.state_row;
-        const bool fast = !(P.render_flags & SRACK_RENDER_EXACT_OSC) && !(op.flags & VCF_LITERAL);
-        const char* F = fast ? "true" : "false";
-        pro << "    VcfRegs " << m << ";\n";
-        const char* names[10] = {"f", "p", "q", "b0", "b1", "b2", "b3", "b4", "freq", "res"};
-        for (int j = 0; j < 10; j++) pro << "    " << m << "." << names[j] << " = rowf(" << s0 + j << ");\n";
-        pro << "    const float " << m << "_freq = " << par(k, VCF_P_FREQ) << ", " << m << "_exp = " << par(k, VCF_P_EXP) << ", " << m << "_res = vcf_resonance("
-            << par(k, VCF_P_RES) << ");\n";
-        pro << "    bool " << m << "_fin = " << (fast ? "true" : "vcf_nan_free(" + m + ")") << ";\n";
-        const std::string audio = in(op.in_slot[0]);
-        if (op.flags & VCF_HAS_CV) {  // `res` is a parameter: settled before the first sample, the loop compares the frequency only
-            pro << "    if (a.T > 0) vcf_res_settle(" << m << ", " << m << "_res);\n";
-            body << "        vcf_coeffs_freq<" << F << ">(" << m << ", " << (fast ? "vcf_frequency_med3(" : "vcf_frequency(") << m << "_freq, " << in(op.in_slot[1]) << ", "
-                 << m << "_exp), " << m << "_res);\n";
-        } else  // constant cutoff: the "did (frequency, res) change" check can only fire on the first sample
-            pro << "    if (a.T > 0) vcf_coeffs<" << F << ">(" << m << ", vcf_frequency(" << m << "_freq, 0.0f, " << m << "_exp), " << m << "_res);\n";
-        body << "        float " << m << "_lp, " << m << "_bp, " << m << "_hp;\n";
-        const auto bounded = bounded_in.find(op.in_slot[0]);
-        if (!fast && bounded != bounded_in.end()) fast_conds.emplace_back(m + "_fin", "bool " + m + "_fin = true;");
-        if (!fast && bounded != bounded_in.end())  // no per-sample look at the input's magnitude
-            body << "        vcf_run_bounded(" << m << ", " << m << "_fin, " << bounded->second << ", " << audio << ", " << m << "_lp, " << m << "_bp, " << m << "_hp);\n";
-        else
-            body << "        vcf_run<" << F << ">(" << m << ", " << m << "_fin, " << audio << ", " << m << "_lp, " << m << "_bp, " << m << "_hp);\n";
-        const char* outs[3] = {"_lp", "_bp", "_hp"};
-        for (int p = 0; p < 3; p++)
-            if (op.out_slot[p] >= 0) slot[op.out_slot[p]] = m + outs[p];
-        epi << "       ";
-        for (int j = 0; j < 10; j++) epi << " put(" << s0 + j << ", __float_as_uint(" << m << "." << names[j] << "));";
-        epi << "\n";
-    }
-
-    void gen_adsr(int k, const DevOp& op)
-    {
-        const std::string m = "m" + std::to_string(k);
-        const int sr = op.state_row;
-        pro << "    AdsrRegs " << m << ";\n";
-        pro << "    " << m << ".phase = rowf(" << sr + ADSR_S_PHASE << "); " << m << ".mode = (int)row(" << sr + ADSR_S_MODE << "); " << m << ".r_val = rowf("
-            << sr + ADSR_S_R_VAL << "); " << m << ".from_a_val = rowf(" << sr + ADSR_S_FROM_A << "); " << m << ".gate_last = row(" << sr + ADSR_S_GATE_LAST << ") != 0;\n";
-        pro << "    const AdsrConst " << m << "_k = adsr_consts(" << par(k, ADSR_P_A) << ", " << par(k, ADSR_P_D) << ", " << par(k, ADSR_P_S) << ", " << par(k, ADSR_P_R)
-            << ", " << par(k, ADSR_P_SR) << ");\n";
-        if (op.flags & ADSR_HAS_GATE) {  // the segmented form: adsr.rs's own operations between mode changes (modules.hip.h)
-            pro << "    AdsrSeg " << m << "_g;\n    adsr_seg_enter(" << m << ", " << m << "_k, " << m << "_g);\n";
-            const auto lv = quiet_in.find(op.in_slot[0]);
-            const char* seg_step = "adsr_seg_step";
-            if (across_lanes) {
-                body << "        const float " << m << "_y = adsr_seg_tile(" << m << ", " << m << "_k, " << m << "_g, " << in(op.in_slot[0]) << ", n);\n";
-            } else if (!is_ctl && lv != quiet_in.end()) {
-                // the gate is one level for a whole quiet group: the envelope asks its questions once per group (modules.hip.h, adsr_seg_quiet)
-                group_begin << "                uint64_t " << m << "_qh;\n                const bool " << m << "_ql = adsr_seg_quiet(" << m << ", " << m << "_g, " << lv->second << ", "
-                            << m << "_qh, {LEN});\n";
-                quiet_lane.push_back(m + "_ql");
-                group_end_quiet << "                    " << m << "_g.last = " << m << "_qh;\n";
-                env_of[op.out_slot[0]] = m;
-                body << "        float " << m << "_y;\n        if constexpr (kQuiet) {\n            " << m << "_y = adsr_seg_quiet_step(" << m << ", " << m
-                     << "_g);\n        } else {\n            " << m << "_y = " << seg_step << "(" << m << ", " << m << "_k, " << m << "_g, " << in(op.in_slot[0]) << ");\n        }\n";
-            } else {
-                body << "        const float " << m << "_y = " << seg_step << "(" << m << ", " << m << "_k, " << m << "_g, " << in(op.in_slot[0]) << ");\n";
-            }
-            epi << "        adsr_seg_flush(" << m << ", " << m << "_g);\n";
-        } else {
-            body << "        const float " << m << "_y = adsr_step(" << hex(op.flags) << ", " << m << ", " << m << "_k, 0.0f);\n";
-        }
-        slot[op.out_slot[0]] = m + "_y";
-        epi << "        put(" << sr + ADSR_S_PHASE << ", __float_as_uint(" << m << ".phase)); put(" << sr + ADSR_S_MODE << ", (uint32_t)" << m << ".mode); put("
-            << sr + ADSR_S_R_VAL << ", __float_as_uint(" << m << ".r_val)); put(" << sr + ADSR_S_FROM_A << ", __float_as_uint(" << m << ".from_a_val)); put("
-            << sr + ADSR_S_GATE_LAST << ", " << m << ".gate_last ? 1u : 0u);\n";
-    }
-
-    void gen_simple(int k, const DevOp& op)
-    {
-        const std::string m = "m" + std::to_string(k);
-        switch (op.kind) {
-        case OP_VCA: {
-            pro << "    const bool " << m << "_neg = " << par(k, VCA_P_NEG) << " != 0.0f;\n";
-            const auto env = env_in.find(op.in_slot[1]);
-            if (!is_ctl && env != env_in.end() && (op.flags & (VCA_HAS_AUDIO | VCA_HAS_CV)) == (VCA_HAS_AUDIO | VCA_HAS_CV)) {
-                // the CV is an envelope in its quiet form: `cv > 0.0` has one answer per lane and group (modules.hip.h, adsr_seg_open)
-                const std::string& e = env->second;
-                group_decl << "        bool " << m << "_open = false;\n";
-                group_begin << "                bool " << m << "_dec;\n                " << m << "_open = adsr_seg_open(" << e << ", " << e << "_g, " << m << "_dec) || " << m
-                            << "_neg;\n";
-                quiet_lane.push_back("(" + m + "_dec || " + m + "_neg)");
-                body << "        float " << m << "_y;\n        if constexpr (kQuiet) {\n            " << m << "_y = vca_step_decided(" << m << "_open, " << in(op.in_slot[0]) << ", "
-                     << in(op.in_slot[1]) << ");\n        } else {\n            " << m << "_y = vca_step(" << hex(op.flags) << ", " << m << "_neg, " << in(op.in_slot[0]) << ", "
-                     << in(op.in_slot[1]) << ");\n        }\n";
-            } else {
-                body << "        const float " << m << "_y = " << (!is_ctl && op.in_slot[1] >= kTrackSlot ? "vca_step_uniform(" : "vca_step(") << hex(op.flags) << ", " << m
-                     << "_neg, " << in(op.in_slot[0]) << ", " << in(op.in_slot[1]) << ");\n";
-            }
-            break;
-        }
-        case OP_MIX:
-            pro << "    const float " << m << "_g[4] = {" << par(k, MIX_P_GAIN0) << ", " << par(k, MIX_P_GAIN0 + 1) << ", " << par(k, MIX_P_GAIN0 + 2) << ", "
-                << par(k, MIX_P_GAIN0 + 3) << "};\n";
-            body << "        const float " << m << "_x[4] = {" << in(op.in_slot[0]) << ", " << in(op.in_slot[1]) << ", " << in(op.in_slot[2]) << ", " << in(op.in_slot[3]) << "};\n";
-            body << "        const float " << m << "_y = mixer_step(" << hex(op.flags) << ", " << m << "_x, " << m << "_g);\n";
-            break;
-        case OP_MATH:
-            pro << "    const float " << m << "_c = " << par(k, MATH_P_CONST) << ";\n";
-            body << "        const float " << m << "_y = math_step(" << hex(op.flags) << ", " << in(op.in_slot[0]) << ", " << in(op.in_slot[1]) << ", " << m << "_c);\n";
-            break;
-        case OP_NONLIN:
-            pro << "    const float " << m << "_c = " << par(k, NONLIN_P_CONST) << ";\n";
-            want_lds_tables();
-            body << "        const float " << m << "_y = nonlin_step(" << hex(op.flags) << ", " << in(op.in_slot[0]) << ", " << in(op.in_slot[1]) << ", " << m << "_c, pow_tabs);\n";
-            break;
-        case OP_NOISE:  // stateless: sample n of the voice's stream
-            pro << "    const uint64_t " << m << "_key = noise_voice_key((uint64_t)__double_as_longlong(a.ops[" << k << "].delta), (uint64_t)__double_as_longlong(a.ops[" << k
-                << "].sample_rate) + vc);\n";
-            body << "        const float " << m << "_y = noise_sample(" << m << "_key, a.n0 + t0 + (uint32_t)i);\n";
-            break;
-        default: break;
-        }
-        slot[op.out_slot[0]] = m + "_y";
-        if (op.kind == OP_VCA || op.kind == OP_MIX || op.kind == OP_MATH || op.kind == OP_NONLIN) {
-            std::set<int> deps;
-            bool pure = true;
-            for (int j = 0; j < 4; j++) pure = pure && pure_deps(op.kind == OP_MIX || j < 2 ? op.in_slot[j] : -1, deps);
-            if (pure) pure_of[op.out_slot[0]] = deps;
-        }
-    }
-
-    // A broken feedback edge: the sink reads what the source wrote buffer_size samples ago.
-    //   buffer_size 1        last tick's value: a register (the voice table keeps it between launches);
-    //   buffer_size 2..16    a ring of LDS rows, loaded from / stored to the voice table's state rows like any module state;
-    //   buffer_size >= 32    a ring in HBM ([B][V] f32): the 32 values a tile reads were all written before the tile began, so
-    //                        the reads are issued together at the tile's start and the sample loop is fully unrolled (the
-    //                        prefetch array is indexed by the sample's position in the tile);
-    //   buffer_size 17..31   the same ring read sample by sample (a tile may read what it has just written; a lane's own
-    //                        loads and stores to one address stay in program order).
-    void gen_delay(int k, const DevOp& op)
-    {
-        const int B = P.hdr.buffer_size;
-        const bool global = (op.flags & DELAY_RING_GLOBAL) != 0;
-        const bool prefetch = global && B >= kMixRowsHost;
-        const std::string r = uniq + "ring" + std::to_string(op.aux) + (global ? "g" : "");
-        const std::string m = "m" + std::to_string(k);
-        if (!ring_declared[op.aux * 2 + (global ? 1 : 0)]) {
-            ring_declared[op.aux * 2 + (global ? 1 : 0)] = true;
-            if (!global && B == 1) {
-                ring_check_of[op.aux] = "__builtin_fabsf(" + r + ") <= @";
-                pro << "    float " << r << " = rowf(" << op.aux << ");\n";
-                epi << "        put(" << op.aux << ", __float_as_uint(" << r << "));\n";
-            } else if (!global) {
-                {
-                    std::string c;
-                    for (int j = 0; j < B; j++) c += std::string(j ? " && " : "") + "__builtin_fabsf(" + r + "[" + std::to_string(j) + " * 64 + lane]) <= @";
-                    ring_check_of[op.aux] = "(" + c + ")";
-                }
-                lds_rings << "    __shared__ float " << r << "[" << B << " * 64];\n";
-                pro << "    for (int j = 0; j < " << B << "; j++) " << r << "[j * 64 + lane] = rowf(" << op.aux << " + j);\n";
-                epi << "        for (int j = 0; j < " << B << "; j++) put(" << op.aux << " + j, __float_as_uint(" << r << "[j * 64 + lane]));\n";
-                uses_ring_pos = true;
-            } else {
-                pro << "    float* const " << r << " = a.rings + (size_t)" << op.aux << " * " << B << "u * V;\n";
-                if (prefetch) {
-                    needs_full_unroll = true;
-                    pro << "    uint32_t " << r << "_p0 = (uint32_t)(a.n0 % " << B << "u);\n";
-                    pro << "    auto " << r << "_at = [&](int i) { const uint32_t p = " << r << "_p0 + (uint32_t)i; return p < " << B << "u ? p : p - " << B << "u; };\n";
-                    // the tile's 32 values, fetched a tile ahead when the ring is long enough for the next tile's to be older than this tile too
-                    const bool ahead = B >= 2 * kMixRowsHost;
-                    pro << "    float " << r << "_fed[kMixRows], " << r << "_nxt[kMixRows];\n";
-                    pro << "#pragma unroll\n    for (int i = 0; i < kMixRows; i++) { " << r << "_fed[i] = " << r << "[(size_t)" << r << "_at(i) * V + vc]; " << r << "_nxt[i] = 0.0f; }\n";
-                    if (ahead)
-                        tile_begin << "        if (t0 + kMixRows < a.T) {\n#pragma unroll\n            for (int i = 0; i < kMixRows; i++) " << r << "_nxt[i] = " << r << "[(size_t)" << r
-                                   << "_at(kMixRows + i) * V + vc];\n        }\n";
-                    tile_end << "        " << r << "_p0 = " << r << "_at(n);\n";
-                    if (ahead)
-                        tile_end << "#pragma unroll\n        for (int i = 0; i < kMixRows; i++) " << r << "_fed[i] = " << r << "_nxt[i];\n";
-                    else
-                        tile_end << "        if (t0 + kMixRows < a.T) {\n#pragma unroll\n            for (int i = 0; i < kMixRows; i++) " << r << "_fed[i] = " << r << "[(size_t)" << r
-                                 << "_at(i) * V + vc];\n        }\n";
-                } else {
-                    uses_ring_pos = true;
-                }
-            }
-        }
-        if (op.kind == OP_DELAY_RD && !global && ring_check_of.count(op.aux)) ring_check[k] = ring_check_of[op.aux];
-        if (op.kind == OP_DELAY_RD) {
-            if (!global && B == 1)
-                body << "        const float " << m << "_y = " << r << ";\n";
-            else if (!global)
-                body << "        const float " << m << "_y = " << r << "[ring_pos * 64 + lane];\n";
-            else if (prefetch)
-                body << "        const float " << m << "_y = " << r << "_fed[i];\n";
-            else
-                body << "        const float " << m << "_y = " << r << "[(size_t)ring_pos * V + vc];\n";
-            slot[op.out_slot[0]] = m + "_y";
-        } else {
-            if (!global && B == 1)
-                body << "        " << r << " = " << in(op.in_slot[0]) << ";\n";
-            else if (!global)
-                body << "        " << r << "[ring_pos * 64 + lane] = " << in(op.in_slot[0]) << ";\n";
-            else if (prefetch)
-                body << "        if (active) " << r << "[(size_t)" << r << "_at(i) * V + voice] = " << in(op.in_slot[0]) << ";\n";
-            else
-                body << "        if (active) " << r << "[(size_t)ring_pos * V + voice] = " << in(op.in_slot[0]) << ";\n";
-        }
-    }
-
-    // The tables behind 2^cv (sample player) and log2 (NonLinear, default mode), copied to LDS once per launch: a lane's own index is a
-    // ds_read there and a gather for the vector-memory pipe through the global pointer (modules.hip.h: LdsTables; P4 29.9 -> see NOTES).
-    void want_lds_tables()
-    {
-        if (lds_tables) return;
-        lds_tables = true;
-        lds_rings << "    __shared__ uint64_t " << uniq << "pow_tabs_lds[64];\n";
-        pro << "    " << uniq << "pow_tabs_lds[lane] = lane < 32 ? ((const uint64_t*)kPowfLog2Tab)[lane] : kExp2fTab[lane - 32];\n";
-        pro << "    LdsTables pow_tabs;  // (assigned, not brace-initialised: a constant initialiser may not cast into the LDS address space)\n";
-        pro << "    pow_tabs.log2_tab = (LdsTab*)" << uniq << "pow_tabs_lds;\n    pow_tabs.exp2f_tab = pow_tabs.log2_tab + 32;\n";
-        needs_sync = true;
-    }
-
-    // Sequencers evaluated per voice (a per-voice clock, or everything per voice): the 64 grid cells are wave-shared data in an LDS
-    // array indexed by step; each lane gathers the cell of its own current_step.
-    void gen_seq(int k, const DevOp& op)
-    {
-        const std::string m = "m" + std::to_string(k);
-        const int sr = op.state_row;
-        const bool grid = op.kind == OP_GRIDSEQ;
-        const bool bank = (op.flags & SEQ_BANK) != 0;
-        // SEQ_BANK (a sequence per voice: srack_voices_set_sequences): the length and where the lane's 64 cells start behind the own ones are
-        // per-lane registers read from the voice table, and the cell is gathered from the lane's own cells in seqtab — one load per sample,
-        // 64 lanes in up to 64 sequences.  (Tried: the lane's 64 cells copied once per launch into a step-major LDS tile [64 steps][64 lanes],
-        // 16 KB per sequencer, conflict-free whatever step each lane is on.  At P3's 262 144 voices — four waves per SIMD — two tiles leave
-        // room for three workgroups per CU: 167 ms per step against the gather's 63.7.  Where a tile fits the kernel's LDS share, 65 536
-        // voices, it won 2.3 ms of 32.7 with a clock per voice and tied on a shared clock: not kept.  tools/seq_bank_bench.py, notes/r12.md.)
-        if (!bank) {
-            lds_rings << "    __shared__ uint32_t " << uniq << m << "_cells_lds[64];\n";
-            lds_rings << "    uint32_t* const " << m << "_cells = " << uniq << m << "_cells_lds;\n";
-            pro << "    " << m << "_cells[lane] = a.seqtab[a.ops[" << k << "].aux + lane];\n";
-            needs_sync = true;
-        } else {
-            pro << "    const uint32_t* const " << m << "_cells = a.seqtab + a.ops[" << k << "].aux + row(" << op.par_row[SEQ_P_CELL_OFF] << ");  // this lane's own 64 cells\n";
-        }
-        pro << "    SeqRegs " << m << ";\n    " << m << ".current_step = row(" << sr + SEQ_S_CURRENT << "); " << m << ".step_last = row(" << sr + SEQ_S_STEP_LAST << ") != 0; " << m
-            << ".sync_last = row(" << sr + SEQ_S_SYNC_LAST << ") != 0;\n";
-        if (bank)
-            pro << "    const uint32_t " << m << "_len = row(" << op.par_row[SEQ_P_LEN] << ");  // this lane's sequence\n";
-        else
-            pro << "    const uint32_t " << m << "_len = (uint32_t)a.ops[" << k << "].seq_len;\n";
-        const std::string step = in(op.in_slot[0]), sync = in(op.in_slot[1]);
-        body << "        const float " << m << "_step = " << step << ";\n";
-        body << "        const uint32_t " << m << "_cs = seq_advance(" << m << ", " << m << "_step, " << sync << ", " << m << "_len);\n";
-        body << "        const uint32_t " << m << "_cell = " << m << "_cells[" << m << "_cs];\n";
-        if (grid) {
-            pro << "    float " << m << "_last = rowf(" << sr + GRIDSEQ_S_LAST << ");\n";
-            pro << "    const float " << m << "_inv = 1.0f / " << par(k, GRIDSEQ_P_SPO) << ";  // 1.0 / steps_per_octave as f32 (sequencer.rs:236)\n";
-            body << "        float " << m << "_y0, " << m << "_y1, " << m << "_y2;\n";
-            body << "        gridseq_outputs(" << m << "_cell, " << m << "_cs, " << m << "_step, " << m << "_inv, " << m << "_last, " << m << "_y0, " << m << "_y1, " << m << "_y2);\n";
-            for (int p = 0; p < 3; p++)
-                if (op.out_slot[p] >= 0) slot[op.out_slot[p]] = m + "_y" + std::to_string(p);
-            epi << "        put(" << sr + GRIDSEQ_S_LAST << ", __float_as_uint(" << m << "_last));\n";
-        } else {
-            for (int p = 0; p < 9; p++) {
-                if (op.out_slot[p] < 0) continue;
-                if (p == 8)
-                    body << "        const float " << m << "_y8 = " << m << "_cs == 0u ? 1.0f : 0.0f;\n";
-                else
-                    body << "        const float " << m << "_y" << p << " = patseq_gate(" << m << "_cell, " << p << ", " << m << "_step);\n";
-                slot[op.out_slot[p]] = m + "_y" + std::to_string(p);
-            }
-        }
-        epi << "        put(" << sr + SEQ_S_CURRENT << ", " << m << ".current_step); put(" << sr + SEQ_S_STEP_LAST << ", " << m << ".step_last ? 1u : 0u); put(" << sr + SEQ_S_SYNC_LAST
-            << ", " << m << ".sync_last ? 1u : 0u);\n";
-    }
-
-    // SampleModule (sample.rs:192-240): the position state machine, then one gather from the shared wave per sample.
-    // SMP_BANK (a wave per voice: srack_voices_set_waves): the wave's length, the rate ratio and where the wave starts behind the own wave
-    // are per-lane registers read from the voice table; everything else is the same text.
-    void gen_sample(int k, const DevOp& op)
-    {
-        const std::string m = "m" + std::to_string(k);
-        const int sr = op.state_row;
-        const bool bank = (op.flags & SMP_BANK) != 0;
-        want_lds_tables();
-        pro << "    SmpRegs " << m << ";\n    " << m << ".pos = rowf(" << sr + SMP_S_POS << "); " << m << ".playing = row(" << sr + SMP_S_PLAYING << ") != 0; " << m << ".gate_last = row("
-            << sr + SMP_S_GATE_LAST << ") != 0;\n";
-        pro << "    const float " << m << "_ratio = " << par(k, SMP_P_WAVE_SR) << " / " << par(k, SMP_P_SR) << ";\n";
-        if (bank) {
-            pro << "    const uint32_t " << m << "_n = row(" << op.par_row[SMP_P_WAVE_LEN] << "), " << m << "_base = row(" << op.par_row[SMP_P_WAVE_OFF] << ");  // this lane's wave\n";
-            pro << "    const uint32_t " << m << "_region = (uint32_t)a.ops[" << k << "].seq_len;  // the own wave and the whole bank\n";
-        } else {
-            pro << "    const uint32_t " << m << "_n = (uint32_t)a.ops[" << k << "].seq_len;\n";
-        }
-        // A short wave (a one-shot of up to kSmpLdsWave frames: 8 KB, which keeps eight one-wave workgroups on a CU) is copied to LDS once per
-        // launch: a lane's read of its own position is a ds_read — ~100 cycles, and nothing the frame stores of the samples before it can alias —
-        // where the gather through the global pointer is a trip to L2 per sample that the recurrence around it (the position of sample t + 1 needs
-        // 2^cv of sample t) cannot be scheduled away from at two waves per SIMD (P4, rocprofv3: SQ_WAIT_ANY 47 % of the wave cycles).  Which of the
-        // two a kernel does is part of its source (the wave's length class), like everything else about the program's structure.
-        // ... as long as it does not cost the render its occupancy: with the copy the workgroup must still fit its share of the CU's 160 KB at the
-        // waves per SIMD this render has — 10 KB at four (262 144 voices: sixteen one-wave workgroups per CU in ONE round; the mix tile and the
-        // power tables already take 9.2 KB of it: no copy), 20 KB at two (P4's 131 072: the 8 KB copy fits).  In power-of-two classes from 256
-        // frames.  (tools/patch_survey.py, 262 144 voices, one box: even a 2 KB copy for the fuzzer's 1 ... 400-frame waves put seeds 1 and 8 into a
-        // second round of workgroups — 164 / 168 against 124 / 138 ms.)
-        // With a bank the region that is staged is the own wave and the whole bank (op.seq_len): lanes read it at base + index.  The share is
-        // the KERNEL's: every player's copy counts against it (three players with an 8 KB wave each used to pass the check one by one).
-        int kSmpLdsWave = 256;
-        while (kSmpLdsWave < op.seq_len && kSmpLdsWave < 2048) kSmpLdsWave *= 2;
-        int lds_other = 1024 + ((out_mode & 2) ? 8704 : 0);  // tables, cells; one mix tile
-        for (const DevOp& q : P.ops)
-            if (q.kind == OP_DELAY_RD && !(q.flags & DELAY_RING_GLOBAL)) lds_other += (int)P.hdr.buffer_size * 256;
-        const int lds_share = 160 * 1024 / (4 * std::max(1, std::min(want_waves > 0 ? want_waves : 2, 4))) - lds_other;
-        static const bool lds_ok = [] {  // SRACK_JIT_SMP_LDS=0 (tools/): the gather through the global pointer, for A/B runs
-            const char* e = getenv("SRACK_JIT_SMP_LDS");
-            return !(e && e[0] == '0');
-        }();
-        const bool staged = lds_ok && !is_ctl && op.seq_len > 0 && op.seq_len <= kSmpLdsWave && smp_lds_bytes + 4 * kSmpLdsWave <= lds_share;
-        if (staged) smp_lds_bytes += 4 * kSmpLdsWave;
-        std::string read;  // the expression of the sample at index m_i
-        if (staged && bank) {
-            lds_rings << "    __shared__ uint32_t " << uniq << m << "_bank_lds[" << kSmpLdsWave << "];\n";
-            pro << "    for (uint32_t q = (uint32_t)lane; q < " << m << "_region && q < " << kSmpLdsWave << "u; q += 64u) " << uniq << m << "_bank_lds[q] = (a.seqtab + a.ops[" << k << "].aux)[q];\n";
-            read = uniq + m + "_bank_lds[" + m + "_base + " + m + "_i]";
-            needs_sync = true;
-        } else if (staged) {
-            lds_rings << "    __shared__ uint32_t " << uniq << m << "_wave_lds[" << kSmpLdsWave << "];\n";
-            pro << "    for (uint32_t q = (uint32_t)lane; q < " << m << "_n && q < " << kSmpLdsWave << "u; q += 64u) " << uniq << m << "_wave_lds[q] = (a.seqtab + a.ops[" << k << "].aux)[q];\n";
-            pro << "    const uint32_t* const " << m << "_wave = " << uniq << m << "_wave_lds;\n";
-            read = m + "_wave[" + m + "_i]";
-            needs_sync = true;
-        } else if (bank && smp_window()) {
-            // 64 lanes in 64 different waves: 64 cache lines per sample, and no copy to LDS is possible.  Each lane walks ITS wave nearly
-            // sequentially, so it keeps the aligned group of four dwords around its index and the next one, loaded ahead, in registers
-            // (modules.hip.h, SmpWindow): same memory, same bits, a quarter of the loads — none of them waited for while the lane plays on.
-            // Measured (tools/bank_bench.py, P4 at 131 072 voices, 1024 waves of 48 000 frames, one box, three alternating rounds): 20.36 /
-            // 20.39 / 20.43 ms per step against the plain gather's 22.16 / 22.20 / 22.15 (notes/r11.md).
-            pro << "    SmpWindow " << m << "_win = smp_window_init();\n";
-            pro << "    const uint32_t " << m << "_first = (uint32_t)a.ops[" << k << "].aux + " << m << "_base;  // the lane's wave in seqtab (dwords)\n";
-            read = "smp_window_read(" + m + "_win, a.seqtab, " + m + "_first + " + m + "_i)";
-        } else if (bank) {
-            pro << "    const uint32_t* const " << m << "_wave = a.seqtab + a.ops[" << k << "].aux;  // (bank in global memory, plain gather)\n";
-            read = m + "_wave[" + m + "_base + " + m + "_i]";
-        } else {
-            pro << "    const uint32_t* const " << m << "_wave = a.seqtab + a.ops[" << k << "].aux;\n";
-            read = m + "_wave[" + m + "_i]";
-        }
-        body << "        const uint32_t " << m << "_i = sample_advance(" << hex(op.flags) << ", " << m << ", " << m << "_ratio, " << m << "_n, " << in(op.in_slot[0]) << ", " << in(op.in_slot[1])
-             << ", pow_tabs);\n";
-        body << "        const float " << m << "_y = __uint_as_float(" << m << "_n ? " << read << " : 0u);  // empty wave: `*out = 0.0`\n";
-        slot[op.out_slot[0]] = m + "_y";
-        epi << "        put(" << sr + SMP_S_POS << ", __float_as_uint(" << m << ".pos)); put(" << sr + SMP_S_PLAYING << ", " << m << ".playing ? 1u : 0u); put(" << sr + SMP_S_GATE_LAST << ", "
-            << m << ".gate_last ? 1u : 0u);\n";
-    }
-    static bool smp_window()  // SRACK_JIT_SMP_WINDOW=0 (tools/bank_bench.py): the plain gather from a bank in global memory, for A/B runs
-    {
-        static const bool on = [] {
-            const char* e = getenv("SRACK_JIT_SMP_WINDOW");
-            return !(e && e[0] == '0');
-        }();
-        return on;
-    }
-
-    void gen_out(int k, const DevOp& op)
-    {
-        const std::string e = "em" + std::to_string(k);
-        const int s = op.in_slot[0];
-        if (is_ctl) {
-            // a control unit's plane is a track [T] (one voice): lane j keeps sample j of the tile, one coalesced store per tile
-            pro << "    float " << e << "_keep = 0.0f;\n";
-            pro << "    float* const " << e << "_trk = a.frames + (size_t)" << op.aux << " * a.plane_stride;\n";
-            body << "        " << e << "_keep = lane == i ? " << in(s) << " : " << e << "_keep;\n";
-            tile_end << "        if (lane < n) " << e << "_trk[t0 + (uint32_t)lane] = " << e << "_keep;\n";
-            return;
-        }
-        const bool frames = (out_mode & 1) != 0, mix = (out_mode & 2) != 0;
-        pro << "    Emit " << e << " = make_emit(a, " << op.aux << ", lane);\n";
-        if (s >= kTrackSlot) {  // every voice plays the same thing
-            const int tk = s - kTrackSlot;
-            const std::string v = in(s);
-            body << "        emit_track_put(" << e << ", " << v << ", V, " << (frames ? "true" : "false") << ");\n";
-            tile_end << "        emit_track_flush(" << e << ", (const float*)trk" << tk << "_v + t0, t0, n, V, " << (frames ? "true" : "false") << ", " << (mix ? "true" : "false") << ");\n";
-            return;
-        }
-        const int tile = tile_of_out.count(k) ? tile_of_out[k] : 0;  // (without a mix-down the tile is never touched)
-        n_mix++;
-        if (rows_per_plane > 0 && tile_of_out.count(k)) {
-            const int R = rows_per_plane;
-            body << "        emit_put_rows<KOUT>(" << e << ", mix_tile + " << tile * R << " * kMixPitch, " << in(s) << ", i & " << R - 1 << ", V);\n";
-            tile_end << "        emit_rows_end<KOUT>(" << e << ", n, V);\n";
-            shared_emits.push_back(e);
-            if (tile == (int)tile_of_out.size() - 1) {  // the last plane of the sample: every R samples (and at a ragged tile's end) all the planes' rows leave together
-                pro << "    float* const mix_mp_lane = ";
-                for (size_t j = 0; j < shared_emits.size(); j++) pro << "(lane & 31) / " << R << " == " << j << " ? " << shared_emits[j] << ".mp : ";
-                pro << "nullptr;\n";
-                body << "        if ((KOUT & 2) && ((i & " << R - 1 << ") == " << R - 1 << " || i == n - 1)) emit_rows_flush<" << R << ">(" << shared_emits[0]
-                     << ", mix_tile, mix_mp_lane, t0 + (uint32_t)(i & ~" << R - 1 << "), (i & " << R - 1 << ") + 1);\n";
-            }
-            return;
-        }
-        body << "        emit_put<KOUT>(" << e << ", mix_tile + " << tile << " * kMixTile, " << in(s) << ", i, V);\n";
-        tile_end << "        emit_flush<KOUT>(" << e << ", mix_tile + " << tile << " * kMixTile, t0, n, V);\n";
-    }
-
-    bool gen_ops()
-    {
-        for (int k = 0; k < (int)P.ops.size(); k++) {
-            const DevOp& op = P.ops[(size_t)k];
-            body << "        // op " << k << ": kind " << op.kind << " (module " << op.module << ")\n";
-            // wire slots are recycled: what was known about a slot's previous value ends where this op overwrites it (the op itself
-            // still reads its inputs' facts: pure_in / bounded_in)
-            pure_in = pure_of;
-            bounded_in = bounded_if;
-            quiet_in = quiet_of;
-            env_in = env_of;
-            for (int j = 0; j < (int)(sizeof op.out_slot / sizeof op.out_slot[0]); j++)
-                if (op.out_slot[j] >= 0) {
-                    pure_of.erase(op.out_slot[j]);
-                    bounded_if.erase(op.out_slot[j]);
-                    quiet_of.erase(op.out_slot[j]);
-                    env_of.erase(op.out_slot[j]);
-                }
-            switch (op.kind) {
-            case OP_OSC: gen_osc(k, op); break;
-            case OP_VCF: gen_vcf(k, op); break;
-            case OP_ADSR: gen_adsr(k, op); break;
-            case OP_VCA:
-            case OP_MIX:
-            case OP_MATH:
-            case OP_NONLIN:
-            case OP_NOISE: gen_simple(k, op); break;
-            case OP_DELAY_RD:
-            case OP_DELAY_WR: gen_delay(k, op); break;
-            case OP_OUT: gen_out(k, op); break;
-            case OP_GRIDSEQ:
-            case OP_PATSEQ: gen_seq(k, op); break;
-            case OP_SAMPLE: gen_sample(k, op); break;
-            default: err = "op kind " + std::to_string(op.kind) + " is not covered by the kernel generator"; break;
-            }
-            if (!err.empty()) return false;
-        }
-        return true;
-    }
-
-    // the body of a function whose argument block is `a` (a KernelArgs): everything between its braces
-    void emit_function_body(std::ostream& o)
-    {
-        const DevProgram& H = P.hdr;
-        // how far the sample loop is unrolled: straight-line code lets the scheduler overlap independent recurrences of
-        // neighbouring samples (the oscillator of t+1 beside the filter of t), but the body must stay inside the instruction cache
-        int weight = 0;
-        // (NonLinear: a table-driven power with ocml's powf behind a wave-uniform branch for the special cases — ~300 instructions a sample;
-        // unrolled 32 times P4's loop was 11 000 instructions, 75 KB, more than the instruction cache two CUs share: 94 VALU instructions
-        // took 677 SIMD cycles per wave-sample, and MORE with four waves per SIMD than with two)
-        for (const DevOp& op : P.ops)
-            weight += op.kind == OP_OSC ? ((op.flags & OSC_CONST_FAST) ? 2 : 8)
-                    : op.kind == OP_VCF ? 4 : op.kind == OP_ADSR ? 3 : op.kind == OP_NONLIN ? 20 : (op.kind == OP_SAMPLE && (op.flags & SMP_HAS_CV)) ? 4 : 1;
-        int unroll = needs_full_unroll ? 32 : is_ctl ? 4 : (weight <= 10 ? 32 : (weight <= 24 ? 8 : 4));
-        if (const char* e = getenv("SRACK_JIT_UNROLL"))  // experiment knob (tools/): a cap on the unrolling of voice programs
-            if (!needs_full_unroll && !is_ctl && atoi(e) >= 1) unroll = std::min(unroll, atoi(e));
-        if (!is_ctl) {
-            if (n_tiles > 0)  // one transpose tile per plane that is fed by a wire (+ those only an exact saw oscillator uses)
-                o << "    __shared__ __attribute__((aligned(16))) float mix_tile[" << n_tiles << " * kMixTile];\n";
-            else  // no mix-down, no tile-wise oscillator: never touched
-                o << "    __shared__ __attribute__((aligned(16))) float mix_tile[4];\n";
-            o << "    (void)mix_tile;\n";
-        }
-        o << "    const int lane = threadIdx.x;\n";
-        o << "    const WaveMap wm = wave_map(a, lane);\n";
-        o << "    const uint32_t voice = wm.voice, vc = wm.vc, V = a.V;\n";
-        o << "    const bool active = wm.active;\n";
-        o << "    auto row = [&](int rr) { return a.table[(size_t)rr * V + vc]; };\n";
-        o << "    auto rowf = [&](int rr) { return __uint_as_float(a.table[(size_t)rr * V + vc]); };\n";
-        if (is_ctl) {
-            // (a tick session: the rows nobody rewrites — parameters — travel to the next copy with the state; the fence orders these
-            // stores before the epilogue's stores to the same rows, which another lane issues)
-            o << "    uint32_t* const tout = a.table_out ? a.table_out : a.table;\n";
-            o << "    if (a.table_out) {\n        for (uint32_t r = (uint32_t)lane; r < (uint32_t)a.prog.n_rows; r += 64u) a.table_out[r] = a.table[r];\n"
-                 "        __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"workgroup\");\n    }\n";
-            o << "    auto put = [&](int rr, uint32_t v) { tout[(size_t)rr * V + voice] = v; };\n";
-        } else {
-            o << "    auto put = [&](int rr, uint32_t v) { a.table[(size_t)rr * V + voice] = v; };\n";
-        }
-        o << "    const float zero_in = zero_f32();\n";
-        o << "    (void)voice; (void)active; (void)row; (void)rowf; (void)put; (void)zero_in;\n";
-        o << lds_rings.str();
-        if (uses_ring_pos) o << "    uint32_t ring_pos = (uint32_t)(a.n0 % " << H.buffer_size << "u);  // wave-uniform: scalar arithmetic\n";
-        for (int tk : tracks_used) {
-            // a control track is wave-uniform data written by an earlier launch: read through the scalar unit (constant address space)
-            o << "    const float* const trk" << tk << "_v = a.tracks + (size_t)" << H.track_id[tk] << " * a.t_stride;\n";
-            o << "    CFloat* const trk" << tk << " = (CFloat*)(uintptr_t)trk" << tk << "_v;\n";
-        }
-        o << pro.str();
-        if (needs_sync) o << "    __syncthreads();\n";
-        if (is_ctl)
-            for (int tk : tracks_used) o << "    float trk" << tk << "_nx = trk" << tk << "_v[min((uint32_t)lane, a.T - 1u)];\n";
-        std::ostream& out = o;
-        std::ostringstream loop_text;
-        {
-        std::ostream& o = loop_text;
-        o << "    for (uint32_t t0 = 0; t0 < a.T; t0 += kMixRows) {\n";
-        o << "        const int n = (int)min((uint32_t)kMixRows, a.T - t0);\n";
-        if (is_ctl)
-            for (int tk : tracks_used) {
-                o << "        const float trk" << tk << "_t = trk" << tk << "_nx;\n";
-                o << "        trk" << tk << "_nx = trk" << tk << "_v[min(t0 + (uint32_t)kMixRows + (uint32_t)lane, a.T - 1u)];  // the next tile, in flight while this one runs\n";
-            }
-        o << tile_begin.str();
-        // the values of the input tracks at sample i, as arguments of the sample function
-        std::string track_params, track_direct, track_group_decl, track_group_load, track_group_args;
-        if (!is_ctl)
-            for (int tk : tracks_used) {
-                const std::string t = std::to_string(tk);
-                track_params += ", float tk" + t;
-                track_direct += ", trk" + t + "[t0 + (uint32_t)i]";
-                track_group_decl += "                float tg" + t + "[kGroup];\n";
-                track_group_load += " tg" + t + "[u] = trk" + t + "[t0 + (uint32_t)(i0 + u)];";
-                track_group_args += ", tg" + t + "[u]";
-            }
-        for (const auto& sa : sample_args) {
-            auto at = [&](const std::string& idx) {  // the expression with `i` replaced
-                std::string e = sa.second;
-                const size_t p0 = e.find("(i)");
-                if (p0 != std::string::npos) e.replace(p0, 3, "(" + idx + ")");
-                return e;
-            };
-            track_params += ", float " + sa.first;
-            track_direct += ", " + at("i");
-            track_group_decl += "                float " + sa.first + "_g[kGroup];\n";
-            track_group_load += " " + sa.first + "_g[u] = " + at("i0 + u") + ";";
-            track_group_args += ", " + sa.first + "_g[u]";
-        }
-        const bool quiet = !quiet_lane.empty() && !is_ctl && !across_lanes && !needs_full_unroll;
-        o << group_decl.str();  // (also without quiet groups: the discarded arm of a non-generic lambda's `if constexpr` is still looked up)
-        if (quiet)
-            o << "        auto sample = [&](auto quiet_c, int i" << track_params << ") {\n            constexpr bool kQuiet = decltype(quiet_c)::value != 0u;\n";
-        else
-            o << "        auto sample = [&](int i" << track_params << ") {\n            constexpr bool kQuiet = false;\n            (void)kQuiet;\n";
-        {
-            std::istringstream b(body.str());
-            std::string line;
-            while (std::getline(b, line)) o << "    " << line << "\n";
-            if (uses_ring_pos) o << "            ring_pos = ring_pos + 1u == " << H.buffer_size << "u ? 0u : ring_pos + 1u;\n";
-        }
-        o << "        };\n";
-        if (quiet) {
-            // groups of kQuietGroup samples: the quiet copy of the sample function where no lane can have an event within the group
-            o << "        if (n == kMixRows) {\n            constexpr int kGroup = kQuietGroup;\n#pragma unroll 1\n            for (int i0 = 0; i0 < kMixRows; i0 += kGroup) {\n"
-              << track_group_decl;
-            if (!track_group_load.empty()) o << "#pragma unroll\n                for (int u = 0; u < kGroup; u++) {" << track_group_load << " }\n";
-            // (track values of a group sit in arrays indexed from the group of eight's first sample: a sub-group's sample i is element i & 7)
-            std::string sub_args = track_group_args;
-            for (size_t at = sub_args.find("[u]"); at != std::string::npos; at = sub_args.find("[u]", at)) sub_args.replace(at, 3, "[(i1 + u) & (kGroup - 1)]");
-            std::string one_args = track_group_args;
-            for (size_t at = one_args.find("[u]"); at != std::string::npos; at = one_args.find("[u]", at)) one_args.replace(at, 3, "[i1 & (kGroup - 1)]");
-            // run samples [i1, i1 + kLen) through the event-free copy if no lane can have an event within them; says whether it did
-            o << "                auto quiet_run = [&](auto len_c, int i1) -> bool {\n                    constexpr int kLen = (int)decltype(len_c)::value;\n"
-              << "                    constexpr int kLi = kLen == 8 ? 0 : (kLen == 4 ? 1 : (kLen == 2 ? 2 : 3));\n                    (void)kLi;\n"
-              << indent(subst(group_begin.str(), "kLen", "kLi"), 4) << "                    bool quiet_lane = true;\n";
-            for (const auto& c : quiet_lane) o << "                    quiet_lane = quiet_lane && " << subst(c, "kLen", "kLi") << ";\n";
-            o << "                    if (__builtin_amdgcn_ballot_w64(!quiet_lane) != 0) return false;\n#pragma unroll\n                    for (int u = 0; u < kLen; u++) sample(UC<1u>{}, i1 + u"
-              << sub_args << ");\n" << group_end_quiet.str() << "                    return true;\n                };\n";
-            o << "                if (!quiet_run(UC<8u>{}, i0)) {\n";
-            if (halve_groups()) {
-                o << "#pragma unroll 1\n                    for (int i4 = i0; i4 < i0 + 8; i4 += 4) {\n                        if (quiet_run(UC<4u>{}, i4)) continue;\n"
-                  << "#pragma unroll 1\n                        for (int i2 = i4; i2 < i4 + 4; i2 += 2) {\n                            if (quiet_run(UC<2u>{}, i2)) continue;\n"
-                  << "#pragma unroll 1\n                            for (int i1 = i2; i1 < i2 + 2; i1++) {\n                                if (quiet_run(UC<1u>{}, i1)) continue;\n"
-                  << "                                sample(UC<0u>{}, i1" << one_args << ");\n                            }\n                        }\n                    }\n";
-            } else {
-                o << "#pragma unroll " << nq_unroll() << "\n                    for (int u = 0; u < kGroup; u++) sample(UC<0u>{}, i0 + u" << track_group_args << ");\n";
-            }
-            o << "                }\n            }\n        } else {\n            for (int i = 0; i < n; i++) sample(UC<0u>{}, i" << track_direct << ");\n        }\n";
-        } else if (across_lanes) {  // every statement of the body is a whole tile: lane j computes sample j
-            o << "        sample(lane);\n";
-        } else if (needs_full_unroll) {
-            o << "#pragma unroll\n        for (int i = 0; i < kMixRows; i++)\n            if (i < n) sample(i" << track_direct << ");\n";
-        } else if (track_params.empty()) {
-            o << "        if (n == kMixRows) {\n#pragma unroll " << unroll << "\n            for (int i = 0; i < kMixRows; i++) sample(i);\n        } else {\n"
-              << "            for (int i = 0; i < n; i++) sample(i);\n        }\n";
-        } else {
-            // Track values are fetched a group of samples at a time, ahead of the group's arithmetic (adjacent scalar loads merge into
-            // s_load_dwordx4/x8): a load per sample, each behind the branches of the sample before it, would be waited for every time.
-            const int group = std::min(unroll, 8);
-            o << "        if (n == kMixRows) {\n            constexpr int kGroup = " << group << ";\n#pragma unroll " << unroll / group
-              << "\n            for (int i0 = 0; i0 < kMixRows; i0 += kGroup) {\n" << track_group_decl
-              << "#pragma unroll\n                for (int u = 0; u < kGroup; u++) {" << track_group_load << " }\n"
-              << "#pragma unroll\n                for (int u = 0; u < kGroup; u++) sample(i0 + u" << track_group_args << ");\n            }\n        } else {\n"
-              << "            for (int i = 0; i < n; i++) sample(i" << track_direct << ");\n        }\n";
-        }
-        o << tile_end.str();
-        o << "    }\n";
-        }
-        std::ostringstream loops;  // the sample loop, in as many copies as there are launch-uniform conditions to version it on
-        if (fast_conds.empty() || is_ctl) {
-            loops << loop_text.str();
-        } else {
-            loops << "    if (";
-            for (size_t c = 0; c < fast_conds.size(); c++) loops << (c ? " && " : "") << fast_conds[c].first;
-            loops << ") {  // the common case: these hold for the whole launch and are constants inside this copy of the loop\n";
-            for (const auto& fc : fast_conds) loops << "    " << fc.second << "\n";
-            loops << loop_text.str() << "    } else {\n" << loop_text.str() << "    }\n";
-        }
-        if (fm_ops.empty() || is_ctl) {
-            out << loops.str();
-        } else {
-            // Versioned oscillators (analyze): the wave's vote, once per launch, then the copy of the loop compiled for its classes.
-            const int nf = (int)fm_ops.size(), n_cls = fm_classes();
-            std::set<int> oscs, rings;
-            std::set<std::string> also;
-            out << "    // what this wave can prove about its oscillators' pitch CVs for the whole launch (every lane votes; NaNs vote no)\n";
-            for (int j = 0; j < nf; j++) {
-                const int k = fm_ops[(size_t)j];
-                const Fact& f = cv_fact[(size_t)k];
-                out << "    const float fm_b" << j << " = " << f.bound << ";  // |cv| of op " << k << "\n";
-                oscs.insert(f.oscs.begin(), f.oscs.end());
-                oscs.insert(k);
-                rings.insert(f.rings.begin(), f.rings.end());
-                also.insert(f.also.begin(), f.also.end());
-            }
-            out << "    bool fm_lane = true;\n";
-            for (const auto& c : also) out << "    fm_lane = fm_lane && " << c << ";\n";
-            for (int j = 0; j < nf; j++) {  // the exponent val + cv stays clear of 2^x's overflow, 440 / sr is finite
-                const std::string m = "m" + std::to_string(fm_ops[(size_t)j]);
-                out << "    fm_lane = fm_lane && (double)fm_b" << j << " + __builtin_fabs(" << m << "_k.val) < 1000.0 && " << m << "_k.sr >= 1.0 && osc_below_rate(fm_b" << j << ", " << m
-                    << "_k.val, " << m << "_k.sr);\n";
-            }
-            for (int k : oscs) {  // phases in [0, 1) now; increments finite and >= 0 keep them there
-                const auto pe = osc_pos.find(k);
-                if (pe == osc_pos.end()) {
-                    out << "    fm_lane = false;  // (op " << k << ": an oscillator form without a phase to look at)\n";
-                    continue;
-                }
-                out << "    fm_lane = fm_lane && " << pe->second << " >= 0.0 && " << pe->second << " < 1.0;\n";
-                const auto de = osc_delta.find(k);
-                if (de != osc_delta.end() && !de->second.empty()) out << "    fm_lane = fm_lane && " << de->second << " >= 0.0 && " << de->second << " < 1.0e300;\n";
-            }
-            for (int rd : rings) {  // what a delayed edge hands over first is the host's (a rack file's saved buffer), not the source's
-                const auto rc = ring_check.find(rd);
-                if (rc == ring_check.end()) {
-                    out << "    fm_lane = false;\n";
-                    continue;
-                }
-                std::string c = rc->second;
-                for (size_t at; (at = c.find('@')) != std::string::npos;) c.replace(at, 1, rd_fact[(size_t)rd].bound);
-                out << "    fm_lane = fm_lane && " << c << ";\n";
-            }
-            out << "    const bool fm_ok = __builtin_amdgcn_ballot_w64(!fm_lane) == 0;\n";
-            for (int j = 0; j < nf; j++) {
-                // fm_gain_class: 2 = |cv| <= 1/2, 1 = |cv| <= 2, 0 = neither  ->  class 3 / 2 / 1 (with the classes this many oscillators share)
-                out << "    const int fm_g" << j << " = fm_gain_class(fm_b" << j << ");\n";
-                out << "    const int fm_k" << j << " = ";
-                if (n_cls == 3)
-                    out << "fm_g" << j << " + 1;\n";
-                else if (n_cls == 2)
-                    out << "fm_g" << j << " == 2 ? 3 : 1;\n";
-                else
-                    out << "1;\n    (void)fm_g" << j << ";\n";
-            }
-            out << "    auto fm_run = [&](";
-            for (int j = 0; j < nf; j++) out << (j ? ", " : "") << "auto fm_c" << j;
-            out << ") {\n";
-            for (int j = 0; j < nf; j++) out << "    constexpr uint32_t kFm" << j << " = fm_class_flags(decltype(fm_c" << j << ")::value);\n";
-            out << loops.str() << "    };\n";
-            const int allowed3[3] = {1, 2, 3}, allowed2[2] = {1, 3}, allowed1[1] = {1};
-            const int* allowed = n_cls == 3 ? allowed3 : n_cls == 2 ? allowed2 : allowed1;
-            out << "    if (!fm_ok) {\n        fm_run(";
-            for (int j = 0; j < nf; j++) out << (j ? ", " : "") << "UC<0u>{}";
-            out << ");\n    }";
-            std::vector<int> pick((size_t)nf, 0);
-            for (;;) {
-                out << " else if (";
-                for (int j = 0; j < nf; j++) out << (j ? " && " : "") << "fm_k" << j << " == " << allowed[pick[(size_t)j]];
-                out << ") {\n        fm_run(";
-                for (int j = 0; j < nf; j++) out << (j ? ", " : "") << "UC<" << allowed[pick[(size_t)j]] << "u>{}";
-                out << ");\n    }";
-                int j = 0;
-                while (j < nf && ++pick[(size_t)j] == n_cls) pick[(size_t)j++] = 0;
-                if (j == nf) break;
-            }
-            out << "\n";
-        }
-        o << "    if (active) {\n" << epi.str() << "    }\n";
-    }
-};
-
-void emit_preamble(std::ostream& o, int out_mode, bool libm_tab_lds = false)
-{
-    // (nothing here may depend on more than the program's structure: the text is the cache key.  The flattener's description of the
-    // program — it mentions the interpreter's tile length, which moves with the voice count — is added for human readers only,
-    // by srack_render_kernel_source.)
-    o << "// generated by s-rack_amd/csrc/jit.cpp\n";
-    o << "#define SRK_OPAQUE_ZERO 1\n";
-    if (libm_tab_lds) o << "#define SRK_LIBM_TAB_LDS 1  // pow's table in LDS: an exact oscillator's pitch moves (modules.hip.h)\n";
-    if (const char* e = getenv("SRACK_JIT_QUIET_GROUP"))  // experiment knob (tools/): 4, 8 or 16 samples per quiet group
-        if (atoi(e) == 4 || atoi(e) == 16) o << "#define SRK_QUIET_GROUP " << atoi(e) << "\n";
-    o << "#include \"wave.hip.h\"\n";
-    o << "using namespace srack;\nusing namespace srack::dev;\n";
-    o << "typedef const __attribute__((address_space(4))) float CFloat;\n";
-    o << "#define KOUT " << out_mode << "\n";
-}
-
-// ---- hiprtc, resolved at run time -----------------------------------------------------------------------------------------
-struct Rtc {
-    using prog_t = void*;
-    int (*create)(prog_t*, const char*, const char*, int, const char* const*, const char* const*) = nullptr;
-    int (*compile)(prog_t, int, const char* const*) = nullptr;
-    int (*log_size)(prog_t, size_t*) = nullptr;
-    int (*log)(prog_t, char*) = nullptr;
-    int (*code_size)(prog_t, size_t*) = nullptr;
-    int (*code)(prog_t, char*) = nullptr;
-    int (*destroy)(prog_t*) = nullptr;
-    const char* (*errstr)(int) = nullptr;
-    int (*version_fn)(int*, int*) = nullptr;
-    std::string why, version;
-    bool ok = false;
-};
-
-const Rtc& rtc()
-{
-    static Rtc r;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        // the hiprtc that belongs to the HIP runtime this process already runs on (a host may ship its own: torch does).  A runtime-only
-        // ROCm install has no unversioned libhiprtc.so: the versioned sonames are tried too, next to libamdhip64 first.
-        std::vector<std::string> dirs;
-        Dl_info info;
-        if (dladdr((void*)&hipModuleLoadData, &info) && info.dli_fname) {
-            std::string dir(info.dli_fname);
-            const size_t slash = dir.rfind('/');
-            if (slash != std::string::npos) dirs.push_back(dir.substr(0, slash + 1));
-        }
-        dirs.push_back("");  // the default search path
-        dirs.push_back("/opt/rocm/lib/");
-        std::vector<std::string> candidates;
-        for (const auto& d : dirs) {
-            candidates.push_back(d + "libhiprtc.so");
-            for (int v = 9; v >= 5; v--) candidates.push_back(d + "libhiprtc.so." + std::to_string(v));
-            if (!d.empty())  // ... and whatever else that directory calls it
-                if (DIR* dd = opendir(d.c_str())) {
-                    while (dirent* e = readdir(dd))
-                        if (std::strncmp(e->d_name, "libhiprtc.so.", 13) == 0) candidates.push_back(d + e->d_name);
-                    closedir(dd);
-                }
-        }
-        void* lib = nullptr;
-        for (const auto& c : candidates) {
-            lib = dlopen(c.c_str(), RTLD_NOW | RTLD_LOCAL);
-            if (lib) break;
-        }
-        if (!lib) {
-            const char* e = dlerror();
-            r.why = std::string("cannot load libhiprtc (tried libhiprtc.so and its versioned names next to libamdhip64, on the search path and in /opt/rocm/lib): ") + (e ? e : "unknown error");
-            return;
-        }
-        auto sym = [&](const char* n) { return dlsym(lib, n); };
-        r.create = (decltype(r.create))sym("hiprtcCreateProgram");
-        r.compile = (decltype(r.compile))sym("hiprtcCompileProgram");
-        r.log_size = (decltype(r.log_size))sym("hiprtcGetProgramLogSize");
-        r.log = (decltype(r.log))sym("hiprtcGetProgramLog");
-        r.code_size = (decltype(r.code_size))sym("hiprtcGetCodeSize");
-        r.code = (decltype(r.code))sym("hiprtcGetCode");
-        r.destroy = (decltype(r.destroy))sym("hiprtcDestroyProgram");
-        r.errstr = (decltype(r.errstr))sym("hiprtcGetErrorString");
-        r.version_fn = (decltype(r.version_fn))sym("hiprtcVersion");
-        int major = 0, minor = 0;
-        if (r.version_fn && r.version_fn(&major, &minor) == 0) r.version = std::to_string(major) + "." + std::to_string(minor);
-        int rt = 0;
-        if (hipRuntimeGetVersion(&rt) == hipSuccess) r.version += "/" + std::to_string(rt);  // (hiprtcVersion is coarse: the runtime's build number tells patch releases apart)
-        r.ok = r.create && r.compile && r.log_size && r.log && r.code_size && r.code && r.destroy;
-        if (!r.ok) r.why = "libhiprtc lacks the hiprtc* entry points";
-    });
-    return r;
-}
-
-std::string plain_arch(std::string arch)  // "gfx950:sramecc+:xnack-" -> "gfx950": what the library itself is built for; loads on every configuration
-{
-    const size_t colon = arch.find(':');
-    if (colon != std::string::npos) arch.resize(colon);
-    return arch;
-}
-
-std::string device_arch()
-{
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.gcnArchName[0]) return plain_arch(prop.gcnArchName);
-    return "gfx950";  // no device in this process (a build or test host): the library's one target
-}
-
-// ---- the kernel cache: memory (bounded, LRU) over disk (persistent) over hiprtc ------------------------------------------------------
-// A kernel is a pure function of (architecture, hiprtc version, the device headers this library embeds, the generated source), and the
-// source depends on the program's STRUCTURE only.  Compiling takes 0.3 s (a few ops) to 2 s (an FM pair's ten loop copies):
-//   * memory: code objects and loaded modules of the structures this process used last, each bounded (SRACK_KERNEL_CACHE_MAX, default 64)
-//     with least-recently-used eviction; a module is unloaded when the cache AND every patch that renders with it have let go;
-//   * disk: code objects under a caller-settable directory (srack_kernel_cache_set_dir / SRACK_KERNEL_CACHE_DIR; default: a
-//     `.srack_kernel_cache` next to this library if that is writable, else $XDG_CACHE_HOME or ~/.cache/srack_hip), so the second start of
-//     a host — and every other rank of a job — finds them: ranks that start together serialise on a per-kernel file lock, one compiles,
-//     the others read.  Bounded by size (256 MB, oldest files go first).  "off" / "0" / an unusable directory: memory only.
-//   * compilation runs OUTSIDE the process-wide lock (one in-flight slot per key: a second thread asking for the same kernel waits for
-//     the first; threads asking for others are not held up).
-struct CodeObject {
-    std::vector<char> code;
-};
-using CodePtr = std::shared_ptr<const CodeObject>;
-
-struct Fetched {  // one trip through the cache
-    int rc = SRACK_OK;
-    std::string err;
-    CodePtr code;
-    double compile_ms = 0.0;
-    int how = 0;  // 0 memory, 1 disk, 2 compiled
-};
-
-std::mutex g_mutex;
-template <class V>
-struct Lru {  // key -> value, least recently used first
-    std::list<std::pair<std::string, V>> order;
-    std::map<std::string, typename std::list<std::pair<std::string, V>>::iterator> index;
-    V* find(const std::string& k)
-    {
-        auto it = index.find(k);
-        if (it == index.end()) return nullptr;
-        order.splice(order.end(), order, it->second);
-        return &it->second->second;
-    }
-    uint64_t put(const std::string& k, V v, size_t bound)  // -> entries evicted
-    {
-        uint64_t evicted = 0;
-        if (V* have = find(k)) {
-            *have = std::move(v);
-            return 0;
-        }
-        order.emplace_back(k, std::move(v));
-        index[k] = std::prev(order.end());
-        while (order.size() > bound) {
-            index.erase(order.front().first);
-            order.pop_front();
-            evicted++;
-        }
-        return evicted;
-    }
-};
-// (Heap objects that are never destroyed: ~JitKernel unloads its module, and a static's destructor would run at process exit AFTER the
-// HIP runtime's own teardown — hipModuleUnload into a runtime that is gone, in a host that dlopen'ed the library.  Modules are unloaded
-// on eviction and when a patch lets go of them, while the runtime is alive; what is resident at exit is the process's to reclaim.)
-Lru<CodePtr>& g_code = *new Lru<CodePtr>;                                                       // key -> code object
-Lru<std::shared_ptr<const JitKernel>>& g_kernels = *new Lru<std::shared_ptr<const JitKernel>>;  // "<device>:" + key -> loaded module + function
-std::map<std::string, std::shared_future<Fetched>> g_inflight;
-JitCacheStats g_stats;
-std::string g_dir;       // the disk cache's directory as set through the API ("" = not set)
-bool g_dir_set = false;
-
-size_t memory_bound()
-{
-    static const size_t n = [] {
-        const char* e = getenv("SRACK_KERNEL_CACHE_MAX");
-        const long v = e && *e ? strtol(e, nullptr, 10) : 64;
-        return (size_t)std::min(std::max(v, 1L), 4096L);
-    }();
-    return n;
-}
-
-// 128 bits of FNV-1a (two lanes with different offsets): a name for a source text, not a defence against an adversary
-std::string digest(const std::string& a, const std::string& b, const std::string& c, const std::string& d)
-{
-    uint64_t h0 = 0xcbf29ce484222325ull, h1 = 0x84222325cbf29ce4ull;
-    auto feed = [&](const std::string& s) {
-        for (unsigned char ch : s) {
-            h0 = (h0 ^ ch) * 0x100000001b3ull;
-            h1 = (h1 ^ (ch + 0x9e)) * 0x100000001b3ull;
-            h1 ^= h1 >> 29;
-        }
-        h0 = (h0 ^ 0xff) * 0x100000001b3ull;  // a separator between the parts
-        h1 = (h1 ^ 0x01) * 0x100000001b3ull;
-    };
-    feed(a);
-    feed(b);
-    feed(c);
-    feed(d);
-    char buf[40];
-    std::snprintf(buf, sizeof buf, "%016llx%016llx", (unsigned long long)h0, (unsigned long long)h1);
-    return buf;
-}
-
-const std::string& headers_digest()  // the embedded device headers are part of what is compiled
-{
-    static const std::string h = [] {
-        std::string all;
-        for (int i = 0; i < kJitHeaderCount; i++) {
-            all += kJitHeaderNames[i];
-            all += '\n';
-            all += kJitHeaderBodies[i];
-        }
-        return digest(all, "", "", "");
-    }();
-    return h;
-}
-
-// A cached file is loaded as GPU code after nothing but a self-checksum: the directory must be this user's own and closed to others
-// (created 0700; an existing one that someone else owns, or that group / others may write to, is not used).
-bool usable_dir(const std::string& dir)
-{
-    if (dir.empty()) return false;
-    std::string partial;
-    for (size_t i = 0; i <= dir.size(); i++)  // mkdir -p
-        if (i == dir.size() || (dir[i] == '/' && i > 0)) {
-            partial = dir.substr(0, i);
-            if (mkdir(partial.c_str(), i == dir.size() ? 0700 : 0755) != 0 && errno != EEXIST) return false;
-        }
-    struct stat st;
-    if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) return false;
-    if (st.st_uid != geteuid() || (st.st_mode & (S_IWGRP | S_IWOTH))) return false;
-    return access(dir.c_str(), W_OK | X_OK) == 0;
-}
-
-// "" = no disk cache.  (Called with g_mutex held.)
-std::string disk_dir()
-{
-    static std::string resolved;
-    static bool done = false;
-    if (g_dir_set) return (g_dir == "off" || g_dir == "0" || !usable_dir(g_dir)) ? std::string() : g_dir;
-    if (done) return resolved;
-    done = true;
-    const char* e = getenv("SRACK_KERNEL_CACHE_DIR");
-    if (e && *e) {
-        const std::string v(e);
-        resolved = (v == "off" || v == "0" || !usable_dir(v)) ? std::string() : v;
-        return resolved;
-    }
-    std::vector<std::string> candidates;
-    Dl_info info;
-    if (dladdr((void*)&headers_digest, &info) && info.dli_fname) {  // next to this library (an in-tree build: the cache travels with it)
-        std::string dir(info.dli_fname);
-        const size_t slash = dir.rfind('/');
-        if (slash != std::string::npos) candidates.push_back(dir.substr(0, slash + 1) + ".srack_kernel_cache");
-    }
-    const char* xdg = getenv("XDG_CACHE_HOME");
-    const char* home = getenv("HOME");
-    if (xdg && *xdg) candidates.push_back(std::string(xdg) + "/srack_hip");
-    if (home && *home) candidates.push_back(std::string(home) + "/.cache/srack_hip");
-    for (const auto& c : candidates)
-        if (usable_dir(c)) {
-            resolved = c;
-            break;
-        }
-    return resolved;
-}
-
-constexpr char kFileMagic[8] = {'S', 'R', 'K', 'C', 'O', 'B', 'J', '1'};
-
-CodePtr disk_read(const std::string& path)
-{
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return nullptr;
-    struct stat fst;
-    if (fstat(fileno(f), &fst) != 0 || fst.st_uid != geteuid() || !S_ISREG(fst.st_mode)) {  // somebody else's file: not ours to load
-        std::fclose(f);
-        return nullptr;
-    }
-    auto obj = std::make_shared<CodeObject>();
-    char magic[8];
-    uint64_t n = 0, sum = 0;
-    bool ok = std::fread(magic, 1, 8, f) == 8 && std::memcmp(magic, kFileMagic, 8) == 0 && std::fread(&n, 8, 1, f) == 1 && std::fread(&sum, 8, 1, f) == 1 &&
-              n > 0 && n < (1ull << 30);
-    if (ok) {
-        obj->code.resize((size_t)n);
-        ok = std::fread(obj->code.data(), 1, (size_t)n, f) == (size_t)n;
-    }
-    std::fclose(f);
-    if (ok) {
-        uint64_t h = 0xcbf29ce484222325ull;
-        for (char ch : obj->code) h = (h ^ (unsigned char)ch) * 0x100000001b3ull;
-        ok = h == sum;
-    }
-    if (!ok) {  // truncated or damaged: as if it were not there (it will be rewritten)
-        (void)unlink(path.c_str());
-        return nullptr;
-    }
-    (void)utimes(path.c_str(), nullptr);  // recently used
-    return obj;
-}
-
-void disk_trim(const std::string& dir, uint64_t keep_bytes)
-{
-    DIR* d = opendir(dir.c_str());
-    if (!d) return;
-    std::vector<std::pair<time_t, std::pair<std::string, uint64_t>>> files;
-    uint64_t total = 0;
-    while (dirent* e = readdir(d)) {
-        const std::string name(e->d_name);
-        if (name.size() < 6 || name.compare(name.size() - 6, 6, ".hsaco") != 0) continue;
-        struct stat st;
-        if (stat((dir + "/" + name).c_str(), &st) != 0) continue;
-        files.push_back({st.st_mtime, {name, (uint64_t)st.st_size}});
-        total += (uint64_t)st.st_size;
-    }
-    closedir(d);
-    std::sort(files.begin(), files.end());
-    for (size_t i = 0; i < files.size() && total > keep_bytes; i++) {
-        (void)unlink((dir + "/" + files[i].second.first).c_str());
-        total -= files[i].second.second;
-    }
-}
-
-void disk_write(const std::string& dir, const std::string& path, const CodeObject& obj)
-{
-    const std::string tmp = path + ".tmp." + std::to_string((long)getpid());
-    FILE* f = std::fopen(tmp.c_str(), "wb");
-    if (!f) return;
-    uint64_t n = obj.code.size(), h = 0xcbf29ce484222325ull;
-    for (char ch : obj.code) h = (h ^ (unsigned char)ch) * 0x100000001b3ull;
-    const bool ok = std::fwrite(kFileMagic, 1, 8, f) == 8 && std::fwrite(&n, 8, 1, f) == 1 && std::fwrite(&h, 8, 1, f) == 1 &&
-                    std::fwrite(obj.code.data(), 1, obj.code.size(), f) == obj.code.size();
-    if (std::fclose(f) != 0 || !ok || rename(tmp.c_str(), path.c_str()) != 0) {
-        (void)unlink(tmp.c_str());
-        return;
-    }
-    disk_trim(dir, 256ull << 20);
-}
-
-// Further compiler options, part of a kernel's identity (cache_key): the library's own (kJitBackendOptions) and, for experiments
-// (tools/), SRACK_JIT_OPTS — space-separated, e.g. "-mllvm -amdgpu-sched-strategy=max-ilp".
-const std::vector<std::string>& extra_options()
-{
-    static const std::vector<std::string> v = [] {
-        std::vector<std::string> out;
-        std::string all;
-        if (const char* e = getenv("SRACK_JIT_OPTS")) all = e;
-        std::istringstream in(all);
-        for (std::string w; in >> w;) out.push_back(w);
-        return out;
-    }();
-    return v;
-}
-std::string extra_options_text()
-{
-    std::string t;
-    for (const auto& e : extra_options()) t += e + " ";
-    return t;
-}
-
-Fetched hiprtc_compile(const std::string& arch, const std::string& src)
-{
-    Fetched r;
-    const Rtc& R = rtc();
-    if (!R.ok) {
-        r.rc = SRACK_ERR_UNSUPPORTED;
-        r.err = "specialise: " + R.why;
-        return r;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    Rtc::prog_t prog = nullptr;
-    int rc = R.create(&prog, src.c_str(), "srk_voice.hip", kJitHeaderCount, kJitHeaderBodies, kJitHeaderNames);
-    if (rc != 0) {
-        r.rc = SRACK_ERR_DEVICE;
-        r.err = std::string("hiprtcCreateProgram: ") + (R.errstr ? R.errstr(rc) : "error");
-        return r;
-    }
-    const std::string arch_opt = "--offload-arch=" + arch;
-    // the flags the library itself is built with (Makefile): no FMA contraction, no fast-math — the f32 modules must round like the reference
-    std::vector<const char*> opts = {arch_opt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math"};
-    const std::vector<std::string>& extra = extra_options();
-    for (const auto& e : extra) opts.push_back(e.c_str());
-    rc = R.compile(prog, (int)opts.size(), opts.data());
-    std::string log;
-    size_t n = 0;
-    if (R.log_size(prog, &n) == 0 && n > 1) {
-        log.resize(n);
-        R.log(prog, &log[0]);
-    }
-    if (rc != 0) {
-        r.rc = SRACK_ERR_DEVICE;
-        r.err = std::string("hiprtcCompileProgram: ") + (R.errstr ? R.errstr(rc) : "error") + "\n" + log.substr(0, 4000);
-        R.destroy(&prog);
-        return r;
-    }
-    if (R.code_size(prog, &n) != 0 || n == 0) {
-        r.rc = SRACK_ERR_DEVICE;
-        r.err = "hiprtcGetCodeSize failed";
-        R.destroy(&prog);
-        return r;
-    }
-    auto obj = std::make_shared<CodeObject>();
-    obj->code.resize(n);
-    R.code(prog, obj->code.data());
-    R.destroy(&prog);
-    r.code = obj;
-    r.how = 2;
-    r.compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return r;
-}
-
-// disk, then hiprtc; ranks that start together serialise on the kernel's lock file so that one of them compiles
-Fetched fetch_slow(const std::string& dir, const std::string& key, const std::string& arch, const std::string& src)
-{
-    Fetched r;
-    const std::string path = dir.empty() ? std::string() : dir + "/" + key + ".hsaco";
-    if (!path.empty() && (r.code = disk_read(path))) {
-        r.how = 1;
-        return r;
-    }
-    int lock_fd = -1;
-    const std::string lock_path = path.empty() ? std::string() : dir + "/" + key + ".lock";
-    if (!path.empty()) {
-        lock_fd = open(lock_path.c_str(), O_CREAT | O_RDWR, 0644);
-        if (lock_fd >= 0 && flock(lock_fd, LOCK_EX) == 0 && (r.code = disk_read(path))) {  // somebody compiled it while we waited
-            r.how = 1;
-            (void)flock(lock_fd, LOCK_UN);
-            close(lock_fd);
-            return r;
-        }
-    }
-    r = hiprtc_compile(arch, src);
-    if (r.rc == SRACK_OK && !path.empty()) disk_write(dir, path, *r.code);
-    if (lock_fd >= 0) {
-        (void)unlink(lock_path.c_str());
-        (void)flock(lock_fd, LOCK_UN);
-        close(lock_fd);
-    }
-    return r;
-}
-
-std::string cache_key(const std::string& arch, const std::string& src)
-{
-    const Rtc& R = rtc();
-    return digest(arch + " " + extra_options_text(), R.ok ? R.version : std::string("no-hiprtc"), headers_digest(), src);
-}
-
-// memory -> disk -> hiprtc.  Takes g_mutex itself; compiles without it.
-Fetched fetch_code(const std::string& arch, const std::string& src)
-{
-    const std::string key = cache_key(arch, src);
-    std::shared_future<Fetched> wait_for;
-    std::promise<Fetched> mine;
-    std::string dir;
-    {
-        std::lock_guard<std::mutex> lock(g_mutex);
-        if (CodePtr* have = g_code.find(key)) {
-            g_stats.memory_hits++;
-            Fetched r;
-            r.code = *have;
-            return r;
-        }
-        auto it = g_inflight.find(key);
-        if (it != g_inflight.end()) {
-            wait_for = it->second;
-        } else {
-            g_inflight[key] = mine.get_future().share();
-            dir = disk_dir();
-        }
-    }
-    if (wait_for.valid()) {  // another thread is on it
-        Fetched r = wait_for.get();
-        r.how = 0;
-        r.compile_ms = 0.0;
-        return r;
-    }
-    // Whatever happens from here on — an allocation failing in the cache's bookkeeping included — the in-flight entry goes and the
-    // waiters get an answer: a broken promise would make every later request for this kernel throw.
-    Fetched r;
-    struct Settle {
-        const std::string& key;
-        std::promise<Fetched>& mine;
-        Fetched& r;
-        ~Settle()
-        {
-            {
-                std::lock_guard<std::mutex> lock(g_mutex);
-                g_inflight.erase(key);
-            }
-            try {
-                mine.set_value(r);
-            } catch (...) {
-                try {
-                    Fetched failed;
-                    failed.rc = SRACK_ERR_NOMEM;
-                    mine.set_value(failed);
-                } catch (...) {
-                }
-            }
-        }
-    } settle{key, mine, r};
-    try {
-        r = fetch_slow(dir, key, arch, src);
-        std::lock_guard<std::mutex> lock(g_mutex);
-        if (r.rc == SRACK_OK) {
-            g_stats.code_evictions += g_code.put(key, r.code, memory_bound());
-            if (r.how == 1) g_stats.disk_hits++;
-            if (r.how == 2) {
-                g_stats.compiled++;
-                g_stats.compile_ms += r.compile_ms;
-            }
-        }
-    } catch (...) {
-        r = Fetched{};
-        r.rc = SRACK_ERR_NOMEM;
-        r.err = "specialise: out of memory";
-    }
-    return r;
-}
-
-}  // namespace
-
-bool jit_supported(const FlatProgram& P, std::string* why)
-{
-    auto no = [&](const std::string& w) {
-        if (why) *why = w;
-        return false;
-    };
-    if (P.ops.empty()) return no("empty program");
-    int n_planes_wire = 0;
-    for (const DevOp& op : P.ops) {
-        switch (op.kind) {
-        case OP_OSC:
-        case OP_VCF:
-        case OP_ADSR:
-        case OP_VCA:
-        case OP_MIX:
-        case OP_MATH:
-        case OP_NONLIN:
-        case OP_NOISE:
-        case OP_GRIDSEQ:
-        case OP_PATSEQ:
-        case OP_SAMPLE: break;
-        case OP_OUT:
-            if (op.in_slot[0] < kTrackSlot) n_planes_wire++;
-            break;
-        case OP_DELAY_RD:
-        case OP_DELAY_WR:
-            break;
-        default: return no("op kind " + std::to_string(op.kind) + (op.kind == OP_FREEVERB ? " (FreeverbModule)" : ""));
-        }
-    }
-    if (n_planes_wire > 4) return no("more than four distinct output planes");  // one LDS mix tile each
-    if ((int)P.ops.size() > 48) return no("more than 48 ops: the state would not stay in registers");
-    return true;
-}
-
-bool jit_ctl_supported(const FlatPair& pair, std::string* why)
-{
-    if (pair.n_tracks <= 0 || pair.ctl.empty()) {
-        if (why) *why = "no control program";
-        return false;
-    }
-    for (const FlatProgram& c : pair.ctl)
-        if (!jit_supported(c, why)) return false;
-    return true;
-}
-
-// One kernel: the voice program, and — with_ctl — the control program's units as blocks [0, block0) of the same launch.
-int jit_source(const FlatPair& pair, int out_mode, bool with_ctl, std::string& src, int waves_budget, int want_waves)
-{
-    const FlatProgram& P = pair.voice;
-    std::string why;
-    if (!jit_supported(P, &why) || (with_ctl && !jit_ctl_supported(pair, &why))) {
-        set_error("specialise: " + why);
-        return SRACK_ERR_UNSUPPORTED;
-    }
-    std::ostringstream o;
-    const int n_units = with_ctl ? (int)pair.ctl.size() : 0;
-    // pow's table in LDS where an exact oscillator's pitch moves (the lookup is inside its recurrence)
-    auto moving_exact = [](const FlatProgram& Q) {
-        for (const DevOp& op : Q.ops)
-            if (op.kind == OP_OSC && (op.flags & (OSC_EXACT | OSC_HAS_CV)) == (OSC_EXACT | OSC_HAS_CV)) return true;
-        return false;
-    };
-    bool libm_tab_lds = moving_exact(P);
-    for (int u = 0; u < n_units; u++) libm_tab_lds = libm_tab_lds || moving_exact(pair.ctl[(size_t)u]);
-    emit_preamble(o, out_mode, libm_tab_lds);
-    for (int u = 0; u < n_units; u++) {
-        Gen g(pair.ctl[(size_t)u], 1, true, "u" + std::to_string(u) + "_");
-        if (!g.gen_ops()) {
-            set_error("specialise (control unit " + std::to_string(u) + "): " + g.err);
-            return SRACK_ERR_UNSUPPORTED;
-        }
-        o << "// control unit " << u << "\n";
-        o << "static __device__ __forceinline__ void srk_ctl" << u << "(const KernelArgs& a)\n{\n";
-        o << "    if (a.T == 0) return;  // an idle slot of the pipeline\n";
-        g.emit_function_body(o);
-        o << "}\n\n";
-    }
-    Gen g(P, out_mode);
-    g.want_waves = want_waves;
-    if (!g.gen_ops()) {
-        set_error("specialise: " + g.err);
-        return SRACK_ERR_UNSUPPORTED;
-    }
-    {
-        // a register budget for so many waves per SIMD (jit_get decides; SRACK_JIT_WAVES overrides, tools/) — the compiler's default for a
-        // 64-thread workgroup is "all 512 registers"
-        const char* w = getenv("SRACK_JIT_WAVES");
-        const int waves = w ? atoi(w) : waves_budget;
-        o << "extern \"C\" __global__ __launch_bounds__(64) ";
-        if (waves >= 1 && waves <= 8) o << "__attribute__((amdgpu_waves_per_eu(" << waves << ", 8))) ";
-        o << "void srk_voice(KernelArgs a)\n{\n";
-        if (libm_tab_lds) o << "    libm_tab_fill((int)threadIdx.x);\n";
-    }
-    if (n_units > 0) {
-        // Blocks [0, block0) are not voice waves: block b evaluates control unit b for a LATER chunk while the voice blocks
-        // consume tracks an earlier launch finished (render.hip).  Same stream, no events, no second hardware queue.  A unit is a
-        // latency chain sharing its SIMD with throughput-bound voice waves: without priority it can outlast them.
-        o << "    if (blockIdx.x < a.block0) {\n        __builtin_amdgcn_s_setprio(3);\n        const KernelArgs c = a.ctl_slots[blockIdx.x];\n";
-        o << "        switch (blockIdx.x) {\n";
-        for (int u = 0; u < n_units; u++) o << "        case " << u << ": srk_ctl" << u << "(c); break;\n";
-        o << "        default: break;\n        }\n        return;\n    }\n";
-    }
-    g.emit_function_body(o);
-    o << "}\n";
-    src = o.str();
-    return SRACK_OK;
-}
 
 int jit_compile_only(const FlatPair& pair, int out_mode, bool with_ctl)
 {
@@ -1977,14 +83,10 @@ int jit_get(const FlatPair& pair, int out_mode, bool with_ctl, std::shared_ptr<c
     }
     const std::string arch = device_arch();
     const std::string kkey = std::to_string(dev) + ":" + cache_key(arch, src);
-    {
-        std::lock_guard<std::mutex> lock(g_mutex);
-        if (auto* have = g_kernels.find(kkey)) {
-            g_stats.memory_hits++;
-            *out = *have;
-            if (how) *how = JitFetchInfo{0, 0.0, budget, vgprs, src.find("_bank_lds[") != std::string::npos};
-            return SRACK_OK;
-        }
+    if (auto have = kernel_cache_find(kkey)) {
+        *out = have;
+        if (how) *how = JitFetchInfo{0, 0.0, budget, vgprs, src.find("_bank_lds[") != std::string::npos};
+        return SRACK_OK;
     }
     const Fetched f = fetch_code(arch, src);
     if (f.rc != SRACK_OK) {
@@ -2007,35 +109,8 @@ int jit_get(const FlatPair& pair, int out_mode, bool with_ctl, std::shared_ptr<c
         return SRACK_ERR_DEVICE;
     }
     k->function = fn;
-    std::lock_guard<std::mutex> lock(g_mutex);
-    if (auto* have = g_kernels.find(kkey)) {  // another thread loaded it meanwhile: one module per kernel and device
-        *out = *have;
-        return SRACK_OK;
-    }
-    // An evicted module stays loaded for as long as a patch renders with it (shared ownership); the cache only forgets it.
-    g_stats.module_evictions += g_kernels.put(kkey, k, memory_bound());
-    g_stats.modules_loaded++;
-    *out = k;
+    *out = kernel_cache_keep(kkey, k);  // (another thread may have loaded it meanwhile: one module per kernel and device)
     return SRACK_OK;
-}
-
-int jit_cache_set_dir(const char* dir)
-{
-    std::lock_guard<std::mutex> lock(g_mutex);
-    g_dir_set = dir != nullptr;
-    g_dir = dir ? dir : "";
-    return SRACK_OK;
-}
-
-JitCacheStats jit_cache_stats()
-{
-    std::lock_guard<std::mutex> lock(g_mutex);
-    JitCacheStats st = g_stats;
-    st.resident_code_objects = g_code.order.size();
-    st.resident_modules = g_kernels.order.size();
-    const std::string dir = disk_dir();
-    std::snprintf(st.directory, sizeof st.directory, "%s", dir.c_str());
-    return st;
 }
 
 int jit_launch(const JitKernel& k, const KernelArgs& ka, uint32_t n_blocks, void* stream)

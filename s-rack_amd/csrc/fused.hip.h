@@ -386,6 +386,16 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
         cosc_init(ca, sa.pos, ka.delta);
         if (a.T > 0) x = cosc_step<kOscAPort>(ca);
     }
+    // Default mode: the ladder's clamp behind the cubic is proved idle for the whole launch (modules.hip.h, vcf_b4_bounded: this filter
+    // has no CV, so its coefficients stay; the state's and the coefficients' bound is the helper's), given an input within [-1, 1] —
+    // which every port of the oscillator delivers while its two PolyBLEP windows do not overlap (increment below 1/4; the phase
+    // inside [0, 1), which the fixed-point phase is by construction).  A wave for which every lane passes runs the tile copies without
+    // that clamp; any other wave, or all of them without kTileVcfB4 in a.tile_flags (SRACK_VCF_B4=0), the copies with all five.
+    bool b4_free = false;
+    if (!kExact && (a.tile_flags & kTileVcfB4) != 0u && a.T > 0) {
+        const bool osc_ok = kFixed ? fa_osc.dhi < 0x40000000u : (ka.delta >= 0.0 && ka.delta < 0.25 && sa.pos >= 0.0 && sa.pos < 1.0);
+        b4_free = __builtin_amdgcn_ballot_w64(!osc_ok) == 0 && vcf_b4_bounded(sv);
+    }
     // The envelope track is wave-uniform data written by an earlier launch: it is read through the scalar unit (constant address
     // space), costing no vector instruction.  A full tile takes it eight samples at a time (uniform_load8, wave.hip.h: one
     // s_load_dwordx8, the next eight requested while these are consumed — four loads and four waits per tile); a short last tile one
@@ -397,11 +407,11 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
     // once per tile instead: lane l looks at sample l & 31 of the NEXT tile (a vector load at the top of this full tile, its ballot taken
     // after this tile's samples — in flight behind the frame stores, never waited for at once; clamped to the launch's last sample),
     // and a full tile whose 32 values are all > 0 runs a copy of the samples with o = y * cv alone: the select would have taken the
-    // product on every one of them, whatever `negative` is.  Any other tile runs the copy that asks per sample.  a.tile_plain = 0
+    // product on every one of them, whatever `negative` is.  Any other tile runs the copy that asks per sample.  Without kTilePlain in a.tile_flags
     // (SRACK_TILE_PLAIN=0, tools/ and tests/): always that one — every value then looks negative to the ballot.
     const uint32_t* env_bits = (const uint32_t*)env_track;
     const uint32_t l32 = (uint32_t)lane & (uint32_t)(kMixRows - 1);
-    const uint32_t gate_force = a.tile_plain != 0u ? 0u : 0x80000000u;
+    const uint32_t gate_force = (a.tile_flags & kTilePlain) != 0u ? 0u : 0x80000000u;
     auto all_pos = [&](uint32_t bits) { return __builtin_amdgcn_ballot_w64(!(((bits | gate_force) - 1u) < 0x7f800000u)) == 0; };
     bool plain = a.T >= (uint32_t)kMixRows && all_pos(env_bits[l32]);
     // Exact mode, saw: the oscillator writes a whole tile first (modules.hip.h, XSaw: windowless values, then each lane repairs
@@ -427,14 +437,18 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
         emit_put<kOut>(em, mix_tile, o, i, V);
         if (pinned) emit_row_pin<kOut>(em);
     };
-    auto sample = [&](int i, float env, bool gated, bool pinned) __attribute__((always_inline)) {
+    // kB4: std::true_type = with the ladder's clamp behind the cubic; std::false_type (default mode, b4_free) = without
+    auto sample = [&](int i, float env, bool gated, bool pinned, auto kB4) __attribute__((always_inline)) {
         if (kExact) {
             float sine = 0.0f, square = 0.0f, saw = 0.0f;
             osc_step(fa, sa, ka, 0.0f, 0.0f, sine, square, saw);
             x = kOscAPort == OSC_OUT_SINE ? sine : (kOscAPort == OSC_OUT_SQUARE ? square : saw);
         }
         float lp, bp, hp;
-        vcf_run<!kExact>(sv, sv_fin, x, lp, bp, hp);
+        if (!kExact && !decltype(kB4)::value)
+            vcf_step<true, true, false>(sv, x, lp, bp, hp);
+        else
+            vcf_run<!kExact>(sv, sv_fin, x, lp, bp, hp);
         const float y = kVcfPort == VCF_OUT_LP ? lp : (kVcfPort == VCF_OUT_BP ? bp : hp);
         if (kFixed) {
             fpos_lo = fa_osc.lo;
@@ -452,8 +466,8 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
         if (pinned) emit_row_pin<kOut>(em);
     };
     // One full tile at t0 (constant trip count: unrollable — readlane is convergent, so a runtime count is not).  kX: the tile-wise
-    // exact saw; gated: the copy that keeps the VCA's gate.
-    auto full_tile = [&](uint32_t t0, auto kX, bool gated) __attribute__((always_inline)) {
+    // exact saw; gated: the copy that keeps the VCA's gate; kB4: the copy that keeps the ladder's fifth clamp.
+    auto full_tile = [&](uint32_t t0, auto kX, bool gated, auto kB4) __attribute__((always_inline)) {
         if (!pace.word) {
             if (t0 >= prio1_at && t0 < prio1_at + kMixRows) __builtin_amdgcn_s_setprio(1);
             if (t0 >= prio0_at && t0 < prio0_at + kMixRows) __builtin_amdgcn_s_setprio(0);
@@ -479,7 +493,7 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
                 }
                 sample_x(i, xin[i & 7], e[i >> 3][i & 7], gated, true);
             } else {
-                sample(i, e[i >> 3][i & 7], gated, true);
+                sample(i, e[i >> 3][i & 7], gated, true, kB4);
             }
         }
         // (the atomic's value is looked at whether a step was taken or not: a register that a vector-memory result may still be on its
@@ -498,16 +512,30 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
         uint32_t t0 = 0;
         // (exact mode's stepwise oscillator, hundreds of f64 instructions per sample, keeps the one gated copy: a second copy of it costs
         // the statistics variant its fourth wave per SIMD, 100 -> 131 VGPRs, for one instruction per sample)
+        // Default mode has four copies: plain and gated without the ladder's fifth clamp for a wave whose vote passed (b4_free), and
+        // plain and gated with all five for any other wave, which so runs exactly the two loops it ran before the vote existed.
         constexpr bool kTwo = !kExact || decltype(kX)::value;
         while (t0 < t_full) {
-            if (kTwo && plain) {
+            if (!kExact && b4_free) {
+                if (plain) {
+                    do {
+                        full_tile(t0, kX, false, std::false_type{});
+                        t0 += kMixRows;
+                    } while (t0 < t_full && plain);
+                } else {
+                    do {
+                        full_tile(t0, kX, true, std::false_type{});
+                        t0 += kMixRows;
+                    } while (t0 < t_full && !plain);
+                }
+            } else if (kTwo && plain) {
                 do {
-                    full_tile(t0, kX, false);
+                    full_tile(t0, kX, false, std::true_type{});
                     t0 += kMixRows;
                 } while (t0 < t_full && plain);
             } else {
                 do {
-                    full_tile(t0, kX, true);
+                    full_tile(t0, kX, true, std::true_type{});
                     t0 += kMixRows;
                 } while (t0 < t_full && !(kTwo && plain));
             }
@@ -523,7 +551,7 @@ __global__ __launch_bounds__(64) void render_voice_chain_track(KernelArgs a, Cha
                 xsaw_tile(xo, mix_tile + lane, kMixPitch, n);
                 for (int i = 0; i < n; i++) sample_x(i, mix_tile[i * kMixPitch + lane], env_s[t0 + (uint32_t)i], true, false);
             } else {
-                for (int i = 0; i < n; i++) sample(i, env_s[t0 + (uint32_t)i], true, false);
+                for (int i = 0; i < n; i++) sample(i, env_s[t0 + (uint32_t)i], true, false, std::true_type{});  // (all five clamps: a rolled loop, no further copy)
             }
             emit_flush<kOut>(em, mix_tile, t0, n, V);
         }

@@ -42,10 +42,14 @@ struct KernelArgs {
     // render_voice_chain_track: this launch's slice of the pacing table (wave.hip.h, kPaceKeys words, cleared by the host), or null: the
     // voice waves keep the open-loop priority ramp
     uint32_t* pace;
-    // render_voice_chain_track: 1 = a full tile whose 32 envelope values are all > 0 runs the copy of the samples without the VCA's
-    // gate (fused.hip.h; same bits either way); 0 = every tile runs the gated copy (SRACK_TILE_PLAIN=0: tools/ and the tests' A/B)
-    uint32_t tile_plain;
+    // render_voice_chain_track: which copies of the tile a wave may run, kTile* below (same bits whatever is set; tools/ and the tests' A/B)
+    uint32_t tile_flags;
 };
+// KernelArgs::tile_flags.  kTilePlain: a full tile whose 32 envelope values are all > 0 runs the copy of the samples without the VCA's
+// gate (fused.hip.h); clear = every tile runs the gated copy (SRACK_TILE_PLAIN=0).  kTileVcfB4: a default-mode wave whose vote passes
+// (modules.hip.h, vcf_b4_bounded) runs without the ladder's clamp behind the cubic; clear = no wave does (SRACK_VCF_B4=0).
+constexpr uint32_t kTilePlain = 1u;
+constexpr uint32_t kTileVcfB4 = 2u;
 
 struct ChainRoles {  // op indices of the fused voice chain (osc_l / adsr unused in the track variant)
     int osc_a, osc_l, vcf, adsr, vca, out, track;

@@ -1232,6 +1232,9 @@ SRK_DEV void xsaw_tile(XSaw& o, Ptr tile, int pitch, int n)
 // ---------------------------------------------------------------------------------------------
 // Moog ladder — InternalMoogFilterState::calc + clamp_buffers, filter.rs:58-92
 // ---------------------------------------------------------------------------------------------
+// (What lies between a `host-probe begin` and a `host-probe end` line is compiled for the CPU by tests/test_vcf_bound_host.py as it
+// stands: plain C++ and __builtin_* that g++ knows, no wave intrinsics.)
+// host-probe begin
 struct VcfRegs {
     float f, p, q;
     float b0, b1, b2, b3, b4;
@@ -1265,6 +1268,7 @@ SRK_DEV void vcf_polys(float frequency, float res, float& p, float& f, float& qq
         qq = res * (1.0f + 0.5f * q * (1.0f - q + 5.6f * q * q));
     }
 }
+// host-probe end
 
 // Lanes whose (frequency, res) pair changed take new coefficients, the others keep theirs (`changed_lanes`: the ballot of `changed`,
 // not zero).  A cutoff swept by an envelope changes in every lane at once: that case, wave-uniform and known before the arithmetic,
@@ -1322,7 +1326,10 @@ SRK_DEV void vcf_coeffs_freq(VcfRegs& s, float frequency, float res)
 // kMed3 (default: as kFast): the clamps as v_med3_f32.  Identical to min/max for every non-NaN value, so the exact flavour may
 // use it too whenever no NaN can reach the filter: its states are clamped to [-1, 1] and its coefficients are finite, so a NaN
 // can only come in through the input (see vcf_nan_free).
-template <bool kFast = false, bool kMed3 = kFast>
+// kClampB4 = false: the clamp behind the cubic is left out and nothing else — for a wave whose vcf_b4_bounded vote has shown that it would
+// return its operand on every sample of the launch.
+// host-probe begin
+template <bool kFast = false, bool kMed3 = kFast, bool kClampB4 = true>
 SRK_DEV void vcf_step(VcfRegs& s, float input, float& lowpass, float& bandpass, float& highpass)
 {
     if (kFast) {
@@ -1350,11 +1357,12 @@ SRK_DEV void vcf_step(VcfRegs& s, float input, float& lowpass, float& bandpass, 
     s.b1 = clamp1<kMed3>(s.b1);
     s.b2 = clamp1<kMed3>(s.b2);
     s.b3 = clamp1<kMed3>(s.b3);
-    s.b4 = clamp1<kMed3>(s.b4);
+    if (kClampB4) s.b4 = clamp1<kMed3>(s.b4);
     lowpass = s.b4;
     highpass = input - s.b4;
     bandpass = 3.0f * (s.b3 - s.b4);
 }
+// host-probe end
 
 // No lane of the wave holds a NaN (or an infinity) in the filter's state or coefficients: with a finite input every later
 // value is finite too (the states are clamped, the arithmetic is sums and products of bounded numbers).
@@ -1363,6 +1371,37 @@ SRK_DEV bool vcf_nan_free(const VcfRegs& s)
     auto fin = [](float x) { return __builtin_fabsf(x) < __builtin_inff(); };
     return __builtin_amdgcn_ballot_w64(!(fin(s.f) && fin(s.p) && fin(s.q) && fin(s.b0) && fin(s.b1) && fin(s.b2) && fin(s.b3) && fin(s.b4))) == 0;
 }
+
+// The clamp behind the cubic, s.b4 = clamp1(s.b4), returns its operand on every sample of a launch — the vote, wave-uniform, once per
+// launch behind vcf_coeffs, for a filter whose coefficients do not change during the launch and whose input stays within
+// |x| <= kVcfB4InMax (the caller's business: an oscillator's output).
+//   The clamps act at the END of a step (filter.rs:81), so the stages inside a step see the step's own b1 ... b3 unclamped; what is known
+// at a step's start is |b0 ... b3| <= 1 and |b4| <= M.  The value entering the cubic is LINEAR in x and in that state: unrolled,
+//     pre = p^4 (x + b0) + p^3 (1 - f) b1 + p^2 (1 - f) b2 + p (1 - f) b3 - (f + p^4 q) b4,
+// so  |pre| <= p^4 (X + 1) + (|p|^3 + p^2 + |p|) |1 - f| + (|f| + p^4 |q|) M  — attained at a corner of the state's box, so it is sharp.
+// With the ladder's own f = 2p - 1, 0 <= p <= 1 and X = 1 this is 2p + (|f| + p^4 q) M: the resonance feedback reaches the fourth stage
+// within the step, damped by p^4 only.  (2p + |f| M, the bound one gets by taking the fourth stage's operand b3' + b3 as clamped, is
+// not one: cutoff 0.89, resonance 1, b0 ... b3 = 1, b4 = -0.95, x = 1 passes it, enters the cubic at 3.71 and leaves it at -4.8.)
+//   The cubic g(y) = y - y^3 * 0.166667 has |g| <= 0.9428 on |y| <= sqrt(2) and grows again beyond: |g(2.83)| = 0.94753 (both forms, swept
+// in f32), |g| = 1 at |y| = 2.847.  So |pre| <= kVcfB4PreMax = 2.83 gives |b4'| <= 0.9476 <= kVcfB4Bound = 0.95 — inside the clamp, which
+// v_med3 then passes through bit for bit — and with M = max(|b4|, 0.95) at the launch's start the same inequality holds for the next
+// step (the clamps keep b0 ... b3, the coefficients stay): for the whole launch.  The f32 roundings of the stages and of this test, a few
+// 1e-7 each, are covered by the 2.5e-3 between 0.94753 and 0.95 (|g'(2.83)| = 3.0).
+//   Every comparison is written so that a NaN fails it: a NaN state then keeps the clamp that turns it into -1.0 (clamp1).
+// host-probe begin
+constexpr float kVcfB4PreMax = 2.83f;
+constexpr float kVcfB4Bound = 0.95f;
+constexpr float kVcfB4InMax = 1.0f;
+SRK_DEV bool vcf_b4_bounded_lane(const VcfRegs& s)
+{
+    auto unit = [](float x) { return __builtin_fabsf(x) <= 1.0f; };
+    const float ap = __builtin_fabsf(s.p), p2 = s.p * s.p, p4 = p2 * p2;
+    const float m = fmaxf(__builtin_fabsf(s.b4), kVcfB4Bound);
+    const float pre = p4 * (kVcfB4InMax + 1.0f) + (p2 * ap + p2 + ap) * __builtin_fabsf(1.0f - s.f) + (__builtin_fabsf(s.f) + p4 * __builtin_fabsf(s.q)) * m;
+    return unit(s.b0) && unit(s.b1) && unit(s.b2) && unit(s.b3) && unit(s.b4) && pre <= kVcfB4PreMax;
+}
+// host-probe end
+SRK_DEV bool vcf_b4_bounded(const VcfRegs& s) { return __builtin_amdgcn_ballot_w64(!vcf_b4_bounded_lane(s)) == 0; }
 
 // The ladder as a kernel calls it.  kFast: the default mode's contracted form.  Otherwise the literal operations — with the clamps
 // as v_med3 (half the instructions of min + max) whenever that cannot be told from the reference: the two differ only on a NaN,

@@ -60,6 +60,7 @@ struct Knobs {
                                       // cfg3_poly 16.40 against 16.43 — at the power cap a kernel that runs beside the voices is paid for in clock
     int pace = 1;                     // the flagship's voice waves pace themselves against their SIMD's other waves (wave.hip.h, notes/r10.md); 0: the open-loop priority ramp
     int tile_plain = 1;               // the flagship's all-positive envelope tiles run without the VCA's gate (fused.hip.h, notes/r15.md); 0: every tile keeps it — same bits
+    int vcf_b4 = 1;                   // the flagship's default-mode waves vote on the ladder's clamp behind the cubic and run without it where a bound rules it out (modules.hip.h vcf_b4_bounded, notes/r30.md); 0: the vote fails — same bits
     int tick = 2;                     // calls keep the control program running ahead across calls (TickSession below); 1: calls of one chunk only (round 3); 0: every call starts it afresh
 };
 static const Knobs& knobs()
@@ -88,6 +89,7 @@ static const Knobs& knobs()
         v.mix_aside = (int)num("SRACK_MIX_ASIDE", 0, 1, 0);
         v.pace = (int)num("SRACK_PACE", 0, 1, 1);
         v.tile_plain = (int)num("SRACK_TILE_PLAIN", 0, 1, 1);
+        v.vcf_b4 = (int)num("SRACK_VCF_B4", 0, 1, 1);
         return v;
     }();
     return k;
@@ -1248,7 +1250,7 @@ struct Segment {
             ka.lanes = lanes;
             ka.n0 = h.samples_rendered + t_off;
             ka.stats = fold ? nullptr : d_stats;  // (in-kernel statistics: the fused voice chains)
-            ka.tile_plain = (uint32_t)knobs().tile_plain;
+            ka.tile_flags = (knobs().tile_plain ? kTilePlain : 0u) | (knobs().vcf_b4 ? kTileVcfB4 : 0u);
             if (fold_rows) {
                 ka.frames = d->d_stat_frames;
                 ka.plane_stride = (uint64_t)fold_rows * V;

@@ -155,6 +155,11 @@ public:
     // one mix per bus.  The table is not part of the program: changing it between execute_batch calls restarts nothing.
     void set_buses(uint32_t n_buses, const int* bus = nullptr, const float* gain = nullptr) { check(srack_voices_set_buses(p_, n_buses, bus, gain)); }
     uint32_t get_buses(int* bus = nullptr, float* gain = nullptr, uint32_t cap = 0) const { return (uint32_t)check(srack_voices_get_buses(p_, bus, gain, cap)); }
+    // The same table with up to SRACK_MAX_VOICE_SLOTS buses per voice and a gain per channel: bus [n_voices][n_slots] (nullptr: slot 0 is
+    // bus 0), gain [n_voices][n_slots][channels] (nullptr: 1).  Pan is one slot with a gain per channel, a per-voice send a second slot; the
+    // fold still reads each frame once.  One table per handle: set_buses and set_bus_slots replace each other.
+    void set_bus_slots(uint32_t n_buses, uint32_t n_slots, const int* bus = nullptr, const float* gain = nullptr) { check(srack_voices_set_bus_slots(p_, n_buses, n_slots, bus, gain)); }
+    uint32_t get_bus_slots(int* n_slots = nullptr, int* bus = nullptr, float* gain = nullptr, uint32_t cap = 0) const { return (uint32_t)check(srack_voices_get_bus_slots(p_, n_slots, bus, gain, cap)); }
     // A wave per voice for a SampleModule: a bank of n_waves waves back to back (lengths, rates; copied) and, per voice, an index into it
     // or SRACK_WAVE_OWN (the module's own wave).  Voice v plays what a one-voice patch plays after set_wave(bank wave wave[v], its rate).
     void set_wave_bank(const SharedSynthModule& m, const float* samples, const int* lengths, const float* sample_rates, uint32_t n_waves)

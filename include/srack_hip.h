@@ -434,6 +434,39 @@ int srack_voices_get_buses(const srack_patch* p, int* bus, float* gain, uint32_t
  * the scratch rows ascend with the tile: that is the order the bus's segments are added in.  Either pointer may be NULL. */
 int srack_voices_bus_plan(const srack_patch* p, int* segments, uint32_t segment_cap, int* order, uint32_t order_cap);
 
+/* ---- voice bus slots: each voice in up to four buses, a gain per channel ---------------------------------------
+ * The mix table generalised the way a console expects it: a voice feeds up to n_slots buses, each with a gain PER CHANNEL.  Pan is
+ * one slot with different gains for Left and Right — in the reference two MonoMixerModules fed by the same wire, each with its own gain
+ * per input (mixer.rs:106-119) — and costs no second plane; a per-voice send amount ("this voice dry, that one drenched") is a second
+ * slot naming an aux bus.  Host memory, copied:
+ *   bus  : [n_voices][n_slots], bus[v][k] in [0, n_buses) or SRACK_BUS_NONE;  NULL = slot 0 is bus 0, the other slots are none
+ *   gain : [n_voices][n_slots][channels], any f32, copied bit for bit;         NULL = 1.0f
+ * 1 <= n_slots <= SRACK_MAX_VOICE_SLOTS; `channels` is the channel count the patch was created with.  A voice may name the same bus
+ * in several slots: there are then two terms.  Errors and lifetime follow srack_voices_set_buses: SRACK_ERR_STATE before
+ * srack_voices_configure; SRACK_ERR_INVALID for a bad count or index, the earlier table (of either kind) left in place;
+ * srack_voices_configure drops the table; another n_buses drops the console's stages, the same n_buses keeps them.  The table is not
+ * part of the program: setting it re-flattens nothing, restarts nothing, changes no bit of frames, mix, statistics or voice state and
+ * does not change which kernel renders.
+ * There is ONE mix table per handle and the two setters replace each other; every console call that needs "a mix table" accepts either.
+ * srack_voices_get_buses on a slot table returns n_buses and copies slot 0 and channel 0; srack_voices_get_bus_slots on a table set
+ * through srack_voices_set_buses reports n_slots = 1 with the gain repeated per channel.  srack_voices_bus_plan on a slot table: a
+ * segment's "tile" is the GROUP index tile * n_slots + slot, `order` holds real voice numbers; for n_slots == 1 the answer equals the
+ * plan the same table gives through srack_voices_set_buses.  srack_render_info writes " buses=<n>[fold slots=<K>]".
+ *
+ * srack_render_buses with a slot table fills d_bus_mix as before.  For bus b and channel c with plane(c) >= 0 the terms are all (v, k)
+ * with bus[v][k] == b, each term p = fl32(gain[v][k][c] * x[plane(c)][t][v]).  A GROUP is the terms of one (tile = v / 64, slot k),
+ * voices ascending; a group's sum is its first product, then one f32 addition per further term, in order; the bus's sample is the first
+ * group's sum, then one f32 addition per further group, in ascending (tile, slot).  IEEE f32, one rounding per operation, no fma, no
+ * atomics.  A bus without terms is +0.0f, an unconnected channel is 0.  A non-finite gain or sample reaches the buses and channels it
+ * is sent to, and no others.  The order depends on the table and the voice count alone — never on n_samples, on how the render is cut
+ * or on what else the call is asked for.  With n_slots == 1 and equal gains across channels this is the definition of
+ * srack_render_buses below word for word, and the bits are the same.  Each frame is read from device memory once per fold, whatever
+ * n_slots and the channel count are. */
+#define SRACK_MAX_VOICE_SLOTS 4
+int srack_voices_set_bus_slots(srack_patch* p, uint32_t n_buses, uint32_t n_slots, const int* bus, const float* gain);
+/* returns n_buses (0: no table set; *n_slots is then 0); copies up to cap VOICES of each (any pointer may be NULL) */
+int srack_voices_get_bus_slots(const srack_patch* p, int* n_slots, int* bus, float* gain, uint32_t cap);
+
 /* srack_render_stats plus the bus mixes:
  *   d_bus_mix : device, f32 [n_buses][channels][n_samples]
  *   d_bus_mix[b][c][t] = sum over the voices v with bus[v] == b of  fl32(gain[v] * x[plane(c)][t][v])

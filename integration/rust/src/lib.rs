@@ -58,6 +58,8 @@ mod ffi {
         pub fn srack_render_stats(p: *mut SrackPatch, n_samples: u32, d_frames: *mut f32, d_mix: *mut f32, d_stats: *mut f64, flags: u32, stream: *mut c_void) -> c_int;
         pub fn srack_voices_set_buses(p: *mut SrackPatch, n_buses: u32, bus: *const c_int, gain: *const f32) -> c_int;
         pub fn srack_voices_get_buses(p: *const SrackPatch, bus: *mut c_int, gain: *mut f32, cap: u32) -> c_int;
+        pub fn srack_voices_set_bus_slots(p: *mut SrackPatch, n_buses: u32, n_slots: u32, bus: *const c_int, gain: *const f32) -> c_int;
+        pub fn srack_voices_get_bus_slots(p: *const SrackPatch, n_slots: *mut c_int, bus: *mut c_int, gain: *mut f32, cap: u32) -> c_int;
         pub fn srack_patch_set_wave_bank(p: *mut SrackPatch, module: c_int, samples: *const f32, lengths: *const c_int, sample_rates: *const f32, n_waves: u32) -> c_int;
         pub fn srack_patch_get_wave_bank(p: *const SrackPatch, module: c_int, lengths: *mut c_int, sample_rates: *mut f32, cap: u32) -> c_int;
         pub fn srack_patch_get_wave_bank_samples(p: *const SrackPatch, module: c_int, wave: c_int, samples: *mut f32, cap: u32) -> c_int;
@@ -125,6 +127,8 @@ pub mod stat {
 /// Mix buses (`SRACK_MAX_BUSES`, `SRACK_BUS_NONE`).
 pub const MAX_BUSES: u32 = 65536;
 pub const BUS_NONE: i32 = -1;
+/// The most buses a voice can feed through `set_bus_slots` (`SRACK_MAX_VOICE_SLOTS`).
+pub const MAX_VOICE_SLOTS: u32 = 4;
 /// A voice that plays its SampleModule's own wave, not one of the bank (`SRACK_WAVE_OWN`).
 pub const WAVE_OWN: i32 = -1;
 /// A voice that plays its sequencer's own cells at the module's length, not a sequence of the bank (`SRACK_SEQ_OWN`).
@@ -329,6 +333,22 @@ impl Patch {
         let (mut b, mut g) = (vec![0 as c_int; n_voices], vec![0f32; n_voices]);
         let n = check(unsafe { ffi::srack_voices_get_buses(self.raw, b.as_mut_ptr(), g.as_mut_ptr(), n_voices as u32) })?;
         Ok((n as u32, b, g))
+    }
+    /// The mix table with up to `MAX_VOICE_SLOTS` buses per voice and a gain per channel: `bus[v][k]` (None: slot 0 is bus 0, the others
+    /// none), `gain[v][k][c]` any f32 (None: 1.0).  Pan is one slot with a gain per channel, a per-voice send a second slot.  Replaces a
+    /// table set with `set_buses`, and is replaced by it (`srack_voices_set_bus_slots`).
+    pub fn set_bus_slots(&mut self, n_buses: u32, n_slots: u32, bus: Option<&[i32]>, gain: Option<&[f32]>) -> Result<(), Error> {
+        let b = bus.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        let g = gain.map_or(std::ptr::null(), |x| x.as_ptr());
+        check(unsafe { ffi::srack_voices_set_bus_slots(self.raw, n_buses, n_slots, b, g) }).map(|_| ())
+    }
+    /// `(n_buses, n_slots, bus [n_voices][n_slots], gain [n_voices][n_slots][channels])` of the table set; `n_buses` 0: none set.
+    pub fn get_bus_slots(&self, n_voices: usize, channels: usize) -> Result<(u32, u32, Vec<i32>, Vec<f32>), Error> {
+        let mut k: c_int = 0;
+        let n = check(unsafe { ffi::srack_voices_get_bus_slots(self.raw, &mut k, std::ptr::null_mut(), std::ptr::null_mut(), 0) })?;
+        let (mut b, mut g) = (vec![0 as c_int; n_voices * k as usize], vec![0f32; n_voices * k as usize * channels]);
+        check(unsafe { ffi::srack_voices_get_bus_slots(self.raw, &mut k, b.as_mut_ptr(), g.as_mut_ptr(), n_voices as u32) })?;
+        Ok((n as u32, k as u32, b, g))
     }
     /// A bank of waves for a SampleModule, laid back to back in `samples`: wave k has `lengths[k]` samples and the rate `sample_rates[k]`
     /// (`srack_patch_set_wave_bank`; an empty bank removes it).  Inert until `set_voice_waves` assigns voices to it.

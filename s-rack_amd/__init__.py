@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libsrack_hip.so")
 
 OK, ERR_INVALID, ERR_PORT, ERR_NO_OUTPUT, ERR_SELF_LOOP, ERR_STATE, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8
 MAX_BUSES, BUS_NONE = 65536, -1
+MAX_VOICE_SLOTS = 4  # srack_voices_set_bus_slots: the most buses a voice can feed
 MASTER_RUN, MASTER_BLOCK = 64, 64  # buses per run, runs per block: the order srack_buses_master adds in
 MAX_SENDS = 1048576  # srack_buses_set_sends: the longest send list
 BUS_FILTER_NPARAMS, BUS_FILTER_NSTATE = 3, 10  # srack_buses_set_filter: FREQ, RES, EXP_AMT per bus; srack_buses_filter_state: VCF_ST_F .. VCF_ST_RES per bus and channel
@@ -46,6 +47,7 @@ ABI_SYMBOLS = [
     "srack_patch_plan", "srack_patch_plan_list", "srack_patch_removed_edges", "srack_patch_delayed_edges",
     "srack_voices_configure", "srack_voices_set_field_f32", "srack_voices_set_field_f64", "srack_render_planes", "srack_render", "srack_render_stats", "srack_render_reserve",
     "srack_voices_set_buses", "srack_voices_get_buses", "srack_voices_bus_plan", "srack_render_buses",
+    "srack_voices_set_bus_slots", "srack_voices_get_bus_slots",
     "srack_buses_set_reverb", "srack_buses_get_reverb", "srack_buses_reset_reverb", "srack_buses_reverb_plan", "srack_buses_reverb",
     "srack_buses_set_master", "srack_buses_get_master", "srack_buses_master",
     "srack_buses_set_sends", "srack_buses_get_sends", "srack_buses_send_plan", "srack_buses_send",
@@ -124,6 +126,9 @@ def _load():
         L.srack_voices_get_buses.argtypes = [vp, ip, fp, u32]
         L.srack_voices_bus_plan.argtypes = [vp, ip, u32, ip, u32]
         L.srack_render_buses.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp]
+    if hasattr(L, "srack_voices_set_bus_slots"):
+        L.srack_voices_set_bus_slots.argtypes = [vp, u32, u32, ip, fp]
+        L.srack_voices_get_bus_slots.argtypes = [vp, ip, ip, fp, u32]
     if hasattr(L, "srack_buses_reverb"):
         L.srack_buses_set_reverb.argtypes = [vp, dp, ip]
         L.srack_buses_get_reverb.argtypes = [vp, dp, ip, u32]
@@ -573,13 +578,36 @@ class Patch:
         _check(lib.srack_voices_get_buses(self.h, b.ctypes.data_as(C.POINTER(C.c_int)), g.ctypes.data_as(C.POINTER(C.c_float)), self.n_voices))
         return n, b, g
 
+    def set_bus_slots(self, n_buses, bus, gain=None):
+        """The mix table with up to MAX_VOICE_SLOTS buses per voice and a gain per channel (srack_voices_set_bus_slots): bus int [V][K],
+        entries in [0, n_buses) or BUS_NONE (None: slot 0 is bus 0, the other slots none; K then comes from gain, or is 1), gain f32
+        [V][K][channels], any f32 (None: 1.0).  Replaces a table set with set_buses, and is replaced by it.  Not part of the program."""
+        k = np.shape(bus)[1] if bus is not None and np.ndim(bus) == 2 else np.shape(gain)[1] if gain is not None and np.ndim(gain) == 3 else 1
+        _, b = _opt(bus, np.intc, (self.n_voices, k))
+        _, g = _opt(gain, np.float32, (self.n_voices, k, self.channels))
+        _check(lib.srack_voices_set_bus_slots(self.h, n_buses, k, b, g))
+
+    def get_bus_slots(self):
+        """-> (n_buses, bus int32 [V][K], gain f32 [V][K][channels]); a table set with set_buses comes back with K = 1 and its gain repeated
+        per channel; (0, None, None) when no table is set"""
+        k = C.c_int(0)
+        n = _check(lib.srack_voices_get_bus_slots(self.h, C.byref(k), None, None, 0))
+        if n == 0:
+            return 0, None, None
+        b, g = np.empty((self.n_voices, k.value), dtype=np.intc), np.empty((self.n_voices, k.value, self.channels), dtype=np.float32)
+        _check(lib.srack_voices_get_bus_slots(self.h, C.byref(k), b.ctypes.data_as(C.POINTER(C.c_int)), g.ctypes.data_as(C.POINTER(C.c_float)), self.n_voices))
+        return n, b, g
+
     def bus_plan(self):
-        """How the table is laid out for the bus fold (srack_voices_bus_plan) -> (segments int [S][4]: tile, bus, scratch row or -1, voices;
-        order: the voices segment after segment)"""
+        """How the table is laid out for the bus fold (srack_voices_bus_plan) -> (segments int [S][4]: tile (a slot table: the group
+        tile * K + slot), bus, scratch row or -1, voices; order: the voices segment after segment)"""
         n = _check(lib.srack_voices_bus_plan(self.h, None, 0, None, 0))
-        seg, order = np.zeros((n, 4), dtype=np.intc), np.zeros(max(1, self.n_voices), dtype=np.intc)
-        _check(lib.srack_voices_bus_plan(self.h, seg.ctypes.data_as(C.POINTER(C.c_int)), n, order.ctypes.data_as(C.POINTER(C.c_int)), self.n_voices))
-        return seg, order[:int(seg[:, 3].sum())]
+        seg = np.zeros((n, 4), dtype=np.intc)
+        _check(lib.srack_voices_bus_plan(self.h, seg.ctypes.data_as(C.POINTER(C.c_int)), n, None, 0))
+        m = int(seg[:, 3].sum())
+        order = np.zeros(max(1, m), dtype=np.intc)
+        _check(lib.srack_voices_bus_plan(self.h, seg.ctypes.data_as(C.POINTER(C.c_int)), n, order.ctypes.data_as(C.POINTER(C.c_int)), m))
+        return seg, order[:m]
 
     # ---- bus reverbs: a Freeverb per mix bus, behind the mixer ---------------------------------------
     def set_bus_reverbs(self, params=None, enabled=None):

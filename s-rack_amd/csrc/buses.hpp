@@ -74,4 +74,18 @@ inline BusPlan bus_plan_make(uint32_t n_voices, uint32_t n_buses, const int32_t*
     return P;
 }
 
+// A slot table (srack_voices_set_bus_slots): a voice feeds up to n_slots buses.  The plan is the one above over GROUPS instead of
+// tiles: group tile * n_slots + k is slot k of the tile's 64 voices, laid out as 64 entries of a virtual voice array (the ragged
+// tail in no bus), so `order` still holds lanes of the tile, a bus's rows ascend in (tile, slot) order, and n_slots == 1 gives the
+// plan of the same table through srack_voices_set_buses (n_tiles counts groups; n_voices is the virtual array's length).
+// bus: [n_voices][n_slots], entries in [0, n_buses) or -1 (validated by the caller)
+inline BusPlan bus_slot_plan_make(uint32_t n_voices, uint32_t n_buses, uint32_t n_slots, const int32_t* bus)
+{
+    const uint32_t n_tiles = (n_voices + kBusTile - 1) / kBusTile;
+    std::vector<int32_t> virt((size_t)n_tiles * n_slots * kBusTile, -1);
+    for (uint32_t v = 0; v < n_voices; v++)
+        for (uint32_t k = 0; k < n_slots; k++) virt[((size_t)(v / kBusTile) * n_slots + k) * kBusTile + v % kBusTile] = bus[(size_t)v * n_slots + k];
+    return bus_plan_make((uint32_t)virt.size(), n_buses, virt.data());
+}
+
 }  // namespace srack

@@ -676,6 +676,9 @@ int srack_voices_configure(srack_patch* p, uint32_t n_voices)
         p->h.bus.clear();
         p->h.bus_gain.clear();
         p->h.bus_plan = BusPlan();
+        p->h.bus_slots = 0;
+        p->h.slot_bus.clear();
+        p->h.slot_gain.clear();
         p->h.bus_revision++;
         device_console_drop(p->h);  // the console's stages sat behind that table
         return SRACK_OK;
@@ -754,8 +757,78 @@ int srack_voices_set_buses(srack_patch* p, uint32_t n_buses, const int* bus, con
         h.bus = std::move(b);
         h.bus_gain = std::move(g);
         h.bus_plan = std::move(plan);
+        h.bus_slots = 0;  // (the one table of the handle is of this kind now)
+        h.slot_bus.clear();
+        h.slot_gain.clear();
         h.bus_revision++;
         return SRACK_OK;
+    });
+}
+
+int srack_voices_set_bus_slots(srack_patch* p, uint32_t n_buses, uint32_t n_slots, const int* bus, const float* gain)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        PatchHandle& h = p->h;
+        if (h.n_voices == 0) {
+            set_error("voices_set_bus_slots: call srack_voices_configure first");
+            return SRACK_ERR_STATE;
+        }
+        if (n_buses == 0 || n_buses > SRACK_MAX_BUSES) {
+            set_error("voices_set_bus_slots: n_buses must be 1 .. 65536");
+            return SRACK_ERR_INVALID;
+        }
+        if (n_slots == 0 || n_slots > SRACK_MAX_VOICE_SLOTS) {
+            set_error("voices_set_bus_slots: n_slots must be 1 .. 4");
+            return SRACK_ERR_INVALID;
+        }
+        const size_t V = h.n_voices, K = n_slots, C = (size_t)h.graph.cfg.channels;
+        for (size_t i = 0; bus && i < V * K; i++)
+            if (bus[i] < SRACK_BUS_NONE || (bus[i] >= 0 && (uint32_t)bus[i] >= n_buses)) {
+                set_error("voices_set_bus_slots: voice " + std::to_string(i / K) + " slot " + std::to_string(i % K) + " names bus " + std::to_string(bus[i]) + " of " + std::to_string(n_buses));
+                return SRACK_ERR_INVALID;
+            }
+        // (built aside and committed at the end, as in srack_voices_set_buses)
+        std::vector<int32_t> sb(V * K, SRACK_BUS_NONE), b0(V);
+        std::vector<float> sg(V * K * C, 1.0f), g0(V);
+        if (bus) std::copy(bus, bus + V * K, sb.begin());
+        else
+            for (size_t v = 0; v < V; v++) sb[v * K] = 0;
+        if (gain) std::copy(gain, gain + V * K * C, sg.begin());
+        for (size_t v = 0; v < V; v++) {
+            b0[v] = sb[v * K];
+            g0[v] = sg[v * K * C];
+        }
+        BusPlan plan = bus_slot_plan_make(h.n_voices, n_buses, n_slots, sb.data());
+        if (n_buses != h.n_buses) device_console_drop(h);
+        h.n_buses = n_buses;
+        h.bus = std::move(b0);
+        h.bus_gain = std::move(g0);
+        h.bus_plan = std::move(plan);
+        h.bus_slots = n_slots;
+        h.slot_bus = std::move(sb);
+        h.slot_gain = std::move(sg);
+        h.bus_revision++;
+        return SRACK_OK;
+    });
+}
+
+int srack_voices_get_bus_slots(const srack_patch* p, int* n_slots, int* bus, float* gain, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        CHECK_HANDLE(p);
+        const PatchHandle& h = p->h;
+        const size_t K = h.bus_slots ? h.bus_slots : 1u, C = (size_t)h.graph.cfg.channels;
+        const size_t n = h.n_buses ? std::min(cap, h.n_voices) : 0u;
+        if (n_slots) *n_slots = h.n_buses ? (int)K : 0;
+        if (h.bus_slots) {
+            if (bus) std::copy(h.slot_bus.begin(), h.slot_bus.begin() + n * K, bus);
+            if (gain) std::copy(h.slot_gain.begin(), h.slot_gain.begin() + n * K * C, gain);
+        } else {  // a table set through srack_voices_set_buses: one slot, the gain repeated per channel
+            if (bus) std::copy(h.bus.begin(), h.bus.begin() + n, bus);
+            for (size_t i = 0; gain && i < n * C; i++) gain[i] = h.bus_gain[i / C];
+        }
+        return (int)h.n_buses;
     });
 }
 
@@ -776,6 +849,7 @@ int srack_voices_bus_plan(const srack_patch* p, int* segments, uint32_t segment_
     return guarded([&]() -> int {
         CHECK_HANDLE(p);
         const BusPlan& B = p->h.bus_plan;
+        const uint32_t K = p->h.bus_slots ? p->h.bus_slots : 1u;  // a slot table: `i` below is the group tile * K + slot
         uint32_t n_order = 0;
         for (uint32_t i = 0; i < B.n_tiles; i++)
             for (uint32_t s = B.tile_seg[i]; s < B.tile_seg[i + 1]; s++) {
@@ -787,7 +861,7 @@ int srack_voices_bus_plan(const srack_patch* p, int* segments, uint32_t segment_
                     segments[4 * s + 3] = (int)(j1 - j0);
                 }
                 for (uint32_t j = j0; j < j1; j++, n_order++)
-                    if (order && n_order < order_cap) order[n_order] = (int)(i * kBusTile + B.order[(size_t)i * kBusTile + j]);
+                    if (order && n_order < order_cap) order[n_order] = (int)(i / K * kBusTile + B.order[(size_t)i * kBusTile + j]);
             }
         return (int)B.seg_end.size();
     });

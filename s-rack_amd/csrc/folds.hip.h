@@ -2,6 +2,7 @@
 //   mix_reduce_groups/final   deterministic sum of the per-wave mix partials (no atomics)
 //   stats_fold                per-voice statistics of a launch's frames
 //   bus_fold_tiles/sum        weighted, grouped mix-down of a launch's frames (mix buses)
+//   bus_slot_fold_tiles/sum   the same with up to four buses per voice and a gain per channel (voice bus slots)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -179,6 +180,103 @@ __global__ __launch_bounds__(256) void bus_fold_sum(BusFoldArgs a)
     }
     for (uint32_t c = 0; c < a.n_channels; c++)
         if (a.channel_plane[c] < 0) o[(size_t)c * a.out_stride] = 0.0f;
+}
+
+// ---- voice bus slots: bus_mix[b][c][t] = sum over the (v, k) with bus[v][k] == b of fl32(gain[v][k][c] * x[plane(c)][t][v]) ------------
+// The same two passes over a plan of GROUPS (tile, slot) instead of tiles (buses.hpp: bus_slot_plan_make), with a gain per slot and
+// channel.
+//
+// Pass 1, bus_slot_fold_tiles: one wave per (tile of 64 voices, slab of 64 rows, plane), as bus_fold_tiles.  The wave loads its 64
+// rows ONCE, into 64 registers per lane (64 loads of 256 bytes in flight) — each frame is read from global memory once per wave,
+// whatever the number of slots and channels: that is what a slot costs less than a plane.  Then, for every slot of the tile that has
+// a segment and every channel mapped to this plane, it (1) writes fl32(gain * row) into the one LDS tile, (2) sums row-wise, segment
+// by segment, in the group's order handed round by v_readlane, (3) stores each segment's 64 sums as one 256-byte store, to the
+// segment's partial row OF THAT CHANNEL or straight to out[bus][channel].  A barrier separates the uses of the tile.  The LDS tile
+// has the pitch of bus_fold_tiles (65 dwords) and is written and read in the same pattern, so the bank argument in that kernel's
+// header carries over unchanged: no table can produce a conflict.
+// Pass 2, bus_slot_fold_sum: one thread per (bus, channel, sample) adds the bus's partial rows of the channel in ascending row
+// (= (tile, slot)) order; an empty bus and an unconnected channel are +0.
+struct BusSlotFoldArgs : BusFoldArgs {  // gain: [n_slots][n_channels][V]; part: [n_channels][n_partials][part_pitch]; tile_seg per GROUP
+    uint32_t n_slots;
+};
+
+__global__ __launch_bounds__(64) void bus_slot_fold_tiles(BusSlotFoldArgs a)
+{
+    __shared__ float tile[kBusRows * kBusPitch];
+    const int lane = (int)threadIdx.x;
+    const uint32_t ti = blockIdx.x, t0 = blockIdx.y * (uint32_t)kBusRows, plane = blockIdx.z;
+    const uint32_t K = a.n_slots, g0 = ti * K;
+    if (a.tile_seg[g0] == a.tile_seg[g0 + K]) return;  // no voice of this tile is in a bus, in any slot
+    const uint32_t n = min((uint32_t)kBusRows, a.T - t0);
+    const uint32_t v = min(ti * 64u + (uint32_t)lane, a.V - 1u);  // (lanes past the last voice read it again; `order` never names them)
+    const float* f = a.frames + (size_t)plane * a.plane_stride + (size_t)t0 * a.V + v;
+    float x[kBusRows];  // the wave's frames: loaded here, once, and only multiplied below
+    if (n == (uint32_t)kBusRows) {
+#pragma unroll
+        for (int r = 0; r < kBusRows; r++) x[r] = f[(size_t)r * a.V];
+    } else {  // a ragged last slab: only the rows that exist
+#pragma unroll
+        for (int r = 0; r < kBusRows; r++) x[r] = (uint32_t)r < n ? f[(size_t)r * a.V] : 0.0f;
+    }
+    const float* row = tile + lane * kBusPitch;
+    for (uint32_t k = 0; k < K; k++) {
+        const uint32_t s0 = a.tile_seg[g0 + k], n_seg = a.tile_seg[g0 + k + 1] - s0;
+        if (n_seg == 0) continue;  // (wave-uniform)
+        const int ord = (int)a.order[(size_t)(g0 + k) * 64u + (uint32_t)lane];
+        const int my_end = (uint32_t)lane < n_seg ? (int)a.seg_end[s0 + (uint32_t)lane] : 0;
+        const int my_dst = (uint32_t)lane < n_seg ? a.seg_dst[s0 + (uint32_t)lane] : 0;
+        for (uint32_t c = 0; c < a.n_channels; c++) {
+            if (a.channel_plane[c] != (int)plane) continue;  // (wave-uniform)
+            const float g = a.gain[((size_t)k * a.n_channels + c) * a.V + v];
+            __syncthreads();  // (one wave: the reads of the tile's last use before these writes)
+#pragma unroll
+            for (int r = 0; r < kBusRows; r++) tile[r * kBusPitch + lane] = __fmul_rn(g, x[r]);
+            __syncthreads();  // (the writes before the reads)
+            if ((uint32_t)lane < n) {
+                int j = 0;
+                for (uint32_t s = 0; s < n_seg; s++) {
+                    const int end = __builtin_amdgcn_readlane(my_end, (int)s), dst = __builtin_amdgcn_readlane(my_dst, (int)s);
+                    float sum = row[__builtin_amdgcn_readlane(ord, j)];
+                    j++;
+                    for (; j + 4 <= end; j += 4) {  // four reads in flight; the additions stay in order
+                        const float x0 = row[__builtin_amdgcn_readlane(ord, j)], x1 = row[__builtin_amdgcn_readlane(ord, j + 1)];
+                        const float x2 = row[__builtin_amdgcn_readlane(ord, j + 2)], x3 = row[__builtin_amdgcn_readlane(ord, j + 3)];
+                        sum = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(sum, x0), x1), x2), x3);
+                    }
+                    for (; j < end; j++) sum = __fadd_rn(sum, row[__builtin_amdgcn_readlane(ord, j)]);
+                    if (dst >= 0) a.part[((size_t)c * a.n_partials + (uint32_t)dst) * a.part_pitch + t0 + (uint32_t)lane] = sum;
+                    else a.out[((size_t)(uint32_t)~dst * a.n_channels + c) * a.out_stride + t0 + (uint32_t)lane] = sum;
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void bus_slot_fold_sum(BusSlotFoldArgs a)
+{
+    const uint32_t n_tb = (a.T + 255u) / 256u;
+    const uint32_t bc = blockIdx.x / n_tb, t = (blockIdx.x % n_tb) * 256u + threadIdx.x;  // bc = bus * channels + channel
+    if (t >= a.T) return;
+    const uint32_t b = bc / a.n_channels, c = bc % a.n_channels;
+    const int cnt = a.channel_plane[c] < 0 ? 0 : a.bus_count[b];
+    if (cnt < 0) return;  // its one segment went straight to the bus mix
+    float s = 0.0f;
+    if (cnt > 0) {
+        const float* p = a.part + ((size_t)c * a.n_partials + a.bus_first[b]) * a.part_pitch + t;
+        s = p[0];
+        // A bus that many voices send to through a slot (an aux bus) has a row per tile: thousands, for a handful of (bus, channel)
+        // pairs — few threads, each latency-bound.  32 loads in flight per thread; the additions stay in row order.
+        int k = 1;
+        for (; k + 32 <= cnt; k += 32) {
+            float x[32];
+#pragma unroll
+            for (int i = 0; i < 32; i++) x[i] = p[(size_t)(k + i) * a.part_pitch];
+#pragma unroll
+            for (int i = 0; i < 32; i++) s = __fadd_rn(s, x[i]);
+        }
+        for (; k < cnt; k++) s = __fadd_rn(s, p[(size_t)k * a.part_pitch]);
+    }
+    a.out[(size_t)bc * a.out_stride + t] = s;
 }
 
 __global__ void fill_zero(float* p, size_t n)

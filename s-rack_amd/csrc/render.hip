@@ -177,13 +177,14 @@ struct DeviceState {
     float* d_stat_frames = nullptr;  // frames of one launch for stats_fold / the bus fold when the host asked for statistics or bus mixes without frames
     size_t stat_frames_bytes = 0;
     // mix buses: the handle's bus plan (buses.hpp) as one block of words on the device — gain, order, tile_seg, seg_end, seg_dst, bus_first,
-    // bus_count — uploaded when the table changed (bus_revision), and the fold's partials
+    // bus_count — uploaded when the table changed (bus_revision), and the fold's partials; a slot table's gains are [slot][channel][voice]
     uint32_t* d_bus_tab = nullptr;
     uint64_t bus_revision = 0;
     float* d_bus_part = nullptr;
     size_t bus_part_bytes = 0;
     bool last_bank_lds = false;  // the last render's kernel read its wave banks from LDS (srack_render_info)
     uint32_t last_buses = 0;  // bus mixes the last render filled (srack_render_info)
+    uint32_t last_slots = 0;  // ... from a slot table of that many slots (0: a table of srack_voices_set_buses)
     std::shared_ptr<const JitKernel> jit[5];  // the specialised voice kernel per output mode (1 frames, 2 mix, 3 both, 4 neither), co-owned with the cache
     bool jit_failed = false;  // specialisation was tried by default and is not available: the interpreter renders
     bool bank_lds[5] = {false, false, false, false, false};  // per output mode: the specialised kernel stages its banked players' waves in LDS
@@ -903,7 +904,15 @@ struct Segment {
         if (d->d_bus_tab && d->bus_revision == h.bus_revision) return SRACK_OK;
         std::vector<uint32_t> w;
         auto put = [&w](const void* p, size_t n) { w.insert(w.end(), (const uint32_t*)p, (const uint32_t*)p + n); };
-        put(h.bus_gain.data(), h.bus_gain.size());
+        if (h.bus_slots) {  // a slot table: the gains as [slot][channel][voice], a lane's loads of one (slot, channel) contiguous
+            const size_t K = h.bus_slots, KC = K * C;
+            std::vector<float> g(KC * V);
+            for (size_t v = 0; v < V; v++)
+                for (size_t kc = 0; kc < KC; kc++) g[kc * V + v] = h.slot_gain[v * KC + kc];
+            put(g.data(), g.size());
+        } else {
+            put(h.bus_gain.data(), h.bus_gain.size());
+        }
         put(B.order.data(), B.order.size());
         put(B.tile_seg.data(), B.tile_seg.size());
         put(B.seg_end.data(), B.seg_end.size());
@@ -919,17 +928,18 @@ struct Segment {
         return SRACK_OK;
     }
     // frames: the slab's first row (plane 0); t_at: the slab's first sample within this segment
-    BusFoldArgs bus_args(const float* frames, uint64_t plane_stride, uint32_t t_at, uint32_t rows)
+    BusSlotFoldArgs bus_args(const float* frames, uint64_t plane_stride, uint32_t t_at, uint32_t rows)
     {
         const BusPlan& B = h.bus_plan;
-        BusFoldArgs b{};
+        BusSlotFoldArgs b{};
+        b.n_slots = h.bus_slots;
         b.frames = frames;
         b.plane_stride = plane_stride;
         b.V = V;
         b.T = rows;
         const uint32_t* w = d->d_bus_tab;
         b.gain = (const float*)w;
-        b.order = (w += h.bus_gain.size());
+        b.order = (w += h.bus_slots ? h.slot_gain.size() : h.bus_gain.size());
         b.tile_seg = (w += B.order.size());
         b.seg_end = (w += B.tile_seg.size());
         b.seg_dst = (const int32_t*)(w += B.seg_end.size());
@@ -953,8 +963,9 @@ struct Segment {
         if (d_bus && (rc = bus_upload()) != SRACK_OK) return rc;
         if (P.hdr.n_planes == 0) {  // nothing reaches the output: silence (output.rs:55)
             if (d_bus) {  // no channel is connected: bus_fold_sum zeroes them all
-                const BusFoldArgs b = bus_args(nullptr, 0, 0, T);
-                hipLaunchKernelGGL(bus_fold_sum, dim3(h.n_buses * ((T + 255) / 256)), dim3(256), 0, st, b);
+                const BusSlotFoldArgs b = bus_args(nullptr, 0, 0, T);
+                if (h.bus_slots) hipLaunchKernelGGL(bus_slot_fold_sum, dim3(h.n_buses * C * ((T + 255) / 256)), dim3(256), 0, st, b);
+                else hipLaunchKernelGGL(bus_fold_sum, dim3(h.n_buses * ((T + 255) / 256)), dim3(256), 0, st, static_cast<const BusFoldArgs&>(b));
                 HIP_TRY(hipGetLastError());
             }
             if (d_mix)
@@ -1040,12 +1051,13 @@ struct Segment {
             if ((rc = grow(d->d_stat_frames, d->stat_frames_bytes, sizeof(float) * (size_t)P.hdr.n_planes * fold_rows * V)) != SRACK_OK) return rc;
         }
         if (d_bus) {
-            // The partials of one slab: [planes][n_partials][bus_slab].  A launch is folded in slabs short enough to keep them within
+            // The partials of one slab: [planes][n_partials][bus_slab] (a slot table: [channels][n_partials][bus_slab], its gains differ per
+            // channel).  A launch is folded in slabs short enough to keep them within
             // kBusPartBytes (a table that scatters every bus over every tile has as many partials as voices), but never under one 64-row tile.
             constexpr size_t kBusPartBytes = (size_t)256 << 20;
             uint32_t longest = 0;
             for (const auto& c : chunks) longest = std::max(longest, c.second);
-            const size_t per_row = sizeof(float) * (size_t)P.hdr.n_planes * std::max(1u, h.bus_plan.n_partials);
+            const size_t per_row = sizeof(float) * (size_t)(h.bus_slots ? C : (uint32_t)P.hdr.n_planes) * std::max(1u, h.bus_plan.n_partials);
             bus_slab = (uint32_t)std::min<size_t>((longest + 63u) / 64u * 64u, std::max<size_t>(64, kBusPartBytes / per_row / 64 * 64));
             if (h.bus_plan.n_partials > 0 && (rc = grow(d->d_bus_part, d->bus_part_bytes, per_row * bus_slab)) != SRACK_OK) return rc;
         }
@@ -1311,9 +1323,15 @@ struct Segment {
                 const uint32_t n_seg = (uint32_t)h.bus_plan.seg_end.size();
                 for (uint32_t r0 = 0; r0 < len; r0 += bus_slab) {
                     const uint32_t rows = std::min(bus_slab, len - r0);
-                    const BusFoldArgs b = bus_args(ka.frames + (size_t)r0 * V, ka.plane_stride, t_off + r0, rows);
-                    if (n_seg > 0) hipLaunchKernelGGL(bus_fold_tiles, dim3(h.bus_plan.n_tiles, (rows + kBusRows - 1) / kBusRows, (uint32_t)P.hdr.n_planes), dim3(64), 0, st, b);
-                    hipLaunchKernelGGL(bus_fold_sum, dim3(h.n_buses * ((rows + 255) / 256)), dim3(256), 0, st, b);
+                    const BusSlotFoldArgs b = bus_args(ka.frames + (size_t)r0 * V, ka.plane_stride, t_off + r0, rows);
+                    const dim3 slabs((V + kBusTile - 1) / kBusTile, (rows + kBusRows - 1) / kBusRows, (uint32_t)P.hdr.n_planes);  // (a slot plan's n_tiles counts groups)
+                    if (h.bus_slots) {
+                        if (n_seg > 0) hipLaunchKernelGGL(bus_slot_fold_tiles, slabs, dim3(64), 0, st, b);
+                        hipLaunchKernelGGL(bus_slot_fold_sum, dim3(h.n_buses * C * ((rows + 255) / 256)), dim3(256), 0, st, b);
+                    } else {
+                        if (n_seg > 0) hipLaunchKernelGGL(bus_fold_tiles, slabs, dim3(64), 0, st, static_cast<const BusFoldArgs&>(b));
+                        hipLaunchKernelGGL(bus_fold_sum, dim3(h.n_buses * ((rows + 255) / 256)), dim3(256), 0, st, static_cast<const BusFoldArgs&>(b));
+                    }
                     HIP_TRY(hipGetLastError());
                 }
             }
@@ -1430,6 +1448,7 @@ int device_render(PatchHandle& h, uint32_t n_samples, float* d_frames, float* d_
     for (uint32_t t = 0; t < n_samples && rc == SRACK_OK; t += kSegment)
         rc = render_segment(h, n_samples, t, std::min(kSegment, n_samples - t), d_frames, d_mix, d_stats, d_bus, flags, (hipStream_t)stream);
     if (h.dev) h.dev->last_buses = d_bus ? h.n_buses : 0u;
+    if (h.dev) h.dev->last_slots = d_bus ? h.bus_slots : 0u;
     return rc;
 }
 
@@ -1504,7 +1523,11 @@ int device_read_rows(PatchHandle& h, int ctl_stage, int first_row, int n_rows, u
 }
 
 const char* device_kernel_name(const PatchHandle& h) { return h.dev ? h.dev->kernel_name : ""; }
-std::string device_bus_note(const PatchHandle& h) { return h.dev && h.dev->last_buses ? " buses=" + std::to_string(h.dev->last_buses) + "[fold]" : std::string(); }
+std::string device_bus_note(const PatchHandle& h)
+{
+    if (!h.dev || !h.dev->last_buses) return std::string();
+    return " buses=" + std::to_string(h.dev->last_buses) + (h.dev->last_slots ? "[fold slots=" + std::to_string(h.dev->last_slots) + "]" : std::string("[fold]"));
+}
 std::string device_waves_note(const PatchHandle& h)
 {
     if (!h.prog_valid || h.prog.n_bank_waves == 0) return std::string();

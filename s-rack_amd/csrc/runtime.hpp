@@ -50,6 +50,12 @@ struct PatchHandle {
     std::vector<float> bus_gain;
     BusPlan bus_plan;
     uint64_t bus_revision = 0;
+    // One table per handle, of either kind.  A slot table (srack_voices_set_bus_slots) has bus_slots >= 1, slot_bus [n_voices][bus_slots],
+    // slot_gain [n_voices][bus_slots][channels] and a plan over groups (bus_slot_plan_make); `bus` and `bus_gain` then hold slot 0 and
+    // channel 0 of it (what srack_voices_get_buses hands out).  bus_slots 0: a table set through srack_voices_set_buses.
+    uint32_t bus_slots = 0;
+    std::vector<int32_t> slot_bus;
+    std::vector<float> slot_gain;
     Console console;                // the seven stages behind the mixer (console.hpp); dropped with the table (srack_voices_configure, another n_buses)
     bool timing_armed = false;      // srack_render_kernel_ms has been called: renders bracket the dominant kernel with HIP events
 

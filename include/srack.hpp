@@ -268,6 +268,28 @@ public:
     {
         check(srack_buses_vca(p_, n_samples, d_rows, row_channels, d_ctl, d_out, d_env, stream));
     }
+    // An LFO per mix bus writes the console's control rows: params f32 [n_buses][SRACK_BUS_OSC_NPARAMS] = val, depth, offset (any f32; nullptr:
+    // 0, 1, 0), port [n_buses] SRACK_OSC_OUT_* (nullptr: sine), antialiasing [n_buses] (nullptr: true), enabled [n_buses] (nullptr: all).  The
+    // reference's oscillator bit for bit, times depth, plus offset.  Calling set_bus_osc again is the slider: state stays; a bus that becomes
+    // enabled starts fresh.  Not part of the program.
+    void set_bus_osc(const float* params = nullptr, const int* port = nullptr, const int* antialiasing = nullptr, const int* enabled = nullptr)
+    {
+        check(srack_buses_set_osc(p_, params, port, antialiasing, enabled));
+    }
+    uint32_t get_bus_osc(float* params = nullptr, int* port = nullptr, int* antialiasing = nullptr, int* enabled = nullptr, uint32_t cap = 0) const
+    {
+        return (uint32_t)check(srack_buses_get_osc(p_, params, port, antialiasing, enabled, cap));
+    }
+    // every state fresh (phase 0, last true), or bus b at phase pos[b] in [0, 1) (f64 [n_buses], host; not -0.0); the setting stays
+    void reset_bus_osc(const double* pos = nullptr) { check(srack_buses_reset_osc(p_, pos)); }
+    // state f64 [n_buses][SRACK_BUS_OSC_NSTATE] (host): phase and last (0.0 / 1.0), behind a wait for the last call; a disabled bus reads fresh
+    uint32_t bus_osc_state(double* state = nullptr, uint32_t cap = 0) { return (uint32_t)check(srack_buses_osc_state(p_, state, cap)); }
+    // d_cv, d_sync f32 [n_buses][n_samples] or null (unconnected) -> d_out f32 [n_buses][n_samples], disjoint from both: what bus_filter's
+    // d_cv, bus_vca's d_ctl and bus_shaper's d_cv take.  A disabled bus's row is +0.0f.  Asynchronous on `stream`.
+    void bus_osc(uint32_t n_samples, const float* d_cv, const float* d_sync, float* d_out, void* stream = nullptr)
+    {
+        check(srack_buses_osc(p_, n_samples, d_cv, d_sync, d_out, stream));
+    }
     // A drive, a waveshaper and a make-up gain per mix bus, behind the mixer: params f32 [n_buses][SRACK_BUS_SHAPER_NPARAMS] = pre, exponent,
     // post (any f32; nullptr: 1, 1, 1), mode [n_buses] SRACK_BUS_SHAPER_* (nullptr: every bus CONST).  sign(a) |a|^e with the host libm's powf,
     // bit for bit.  Calling set_bus_shaper again is the slider; there is no state.  Not part of the program.

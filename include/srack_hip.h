@@ -750,6 +750,65 @@ int srack_buses_vca_state(srack_patch* p, float* state /* host, f32 [n_buses][SR
 int srack_buses_vca(srack_patch* p, uint32_t n_samples, const float* d_rows, uint32_t row_channels,
                     const float* d_ctl, float* d_out, float* d_env, void* stream);
 
+/* ---- the bus oscillators: an LFO per mix bus writes the console's control rows -------------------------------------------------------
+ * What makes the rows that move a strip: the filters' d_cv, the VCAs' d_ctl (a gate or a CV), the shapers' d_cv — sweeps, tremolos and
+ * gate clocks made on the device instead of uploaded.  On the samples of a call every enabled bus runs three reference modules in
+ * series, ticked once per sample:
+ *   OscillatorModule       (oscillator.rs:108-157) CV = d_cv[b][t], Sync = d_sync[b][t]; val = VAL, antialiasing[b]; output port[b]
+ *   MathModule(Multiply)   In1 = that output, In2 unconnected, constant = DEPTH   (math.rs:150-155: a * constant)
+ *   MathModule(Add)        In1 = that product, In2 unconnected, constant = OFFSET -> d_out[b][t]
+ * The oscillator is the reference's own operation sequence, whatever mode the patch renders in (the console has no approximations):
+ * pos += delta; pos %= 1.0 in f64; delta = 440 * 2^(f64(cv) + f64(val)) / f64(sample_rate) with the host libm's pow; the sine
+ * (pos * PI * 2.0).sin() as f32 with the host libm's sin; square and saw with poly_blep in f64 as spelled; the TransitionDetector on
+ * sync > 0.0, its `last` starting TRUE (a sync row whose first sample is high resets nothing).  The two Math operations are IEEE f32,
+ * one rounding each, no fma, and they ALWAYS run: with the defaults DEPTH 1 and OFFSET 0 a -0.0 of the oscillator comes out as +0.0
+ * (-0.0 * 1 = -0.0, -0.0 + 0.0 = +0.0), as the modules would make it.
+ * d_cv == NULL: the CV port is unconnected (2^f64(val)) — the same bits as a row of +0.0f.  d_sync == NULL: sync_val = 0.0, never a
+ * transition, and `last` becomes false.  ANY f32 is accepted for VAL, DEPTH, OFFSET and the rows; a non-finite value affects that bus's
+ * row and no other.  The sample rate is the patch's, as f64.
+ *
+ * params:       f32 [n_buses][SRACK_BUS_OSC_NPARAMS] = VAL, DEPTH, OFFSET; NULL = 0, 1, 0
+ * port:         int [n_buses], SRACK_OSC_OUT_*; NULL = Sine.  A port outside 0..2 is SRACK_ERR_INVALID and leaves the earlier setting
+ *               in place.
+ * antialiasing: int [n_buses], non-zero = true; NULL = true
+ * enabled:      int [n_buses], non-zero = the bus has an oscillator; NULL = all
+ * All four are host memory.
+ * Lifecycle (the VCAs' rules): calling set_osc again is the slider — parameters, ports and flags change, state stays.  A bus that
+ * becomes enabled starts fresh; a bus that leaves drops its state.  get_osc copies up to cap buses (any pointer may be NULL) and returns
+ * n_buses, or 0 when no oscillators are set.  reset_osc(NULL) makes every state fresh — phase 0.0, last TRUE, as OscillatorModule::new —
+ * and keeps the setting; reset_osc(pos) with pos f64 [n_buses] (host) starts bus b at phase pos[b], the phase a rack file would carry:
+ * quadrature LFOs, a spread per strip.  Every pos[b] must be in [0, 1): anything else — NaN, 1.0, a negative number, and -0.0, which no
+ * `pos %= 1.0` of non-negative numbers produces and whose wrap is not +0.0's — is SRACK_ERR_INVALID, and nothing is reset.  osc_state
+ * waits for the last call and copies up to cap buses of state — per bus SRACK_OSC_POS and SRACK_OSC_SYNC_LAST (0.0 / 1.0) as f64; a
+ * disabled bus reads fresh (0.0, 1.0) — and returns n_buses.  The state lives on the device between calls: no bit depends on how the
+ * samples are cut into calls (the held-CV cache of the kernel is not state: every call starts with it empty).
+ * The oscillators belong to the handle, NOT to the patch's program, exactly as the VCAs: setting, changing or running them does not
+ * re-flatten, restarts nothing and changes no bit of any other output; they survive an edit that re-flattens the patch.
+ * srack_voices_configure drops them; so does srack_voices_set_buses with another n_buses (the same n_buses keeps them).  Rack files
+ * carry nothing of this.
+ *
+ * The call:
+ *   d_cv   : device, f32 [n_buses][n_samples], or NULL
+ *   d_sync : device, f32 [n_buses][n_samples], or NULL
+ *   d_out  : device, f32 [n_buses][n_samples], written: the shape of srack_buses_filter's d_cv, srack_buses_vca's d_ctl and
+ *            srack_buses_shaper's d_cv.  A disabled bus's row is written as +0.0f, the convention of srack_buses_vca's d_env.
+ *   d_out must not overlap d_cv or d_sync (SRACK_ERR_INVALID).  Any 4-byte aligned address is accepted for all three.
+ *   stream : as for srack_buses_vca: asynchronous, and the library touches the stream only during the call.
+ * Errors, in this order: SRACK_ERR_INVALID for a null handle; SRACK_ERR_STATE before srack_voices_configure or before a mix table
+ * exists (all five calls); SRACK_ERR_STATE for srack_buses_osc, reset_osc and osc_state before set_osc; n_samples == 0 is SRACK_OK and
+ * touches nothing; SRACK_ERR_INVALID for a null d_out or an overlap as above; SRACK_ERR_NOMEM if state and table cannot be allocated.
+ * The kernel takes a lane per enabled bus, a wave of 64 buses per workgroup, tiles of 64 buses x 64 samples of the CV and sync rows
+ * turned through LDS, the state in registers for the call (csrc/busosc.hip.h); without a CV row the increment is computed once per bus
+ * on the host.  srack_render_info says " busosc=<enabled>[<cv|-><sync|->]" in front of " busvcf=" once a call has run. */
+#define SRACK_BUS_OSC_NPARAMS 3
+enum { SRACK_BUS_OSC_VAL = 0, SRACK_BUS_OSC_DEPTH = 1, SRACK_BUS_OSC_OFFSET = 2 };
+#define SRACK_BUS_OSC_NSTATE 2   /* SRACK_OSC_POS, SRACK_OSC_SYNC_LAST (0.0 / 1.0), as f64 */
+int srack_buses_set_osc(srack_patch* p, const float* params, const int* port, const int* antialiasing, const int* enabled);
+int srack_buses_get_osc(const srack_patch* p, float* params, int* port, int* antialiasing, int* enabled, uint32_t cap);
+int srack_buses_reset_osc(srack_patch* p, const double* pos);
+int srack_buses_osc_state(srack_patch* p, double* state /* host, f64 [n_buses][2] */, uint32_t cap);
+int srack_buses_osc(srack_patch* p, uint32_t n_samples, const float* d_cv, const float* d_sync, float* d_out, void* stream);
+
 /* ---- the bus shapers: a drive, a waveshaper and a make-up gain per mix bus, behind the mixer ---------------------------------------
  * The non-linearity of a strip: saturating a drum group, expanding an aux bus, riding the curve from an automation row.  A shaper on
  * the sum is not the sum of shapers, so no patch can stand in for it.  Channel c in {0, 1} of a bus that is not OFF is three reference

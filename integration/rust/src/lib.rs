@@ -92,6 +92,11 @@ mod ffi {
         pub fn srack_buses_reset_vca(p: *mut SrackPatch) -> c_int;
         pub fn srack_buses_vca_state(p: *mut SrackPatch, state: *mut f32, cap: u32) -> c_int;
         pub fn srack_buses_vca(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_ctl: *const f32, d_out: *mut f32, d_env: *mut f32, stream: *mut c_void) -> c_int;
+        pub fn srack_buses_set_osc(p: *mut SrackPatch, params: *const f32, port: *const c_int, antialiasing: *const c_int, enabled: *const c_int) -> c_int;
+        pub fn srack_buses_get_osc(p: *const SrackPatch, params: *mut f32, port: *mut c_int, antialiasing: *mut c_int, enabled: *mut c_int, cap: u32) -> c_int;
+        pub fn srack_buses_reset_osc(p: *mut SrackPatch, pos: *const f64) -> c_int;
+        pub fn srack_buses_osc_state(p: *mut SrackPatch, state: *mut f64, cap: u32) -> c_int;
+        pub fn srack_buses_osc(p: *mut SrackPatch, n_samples: u32, d_cv: *const f32, d_sync: *const f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
         pub fn srack_buses_set_shaper(p: *mut SrackPatch, params: *const f32, mode: *const c_int) -> c_int;
         pub fn srack_buses_get_shaper(p: *const SrackPatch, params: *mut f32, mode: *mut c_int, cap: u32) -> c_int;
         pub fn srack_buses_shaper(p: *mut SrackPatch, n_samples: u32, d_rows: *const f32, row_channels: u32, d_cv: *const f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
@@ -601,6 +606,48 @@ impl Patch {
         let o = out.map_or(rows.as_f32(), |b| b.as_f32());
         let e = env.map_or(std::ptr::null_mut(), |b| b.as_f32());
         check(unsafe { ffi::srack_buses_vca(self.raw, n_samples, rows.as_f32() as *const f32, row_channels, c, o, e, std::ptr::null_mut()) }).map(|_| ())
+    }
+    /// An LFO per mix bus writes the console's control rows (`srack_buses_set_osc`): `params` is `[n_buses][3]` f32 — val (1 V/oct, 0 is
+    /// 440 Hz), depth, offset, any f32; None: 0, 1, 0 —, `port` `[n_buses]` 0 sine, 1 square, 2 sawtooth (None: sine), `antialiasing`
+    /// `[n_buses]` (None: true), `enabled` `[n_buses]` (None: all).  The reference's oscillator bit for bit, times depth, plus offset.
+    /// Calling it again is the slider: state stays; a bus that becomes enabled starts fresh.  Not part of the program: restarts nothing.
+    pub fn set_bus_osc(&mut self, params: Option<&[f32]>, port: Option<&[i32]>, antialiasing: Option<&[i32]>, enabled: Option<&[i32]>) -> Result<(), Error> {
+        let a = params.map_or(std::ptr::null(), |x| x.as_ptr());
+        let po = port.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        let aa = antialiasing.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        let e = enabled.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_int);
+        check(unsafe { ffi::srack_buses_set_osc(self.raw, a, po, aa, e) }).map(|_| ())
+    }
+    /// `(params [n_buses][3], port [n_buses], antialiasing [n_buses], enabled [n_buses])` of the oscillators set; None when none are.
+    pub fn get_bus_osc(&self) -> Result<Option<(Vec<f32>, Vec<i32>, Vec<i32>, Vec<i32>)>, Error> {
+        let null = std::ptr::null_mut::<c_int>();
+        let n = check(unsafe { ffi::srack_buses_get_osc(self.raw, std::ptr::null_mut(), null, null, null, 0) })? as usize;
+        if n == 0 {
+            return Ok(None);
+        }
+        let (mut a, mut po, mut aa, mut e) = (vec![0f32; n * 3], vec![0 as c_int; n], vec![0 as c_int; n], vec![0 as c_int; n]);
+        check(unsafe { ffi::srack_buses_get_osc(self.raw, a.as_mut_ptr(), po.as_mut_ptr(), aa.as_mut_ptr(), e.as_mut_ptr(), n as u32) })?;
+        Ok(Some((a, po, aa, e)))
+    }
+    /// Every oscillator's state fresh (phase 0, the sync detector armed as at `new()`), or, with `pos` `[n_buses]` f64, each in `[0, 1)`
+    /// and not -0.0, bus b at phase `pos[b]`; the setting stays.
+    pub fn reset_bus_osc(&mut self, pos: Option<&[f64]>) -> Result<(), Error> {
+        check(unsafe { ffi::srack_buses_reset_osc(self.raw, pos.map_or(std::ptr::null(), |x| x.as_ptr())) }).map(|_| ())
+    }
+    /// The oscillators' state behind the last call, `[n_buses][2]` f64: phase, sync last (0.0 / 1.0); a disabled bus reads fresh (0, 1).
+    pub fn bus_osc_state(&mut self) -> Result<Vec<f64>, Error> {
+        let n = check(unsafe { ffi::srack_buses_osc_state(self.raw, std::ptr::null_mut(), 0) })? as usize;
+        let mut st = vec![0f64; n * 2];
+        check(unsafe { ffi::srack_buses_osc_state(self.raw, st.as_mut_ptr(), n as u32) })?;
+        Ok(st)
+    }
+    /// `n_samples` of every bus's oscillator (`srack_buses_osc`): `cv` and `sync` `[n_buses][n_samples]` f32 (None: the port is
+    /// unconnected), `out` `[n_buses][n_samples]` f32 written — what `bus_filter`'s `cv`, `bus_vca`'s `ctl` and `bus_shaper`'s `cv` take.
+    /// A disabled bus's row is +0.0.
+    pub fn bus_osc(&mut self, n_samples: u32, cv: Option<&DeviceBuffer>, sync: Option<&DeviceBuffer>, out: &DeviceBuffer) -> Result<(), Error> {
+        let c = cv.map_or(std::ptr::null(), |b| b.as_f32() as *const f32);
+        let g = sync.map_or(std::ptr::null(), |b| b.as_f32() as *const f32);
+        check(unsafe { ffi::srack_buses_osc(self.raw, n_samples, c, g, out.as_f32(), std::ptr::null_mut()) }).map(|_| ())
     }
     /// A drive, a waveshaper and a make-up gain per mix bus, behind the mixer (`srack_buses_set_shaper`): `params` is `[n_buses][3]` f32 —
     /// pre, exponent, post, any f32; None: 1, 1, 1 —, `mode` `[n_buses]` 0 off, 1 the exponent is the constant, 2 it is the bus's CV row

@@ -26,6 +26,9 @@ BUS_FILTER_DEFAULTS = (0.2, 0.5, 0.5)  # MoogFilterModule's three sliders: what 
 BUS_VCA_NPARAMS, BUS_VCA_NSTATE = 4, 6  # srack_buses_set_vca: ADSR_A_SEC .. ADSR_R_SEC per bus; srack_buses_vca_state: ADSR_PHASE .. ADSR_GATE_LAST per bus
 BUS_VCA_OFF, BUS_VCA_CV, BUS_VCA_GATE = 0, 1, 2  # a bus's mode: it passes; its control row is the VCAs' CV; it is the gate of the bus's ADSR
 BUS_VCA_DEFAULTS = (0.0, 0.5, 0.25, 0.5)  # ADSRModule's four sliders: what set_bus_vca(None) gives every bus
+BUS_OSC_NPARAMS, BUS_OSC_NSTATE = 3, 2  # srack_buses_set_osc: VAL, DEPTH, OFFSET per bus; srack_buses_osc_state: OSC_POS, OSC_SYNC_LAST per bus, as f64
+BUS_OSC_VAL, BUS_OSC_DEPTH, BUS_OSC_OFFSET = 0, 1, 2
+BUS_OSC_DEFAULTS = (0.0, 1.0, 0.0)  # the oscillator's val, a gain of 1, an offset of 0: what set_bus_osc(None) gives every bus
 BUS_SHAPER_NPARAMS = 3  # srack_buses_set_shaper: PRE, EXPONENT, POST per bus
 BUS_SHAPER_PRE, BUS_SHAPER_EXPONENT, BUS_SHAPER_POST = 0, 1, 2
 BUS_SHAPER_OFF, BUS_SHAPER_CONST, BUS_SHAPER_CV = 0, 1, 2  # a bus's mode: it passes; the exponent is EXPONENT; the exponent is the bus's CV row
@@ -55,6 +58,7 @@ ABI_SYMBOLS = [
     "srack_buses_set_vca", "srack_buses_get_vca", "srack_buses_reset_vca", "srack_buses_vca_state", "srack_buses_vca",
     "srack_buses_set_shaper", "srack_buses_get_shaper", "srack_buses_shaper",
     "srack_buses_meter",
+    "srack_buses_set_osc", "srack_buses_get_osc", "srack_buses_reset_osc", "srack_buses_osc_state", "srack_buses_osc",
     "srack_patch_set_wave_bank", "srack_patch_get_wave_bank", "srack_patch_get_wave_bank_samples", "srack_voices_set_waves", "srack_voices_get_waves",
     "srack_patch_set_sequence_bank", "srack_patch_get_sequence_bank", "srack_voices_set_sequences", "srack_voices_get_sequences",
     "srack_render_info", "srack_render_kernel_source", "srack_render_kernel_compile", "srack_render_kernel_ms", "srack_voices_get_field", "srack_kernel_cache_set_dir", "srack_kernel_cache_stats", "srack_device_count", "srack_device_set", "srack_device_get",
@@ -162,6 +166,12 @@ def _load():
         L.srack_buses_shaper.argtypes = [vp, u32, vp, u32, vp, vp, vp]
     if hasattr(L, "srack_buses_meter"):
         L.srack_buses_meter.argtypes = [vp, C.c_uint64, u32, vp, u32, u32, vp, u32, vp, vp]
+    if hasattr(L, "srack_buses_osc"):
+        L.srack_buses_set_osc.argtypes = [vp, fp, ip, ip, ip]
+        L.srack_buses_get_osc.argtypes = [vp, fp, ip, ip, ip, u32]
+        L.srack_buses_reset_osc.argtypes = [vp, dp]
+        L.srack_buses_osc_state.argtypes = [vp, dp, u32]
+        L.srack_buses_osc.argtypes = [vp, u32, vp, vp, vp, vp]
     if hasattr(L, "srack_voices_set_waves"):  # (tools/ alternate older builds of the library under this binding)
         L.srack_patch_set_wave_bank.argtypes = [vp, i32, fp, ip, fp, u32]
         L.srack_patch_get_wave_bank.argtypes = [vp, i32, ip, fp, u32]
@@ -854,6 +864,63 @@ class Patch:
         channels beyond the second come back as; in place they come back as they went in."""
         out, env = self._bus_stage(self.bus_vca_raw, rows, ctl, in_place, env=bool(want_env))
         return (out, env) if want_env else out
+
+    # ---- bus oscillators: an LFO per mix bus writes the console's control rows ------------------------------
+    def set_bus_osc(self, params=None, port=None, antialiasing=None, enabled=None):
+        """srack_buses_set_osc: params f32 [n_buses][3] = VAL, DEPTH, OFFSET, any f32 (None: 0, 1, 0), port int [n_buses] OSC_OUT_*
+        (None: sine), antialiasing [n_buses] (None: true), enabled [n_buses] (None: every bus).  Calling it again is the slider:
+        parameters, ports and flags change, state stays; a bus that becomes enabled starts fresh.  Not part of the program: restarts nothing."""
+        n_buses = self.n_buses()
+        _, a = _opt(params, np.float32, (n_buses, BUS_OSC_NPARAMS))
+        _, po = _opt(port, np.intc, (n_buses,))
+        _, aa = _opt(_truth(antialiasing), np.intc, (n_buses,))
+        _, e = _opt(_truth(enabled), np.intc, (n_buses,))
+        _check(lib.srack_buses_set_osc(self.h, a, po, aa, e))
+
+    def get_bus_osc(self):
+        """-> (n_buses, params f32 [n_buses][3], port int32 [n_buses], antialiasing int32 [n_buses], enabled int32 [n_buses]);
+        (0, None, None, None, None) when no oscillators are set"""
+        n = _check(lib.srack_buses_get_osc(self.h, None, None, None, None, 0))
+        if n == 0:
+            return 0, None, None, None, None
+        a, po, aa, e = np.empty((n, BUS_OSC_NPARAMS), dtype=np.float32), np.empty(n, dtype=np.intc), np.empty(n, dtype=np.intc), np.empty(n, dtype=np.intc)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        _check(lib.srack_buses_get_osc(self.h, a.ctypes.data_as(fp), po.ctypes.data_as(ip), aa.ctypes.data_as(ip), e.ctypes.data_as(ip), n))
+        return n, a, po, aa, e
+
+    def reset_bus_osc(self, pos=None):
+        """Every oscillator's state fresh — phase 0.0, last true — or, with pos f64 [n_buses], each in [0, 1) and not -0.0, bus b at phase
+        pos[b]; the setting stays (srack_buses_reset_osc)."""
+        _, ph = _opt(pos, np.float64, (self.n_buses(),))
+        _check(lib.srack_buses_reset_osc(self.h, ph))
+
+    def bus_osc_state(self):
+        """-> f64 [n_buses][BUS_OSC_NSTATE]: OSC_POS and OSC_SYNC_LAST (0.0 / 1.0) per bus behind the last call, a disabled bus as the fresh
+        state (0.0, 1.0) (srack_buses_osc_state)"""
+        n = _check(lib.srack_buses_osc_state(self.h, None, 0))
+        st = np.zeros((n, BUS_OSC_NSTATE), dtype=np.float64)
+        _check(lib.srack_buses_osc_state(self.h, st.ctypes.data_as(C.POINTER(C.c_double)), n))
+        return st
+
+    def bus_osc_raw(self, n_samples, d_cv, d_sync, d_out, stream=None):
+        """Device pointers in; asynchronous on `stream` (srack_buses_osc): d_cv and d_sync f32 [n_buses][n] or None, d_out f32 [n_buses][n]."""
+        _check(lib.srack_buses_osc(self.h, n_samples, d_cv, d_sync, d_out, stream))
+
+    def bus_osc(self, n_samples, cv=None, sync=None):
+        """Convenience for tests: n_samples of every bus's oscillator (cv and sync f32 [n_buses][n_samples] from the host, or None: the
+        port is unconnected) -> f32 [n_buses][n_samples]."""
+        n_buses = self.n_buses()
+        c, _ = _opt(cv, np.float32, (n_buses, n_samples))
+        g, _ = _opt(sync, np.float32, (n_buses, n_samples))
+        out = np.zeros((n_buses, n_samples), dtype=np.float32)
+        if n_samples == 0:
+            return out
+        with DeviceScope() as dev:
+            d_cv, d_sync = (None if x is None else dev.upload(x) for x in (c, g))
+            d_out = dev.upload(out)
+            self.bus_osc_raw(n_samples, d_cv, d_sync, d_out, None)
+            dev.download(out, d_out)
+        return out
 
     # ---- bus shapers: a drive, a waveshaper and a make-up gain per mix bus, behind the mixer ----------------
     def set_bus_shaper(self, params=None, mode=None):

@@ -1439,6 +1439,109 @@ int srack_buses_vca(srack_patch* p, uint32_t n_samples, const float* d_rows, uin
     });
 }
 
+// ---- the bus oscillators ---------------------------------------------------------------------------------------------
+static const float kBusOscDefaults[SRACK_BUS_OSC_NPARAMS] = {0.0f, 1.0f, 0.0f};  // OscillatorModule::new's val; a gain of 1, an offset of 0
+
+int srack_buses_set_osc(srack_patch* p, const float* params, const int* port, const int* antialiasing, const int* enabled)
+{
+    return guarded([&]() -> int {
+        int rc = console_preamble(p, "buses_set_osc");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        BusOsc& F = h.console.busosc;
+        const size_t n = h.n_buses;
+        for (size_t b = 0; port && b < n; b++)
+            if (port[b] < SRACK_OSC_OUT_SINE || port[b] > SRACK_OSC_OUT_SAW) {
+                set_error("buses_set_osc: bus " + std::to_string(b) + " asks for port " + std::to_string(port[b]) + ": an oscillator has sine (0), square (1) and sawtooth (2)");
+                return SRACK_ERR_INVALID;
+            }
+        // (built aside: a failure leaves the earlier setting in place)
+        std::vector<float> par(n * SRACK_BUS_OSC_NPARAMS);
+        std::vector<int32_t> po(n, SRACK_OSC_OUT_SINE);
+        std::vector<uint8_t> aa(n, 1), en(n, 1);
+        for (size_t b = 0; b < n; b++) {
+            for (int f = 0; f < SRACK_BUS_OSC_NPARAMS; f++) par[b * SRACK_BUS_OSC_NPARAMS + f] = kBusOscDefaults[f];
+            if (port) po[b] = port[b];
+            if (antialiasing) aa[b] = antialiasing[b] != 0;
+            if (enabled) en[b] = enabled[b] != 0;
+        }
+        if (params) std::memcpy(par.data(), params, sizeof(float) * par.size());  // bit for bit
+        if ((rc = device_busosc_enable(h, en)) != SRACK_OK) return rc;  // a bus that becomes enabled starts fresh, one that leaves drops its state
+        F.params = std::move(par);
+        F.port = std::move(po);
+        F.aa = std::move(aa);
+        F.enabled = std::move(en);
+        F.rate = (double)h.graph.cfg.sample_rate;
+        F.set = true;
+        device_busosc_changed(h);  // the sliders: the table goes up again, the state stays
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_get_osc(const srack_patch* p, float* params, int* port, int* antialiasing, int* enabled, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        const int rc = console_preamble(p, "buses_get_osc");
+        if (rc != SRACK_OK) return rc;
+        const PatchHandle& h = p->h;
+        const BusOsc& F = h.console.busosc;
+        if (!F.set) return 0;
+        const size_t n = std::min<size_t>(cap, h.n_buses);
+        if (params && n) std::memcpy(params, F.params.data(), sizeof(float) * n * SRACK_BUS_OSC_NPARAMS);
+        for (size_t b = 0; port && b < n; b++) port[b] = F.port[b];
+        for (size_t b = 0; antialiasing && b < n; b++) antialiasing[b] = F.aa[b];
+        for (size_t b = 0; enabled && b < n; b++) enabled[b] = F.enabled[b];
+        return (int)h.n_buses;
+    });
+}
+
+int srack_buses_reset_osc(srack_patch* p, const double* pos)
+{
+    return guarded([&]() -> int {
+        int rc = console_preamble(p, "buses_reset_osc");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        if ((rc = need_set(h.console.busosc.set, "buses_reset_osc", "oscillators", "osc")) != SRACK_OK) return rc;
+        for (size_t b = 0; pos && b < h.n_buses; b++)
+            if (!(pos[b] >= 0.0 && pos[b] < 1.0) || std::signbit(pos[b])) {  // (a NaN fails both compares; -0.0 passes them)
+                set_error("buses_reset_osc: bus " + std::to_string(b) + " asks for phase " + std::to_string(pos[b]) + ": a phase is in [0, 1), and not -0.0");
+                return SRACK_ERR_INVALID;
+            }
+        device_busosc_reset(h, pos);
+        return SRACK_OK;
+    });
+}
+
+int srack_buses_osc_state(srack_patch* p, double* state, uint32_t cap)
+{
+    return guarded([&]() -> int {
+        int rc = console_preamble(p, "buses_osc_state");
+        if (rc != SRACK_OK) return rc;
+        if ((rc = need_set(p->h.console.busosc.set, "buses_osc_state", "oscillators", "osc")) != SRACK_OK) return rc;
+        if (state && cap && (rc = device_busosc_state(p->h, state, cap)) != SRACK_OK) return rc;
+        return (int)p->h.n_buses;
+    });
+}
+
+int srack_buses_osc(srack_patch* p, uint32_t n_samples, const float* d_cv, const float* d_sync, float* d_out, void* stream)
+{
+    return guarded([&]() -> int {
+        int rc = console_preamble(p, "buses_osc");
+        if (rc != SRACK_OK) return rc;
+        PatchHandle& h = p->h;
+        if ((rc = need_set(h.console.busosc.set, "buses_osc", "oscillators", "osc")) != SRACK_OK) return rc;
+        if (n_samples == 0) return SRACK_OK;
+        if (!d_out) {
+            set_error("buses_osc: d_out must be given");
+            return SRACK_ERR_INVALID;
+        }
+        const uint64_t row_bytes = 4ull * h.n_buses * n_samples;
+        if ((rc = need_apart("buses_osc", "d_cv", d_cv, row_bytes, "d_out", d_out, row_bytes)) != SRACK_OK) return rc;
+        if ((rc = need_apart("buses_osc", "d_sync", d_sync, row_bytes, "d_out", d_out, row_bytes)) != SRACK_OK) return rc;
+        return device_buses_osc(h, n_samples, d_cv, d_sync, d_out, stream);
+    });
+}
+
 // ---- the bus shapers -------------------------------------------------------------------------------------------------
 static const float kBusShaperDefaults[SRACK_BUS_SHAPER_NPARAMS] = {1.0f, 1.0f, 1.0f};  // pre, exponent (NonLinearModule::new's constant), post
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -695,9 +696,169 @@ static std::string busmeter_note(const BusMeter& F)
     return F.ran ? " meter=" + std::to_string(F.last_buses) + "[w" + (F.last_window ? std::to_string(F.last_window) : std::string("-")) + "]" : std::string();
 }
 
-// ---- the seven together -------------------------------------------------------------------------------------------------------------
+// ---- the bus oscillators (busosc.hip.h, launched through launch_bus_osc) ---------------------------------------------------------------
+// Two state values per bus, in bus order: nothing is compacted, so a change of the enabled set moves nothing.  The table has an entry per
+// enabled bus, ordered by (port, antialiasing) so that a wave's lanes share a class wherever they can, and the list of the disabled
+// buses behind it.  The table goes up again after a change of the setting, the state after a change of the enabled set or a reset —
+// both behind a host-side wait for the last call's kernel, which may still be using them.  A tick session of unchanged oscillators is
+// the launch and one event per call.
+
+// OscillatorModule::new's state, f64 [2][n]: pos 0.0, TransitionDetector.last true
+static std::vector<double> busosc_fresh(size_t n)
+{
+    std::vector<double> s((size_t)kBusOscFields * n, 0.0);
+    std::fill(s.begin() + n, s.end(), 1.0);
+    return s;
+}
+
+static bool busosc_all_fresh(const BusOsc& F) { return F.pending.empty() && (!F.d_state.p || F.fresh); }
+
+// The state as it stands, f64 [2][n]
+static int busosc_fetch(BusOsc& F, size_t n, std::vector<double>& out)
+{
+    if (!F.pending.empty()) {
+        out = F.pending;
+        return SRACK_OK;
+    }
+    out = busosc_fresh(n);
+    if (busosc_all_fresh(F)) return SRACK_OK;
+    F.sync.wait();
+    HIP_TRY(hipMemcpy(out.data(), F.d_state.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost));
+    return SRACK_OK;
+}
+
+void device_busosc_changed(PatchHandle& h) { h.console.busosc.tab_dirty = true; }
+
+void device_busosc_reset(PatchHandle& h, const double* pos)
+{
+    BusOsc& F = h.console.busosc;
+    F.pending.clear();
+    F.fresh = true;  // uploaded before the next call's kernel
+    if (!pos) return;
+    const size_t n = h.n_buses;
+    F.pending = busosc_fresh(n);
+    for (size_t b = 0; b < n; b++)
+        if (F.enabled[b]) F.pending[b] = pos[b];  // (a disabled bus holds the fresh state)
+    F.fresh = false;
+}
+
+int device_busosc_enable(PatchHandle& h, const std::vector<uint8_t>& enabled)
+{
+    BusOsc& F = h.console.busosc;
+    if (!F.set || busosc_all_fresh(F)) return SRACK_OK;  // fresh stays fresh
+    const size_t n = h.n_buses;
+    bool moved = false;
+    for (size_t b = 0; b < n; b++) moved = moved || ((F.enabled[b] != 0) != (enabled[b] != 0));
+    if (!moved) return SRACK_OK;
+    std::vector<double> cur;
+    const int rc = busosc_fetch(F, n, cur);
+    if (rc != SRACK_OK) return rc;
+    for (size_t b = 0; b < n; b++)  // a bus that stays enabled keeps its state; one that becomes enabled starts fresh; one that leaves drops it
+        if (!F.enabled[b] || !enabled[b]) cur[b] = 0.0, cur[n + b] = 1.0;
+    F.pending = std::move(cur);
+    return SRACK_OK;
+}
+
+int device_busosc_state(PatchHandle& h, double* state, uint32_t cap)
+{
+    BusOsc& F = h.console.busosc;
+    const size_t n_buses = h.n_buses, n = std::min<size_t>(cap, n_buses);
+    std::vector<double> cur;
+    const int rc = busosc_fetch(F, n_buses, cur);
+    if (rc != SRACK_OK) return rc;
+    for (size_t b = 0; b < n; b++) {
+        state[b * kBusOscFields + 0] = F.enabled[b] ? cur[b] : 0.0;
+        state[b * kBusOscFields + 1] = F.enabled[b] ? cur[n_buses + b] : 1.0;
+    }
+    return SRACK_OK;
+}
+
+static void busosc_drop(BusOsc& F)
+{
+    F.sync.wait();
+    F.d_state.release();
+    F.d_tab.release();
+    F.sync.destroy();
+    F = BusOsc();
+}
+
+int device_buses_osc(PatchHandle& h, uint32_t n_samples, const float* d_cv, const float* d_sync, float* d_out, void* stream)
+{
+    BusOsc& F = h.console.busosc;
+    const uint32_t n_buses = h.n_buses;
+    int rc;
+    if ((rc = F.sync.begin(stream)) != SRACK_OK) return rc;
+    const size_t state_bytes = sizeof(double) * kBusOscFields * n_buses;
+    const size_t tab_bytes = sizeof(BusOscBus) * n_buses + sizeof(uint32_t) * n_buses;  // (n_on + n_off = n_buses, and an entry is the larger)
+    if (!F.d_state.p || !F.d_tab.p) {  // (n_buses is fixed while the oscillators live: another n_buses drops them)
+        if ((rc = F.d_state.grow(F.sync, state_bytes, "buses_osc", "the oscillators' state")) != SRACK_OK) return rc;
+        if ((rc = F.d_tab.grow(F.sync, tab_bytes, "buses_osc", "the oscillators' table")) != SRACK_OK) return rc;
+        F.tab_dirty = true;
+        if (F.pending.empty()) F.fresh = true;
+    }
+    if (!F.pending.empty() || F.fresh) {
+        const std::vector<double> up = F.pending.empty() ? busosc_fresh(n_buses) : F.pending;
+        F.sync.wait();
+        HIP_TRY(hipMemcpy(F.d_state.p, up.data(), state_bytes, hipMemcpyHostToDevice));
+        F.pending.clear();
+        F.fresh = false;
+    }
+    if (F.tab_dirty) {
+        std::vector<BusOscBus> tab;
+        std::vector<uint32_t> off;
+        tab.reserve(n_buses);
+        for (int cls = 0; cls < 6; cls++)  // (port, antialiasing), each class in bus order
+            for (uint32_t b = 0; b < n_buses; b++) {
+                if (!F.enabled[b] || F.port[b] * 2 + (F.aa[b] ? 1 : 0) != cls) continue;
+                const float val = F.params[(size_t)b * SRACK_BUS_OSC_NPARAMS + SRACK_BUS_OSC_VAL];
+                BusOscBus r;
+                r.delta = 440.0 * std::pow(2.0, (double)val) / F.rate;  // get_freq_in_hz(None) / f64(sample_rate), oscillator.rs:46,132
+                r.val = (double)val;
+                r.depth = F.params[(size_t)b * SRACK_BUS_OSC_NPARAMS + SRACK_BUS_OSC_DEPTH];
+                r.offset = F.params[(size_t)b * SRACK_BUS_OSC_NPARAMS + SRACK_BUS_OSC_OFFSET];
+                r.bus = b;
+                r.flags = (F.port[b] == SRACK_OSC_OUT_SINE ? OSC_OUT_SINE : F.port[b] == SRACK_OSC_OUT_SQUARE ? OSC_OUT_SQUARE : OSC_OUT_SAW) | (F.aa[b] ? OSC_AA : 0u);
+                tab.push_back(r);
+            }
+        for (uint32_t b = 0; b < n_buses; b++)
+            if (!F.enabled[b]) off.push_back(b);
+        F.sync.wait();
+        if (!tab.empty()) HIP_TRY(hipMemcpy(F.d_tab.p, tab.data(), sizeof(BusOscBus) * tab.size(), hipMemcpyHostToDevice));
+        if (!off.empty()) HIP_TRY(hipMemcpy((char*)F.d_tab.p + sizeof(BusOscBus) * tab.size(), off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice));
+        F.n_on = (uint32_t)tab.size();
+        F.n_off = (uint32_t)off.size();
+        F.tab_dirty = false;
+    }
+    BusOscArgs a;
+    a.cv = d_cv;
+    a.sync = d_sync;
+    a.out = d_out;
+    a.state = (double*)F.d_state.p;
+    a.tab = (const BusOscBus*)F.d_tab.p;
+    a.off = (const uint32_t*)((const char*)F.d_tab.p + sizeof(BusOscBus) * F.n_on);
+    a.sr = F.rate;
+    a.n = n_samples;
+    a.n_buses = n_buses;
+    a.n_on = F.n_on;
+    a.n_off = F.n_off;
+    launch_bus_osc(a, (hipStream_t)stream);
+    if ((rc = F.sync.end(stream)) != SRACK_OK) return rc;
+    F.last_on = F.n_on;
+    F.last_cv = d_cv != nullptr;
+    F.last_sync = d_sync != nullptr;
+    F.ran = true;
+    return SRACK_OK;
+}
+
+static std::string busosc_note(const BusOsc& F)
+{
+    return F.ran ? " busosc=" + std::to_string(F.last_on) + "[" + (F.last_cv ? "cv" : "-") + (F.last_sync ? "sync" : "-") + "]" : std::string();
+}
+
+// ---- the eight together -------------------------------------------------------------------------------------------------------------
 void device_console_drop(PatchHandle& h)
 {
+    busosc_drop(h.console.busosc);
     busfx_drop(h.console.busfx);
     master_drop(h.console.master);
     device_sends_drop(h);
@@ -710,7 +871,7 @@ void device_console_drop(PatchHandle& h)
 std::string device_console_note(const PatchHandle& h)
 {
     const Console& C = h.console;
-    return sends_note(C.sends) + busvcf_note(C.busvcf) + busvca_note(C.busvca) + busshaper_note(C.busshaper) + busfx_note(C.busfx) + master_note(C.master) + busmeter_note(C.busmeter);
+    return sends_note(C.sends) + busosc_note(C.busosc) + busvcf_note(C.busvcf) + busvca_note(C.busvca) + busshaper_note(C.busshaper) + busfx_note(C.busfx) + master_note(C.master) + busmeter_note(C.busmeter);
 }
 
 }  // namespace srack

@@ -1,5 +1,5 @@
-// console.hpp — the host side of the bus console (console.cpp): the seven stages behind the mixer — sends, reverbs, VCAs, shapers, filters,
-// master section, meters — as they hang off the handle.  None of them is part of the program or of DeviceState (that is replaced on every re-flatten,
+// console.hpp — the host side of the bus console (console.cpp): the eight stages behind the mixer — sends, reverbs, VCAs, shapers, filters,
+// master section, meters, and the oscillators that write their control rows — as they hang off the handle.  None of them is part of the program or of DeviceState (that is replaced on every re-flatten,
 // and a reverb's tail or a filter's state carries on across an edit of the patch); all are dropped with the mix table.
 #pragma once
 #include <cstddef>
@@ -133,6 +133,31 @@ struct BusVca {
     bool ran = false;
 };
 
+// The bus oscillators (srack_buses_set_osc / srack_buses_osc): an OscillatorModule and two MathModules per enabled mix bus.
+// The state is indexed by bus, f64 [SRACK_BUS_OSC_NSTATE][n_buses] on the device between calls, every value as the C ABI hands it out
+// (busosc.hip.h): nothing moves when the enabled set changes.  A disabled bus holds the fresh state there; when the enabled set changes,
+// the state comes to the host, the buses that joined or left are made fresh (`pending`) and it goes up again before the next call's
+// kernel.  reset_osc with phases goes the same way.
+struct BusOsc {
+    bool set = false;
+    std::vector<float> params;      // [n_buses][SRACK_BUS_OSC_NPARAMS], as the host gave them
+    std::vector<int32_t> port;      // [n_buses] SRACK_OSC_OUT_*
+    std::vector<uint8_t> aa;        // [n_buses]
+    std::vector<uint8_t> enabled;   // [n_buses]
+    double rate = 0.0;              // f64(the patch's sample rate)
+    // device side; nothing of it exists before the first srack_buses_osc
+    DeviceBuf d_state;              // f64 [2][n_buses]
+    bool fresh = true;              // every state is to be made fresh before the next call uses it (nothing ran yet, or reset_osc(NULL))
+    std::vector<double> pending;    // [2][n_buses] the state to be uploaded before the next call; empty: none
+    DeviceBuf d_tab;                // BusOscBus [n_on], then u32 [n_off]: the disabled buses
+    bool tab_dirty = true;          // parameters, ports, flags or the enabled set changed
+    uint32_t n_on = 0, n_off = 0;
+    StageSync sync;
+    uint32_t last_on = 0;           // srack_render_info, once a call has run
+    bool last_cv = false, last_sync = false;
+    bool ran = false;
+};
+
 // The bus shapers (srack_buses_set_shaper / srack_buses_shaper): a drive, a NonLinearModule and a make-up gain per mix bus and channel.
 // No state: the setting, and on the device a table entry per bus with the list of the buses that are not OFF behind it (busshape.hip.h).
 struct BusShaper {
@@ -162,10 +187,11 @@ struct Console {
     BusVca busvca;
     BusShaper busshaper;
     BusMeter busmeter;
+    BusOsc busosc;
 };
 
-void device_console_drop(PatchHandle& h);               // all seven stages: settings, device memory, events and notes
-std::string device_console_note(const PatchHandle& h);  // the notes of the stages that have run: sends, busvcf, busvca, busshp, busfx, master, meter
+void device_console_drop(PatchHandle& h);               // all eight stages: settings, device memory, events and notes
+std::string device_console_note(const PatchHandle& h);  // the notes of the stages that have run: sends, busosc, busvcf, busvca, busshp, busfx, master, meter
 // The bus reverbs: one call's work enqueued on `stream` (allocating and zeroing what is missing); state handling without a call.
 int device_buses_reverb(PatchHandle& h, uint32_t n_samples, const float* d_bus_mix, float* d_bus_fx, void* stream);
 void device_busfx_free_bus(PatchHandle& h, uint32_t bus);  // the bus's state, once no call uses it any more
@@ -188,6 +214,12 @@ int device_busvca_modes(PatchHandle& h, const std::vector<int32_t>& mode);  // t
 int device_busvca_state(PatchHandle& h, float* state, uint32_t cap);        // host, f32 [cap][6] as the C ABI hands it out, behind a wait for the last call
 void device_busvca_changed(PatchHandle& h);  // sliders, modes or flags were replaced: the next call uploads the table
 void device_busvca_reset(PatchHandle& h);    // every state fresh, before the next call uses it
+// The bus oscillators: one call's work enqueued on `stream` (allocating and uploading what is missing); state handling without a call.
+int device_buses_osc(PatchHandle& h, uint32_t n_samples, const float* d_cv, const float* d_sync, float* d_out, void* stream);
+int device_busosc_enable(PatchHandle& h, const std::vector<uint8_t>& enabled);  // the enabled set is about to become this: a bus that joins or leaves is made fresh
+int device_busosc_state(PatchHandle& h, double* state, uint32_t cap);           // host, f64 [cap][2] as the C ABI hands it out, behind a wait for the last call
+void device_busosc_changed(PatchHandle& h);                 // parameters, ports, flags or the enabled set were replaced: the next call makes the table anew
+void device_busosc_reset(PatchHandle& h, const double* pos);  // every state fresh (pos null) or at phase pos[b], last true, before the next call uses it
 // The bus shapers: one call's work enqueued on `stream` (allocating and uploading the table when it is missing or changed).
 int device_buses_shaper(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream);
 void device_busshaper_changed(PatchHandle& h);  // constants or modes were replaced: the next call uploads the table

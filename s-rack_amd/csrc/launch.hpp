@@ -99,6 +99,9 @@ void launch_bus_filter(const BusVcfArgs& a, hipStream_t st);
 // ---- the bus VCAs (busvca.hip): a workgroup of eight waves per 64 buses of a.tab, the envelopes on its first wave ----
 void launch_bus_vca(const BusVcaArgs& a, hipStream_t st);
 
+// ---- the bus oscillators (busosc.hip): a lane per enabled bus of a.tab, a wave per workgroup; the disabled buses' rows of a.out zeroed ----
+void launch_bus_osc(const BusOscArgs& a, hipStream_t st);
+
 // ---- the bus shapers (busshape.hip): a wave per stretch of kBusShaperStretch samples of a bus, a.n_units of them, four to a workgroup ----
 void launch_bus_shaper(const BusShaperArgs& a, hipStream_t st);
 

@@ -113,6 +113,31 @@ struct BusVcaArgs {
     uint32_t used;              // min(row_channels, 2): the channels that are processed
 };
 
+// One srack_buses_osc call (busosc.hip.h).  The table has an entry per enabled bus, ordered by (port, antialiasing) and then by bus, so
+// that a wave's 64 lanes share a class wherever they can; behind it lies the list of the disabled buses, whose rows are zeroed.
+struct BusOscBus {
+    double delta;        // the increment without a CV row: 440 * 2^f64(val) / f64(sample rate), the host libm's pow
+    double val;          // f64(val), for the increment with a CV row
+    float depth, offset; // the two Math constants, as given
+    uint32_t bus;        // its row of cv, sync and out, and its place in the state
+    uint32_t flags;      // one of OSC_OUT_SINE / _SQUARE / _SAW, and OSC_AA (program.hpp)
+};
+static_assert(sizeof(BusOscBus) == 32, "the host uploads the table as it stands");
+constexpr int kBusOscFields = 2;  // SRACK_BUS_OSC_NSTATE: pos, sync_last
+struct BusOscArgs {
+    const float* cv;            // [n_buses][n] or null: the CV port is unconnected
+    const float* sync;          // [n_buses][n] or null: the Sync port is unconnected
+    float* out;                 // [n_buses][n]
+    double* state;              // [kBusOscFields][n_buses]: pos, then last as 0.0 / 1.0
+    const BusOscBus* tab;       // [n_on]
+    const uint32_t* off;        // [n_off] the disabled buses
+    double sr;                  // f64(sample rate)
+    uint32_t n;                 // samples
+    uint32_t n_buses;
+    uint32_t n_on;
+    uint32_t n_off;
+};
+
 // One srack_buses_shaper call (busshape.hip.h).  The table has an entry per bus, in bus order; behind it lies the list of the buses
 // that are not OFF, which an in-place call works through (an out-of-place one takes every bus: an OFF bus is a copy).
 struct BusShaperBus {

@@ -3,15 +3,8 @@
 // A row's six numbers are the per-voice statistics' (wave.hip.h: VoiceStats, stats_add, stats_load, stats_store — used as they stand,
 // nothing of the definitions is restated here): SUM and SUM_SQ continue the sequential f64 loop from what the buffer holds, the peaks
 // are read back as f32 and move only upwards, the counts are added.  The sums are serial in time per row, so the only parallelism is
-// across rows, and the shape is busvcf.hip.h's: a lane is a row, a wave 64 rows, a workgroup one wave.
-//
-// The rows are time-minor in memory, the lanes want them row-minor: a tile of 64 rows x 64 samples passes through LDS.
-//   load    row j of the tile as one 256-byte piece, lane l on sample t0 + l (64 loads per lane and tile, whole lines each).  Tile i + 1's
-//           loads are issued before tile i's chain and wait in registers.  A lane past the end of the rows reads the last sample again,
-//           a row past the last row is the wave's last row again: 64 loads back to back, none under a mask, every one inside the rows.
-//   run     lane l reads row l, sample k: LDS word l * 65 + k.  The stride of 65 words puts the 32 lanes of a half-wave on 32 banks
-//           (ds_read_b32 banks by word mod 32, 65 mod 32 = 1).  Eight samples are read ahead of the eight being added.
-// Nothing is stored to the rows.
+// across rows: a lane is a row, and the kernel is the lane-per-row tile loop of bustile.hip.h, eight samples read ahead of the eight
+// being added — a read-only tap: nothing goes back into the tile and nothing is stored to the rows.
 //
 // A lane keeps two sets of VoiceStats in registers: the open window's record and the totals.  Every row shares the stream position, so a
 // window boundary is wave-uniform: a tile is walked in segments that end where the open window ends (or the tile does); at a boundary
@@ -19,7 +12,7 @@
 // entity-minor, f64 [SRACK_STAT_COUNT][n_buses][2] per record: with two used channels a wave's 64 entities lie side by side, 512 bytes
 // per field.  With one used channel the lanes are 16 bytes apart and the channel-1 entries are never touched.
 //
-// Indices: a sample index is t0 + min(lane, n - 1 - t0) < n; a row is r0 + min(j, live - 1) < n_rows = n_buses * used, so the bus is
+// Indices: a sample index is t0 + min(lane, n - 1 - t0) < n; row j of a tile is r0 + min(j, live - 1) < n_rows = n_buses * used, so the bus is
 // below n_buses and the channel below used; a lane at or past `live` loads and stores no record; the window index w starts at
 // first / window and is raised only when a sample of the call lies in the next window, so w <= (first + n - 1) / window < n_windows
 // (the host has checked first + n <= n_windows * window).
@@ -30,28 +23,27 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "bustile.hip.h"
 #include "launch_types.hpp"
 #include "wave.hip.h"
 
 namespace srack {
 
-constexpr int kBusMeterTile = 64;    // samples per tile (and rows per wave)
-constexpr int kBusMeterStride = 65;  // LDS words per tile row: odd, so that a column of 32 rows is 32 banks
 constexpr int kBusMeterAhead = 8;    // samples a lane reads from LDS at a time
-static_assert(SRACK_BUS_METER_MIN_WINDOW >= kBusMeterTile, "a tile holds one window boundary at the most");
+static_assert(SRACK_BUS_METER_MIN_WINDOW >= kRowTile, "a tile holds one window boundary at the most");
 static_assert(kStatCount == SRACK_STAT_COUNT, "a record is VoiceStats field by field");
 
 // grid (ceil(n_buses * kUsed / 64)), block 64.  kUsed: a.used, 1 or 2.  kLevels / kTotals: a.levels / a.totals is given.
 template <int kUsed, bool kLevels, bool kTotals>
 __global__ __launch_bounds__(64) void bus_meter(const BusMeterArgs a)
 {
-    __shared__ float s_x[kBusMeterTile * kBusMeterStride];
+    __shared__ float s_x[kRowTileWords];
     const uint32_t lane = threadIdx.x;
     const uint32_t n_rows = a.n_buses * (uint32_t)kUsed;
     const uint32_t r0 = blockIdx.x * 64u;
     const uint32_t live = min(64u, n_rows - r0);  // rows of this wave (wave-uniform)
     const bool on = lane < live;
-    const uint32_t x_at = lane * kBusMeterStride;
+    const uint32_t x_at = lane * kRowTileStride;
     // this lane's entity: (bus, channel) of its row, in a frame of [n_buses][2]
     const uint32_t my_row = r0 + (on ? lane : 0u);
     const size_t ents = (size_t)a.n_buses * 2;
@@ -72,19 +64,16 @@ __global__ __launch_bounds__(64) void bus_meter(const BusMeterArgs a)
         if (on) stats_load(tot, a.totals + ent, ents);
     }
 
-    float pre[kBusMeterTile];  // the tile loaded ahead: row j, sample t0 + lane
-    auto fetch = [&](uint32_t t0) {
-        const uint32_t tl = min(lane, a.n - 1u - t0);
-#pragma unroll
-        for (int j = 0; j < kBusMeterTile; j++) {
-            const uint32_t r = r0 + min((uint32_t)j, live - 1u);  // (wave-uniform: the address is a scalar base and the lane's sample)
-            const size_t base = ((size_t)(r / kUsed) * a.row_channels + r % kUsed) * a.n;
-            pre[j] = (a.rows + base + t0)[tl];
-        }
+    float pre[kRowTile];  // the tile fetched ahead
+    auto row = [&](int j) {  // (wave-uniform: the address is a scalar base and the lane's sample; past the last row the last row again)
+        const uint32_t r = r0 + min((uint32_t)j, live - 1u);
+        return ((size_t)(r / kUsed) * a.row_channels + r % kUsed) * a.n;
     };
+    auto fetch = [&](uint32_t t0) { bustile_fetch(pre, a.rows, t0, bustile_sample(lane, a.n, t0), row); };
+    // (a segment begins anywhere: every word is held to the tile, the last chunk reads its last word again)
     auto read8 = [&](uint32_t k0, float (&x)[kBusMeterAhead]) {
 #pragma unroll
-        for (int q = 0; q < kBusMeterAhead; q++) x[q] = s_x[x_at + min(k0 + q, (uint32_t)(kBusMeterTile - 1))];
+        for (int q = 0; q < kBusMeterAhead; q++) x[q] = s_x[x_at + min(k0 + q, (uint32_t)(kRowTile - 1))];
     };
     auto add = [&](float x) {
         if constexpr (kLevels) stats_add(win, x);
@@ -95,9 +84,9 @@ __global__ __launch_bounds__(64) void bus_meter(const BusMeterArgs a)
         constexpr bool kFull = decltype(full)::value;
         float x[kBusMeterAhead];
         read8(kFull ? 0u : kb, x);
-        for (uint32_t k0 = kFull ? 0u : kb; k0 < (kFull ? (uint32_t)kBusMeterTile : ke); k0 += kBusMeterAhead) {
+        for (uint32_t k0 = kFull ? 0u : kb; k0 < (kFull ? (uint32_t)kRowTile : ke); k0 += kBusMeterAhead) {
             float xn[kBusMeterAhead];
-            read8(k0 + kBusMeterAhead, xn);  // (clamped to the tile: the last chunk reads its last word again)
+            read8(k0 + kBusMeterAhead, xn);
 #pragma unroll
             for (int q = 0; q < kBusMeterAhead; q++)
                 if (kFull || k0 + q < ke) add(x[q]);
@@ -106,21 +95,20 @@ __global__ __launch_bounds__(64) void bus_meter(const BusMeterArgs a)
         }
     };
 
-    const uint32_t n_tiles = (a.n + kBusMeterTile - 1) / kBusMeterTile;
+    const uint32_t n_tiles = (a.n + kRowTile - 1) / kRowTile;
     fetch(0);
     for (uint32_t i = 0; i < n_tiles; i++) {
-        const uint32_t t0 = i * kBusMeterTile;
-        const uint32_t len = min((uint32_t)kBusMeterTile, a.n - t0);
-#pragma unroll
-        for (int j = 0; j < kBusMeterTile; j++) s_x[j * kBusMeterStride + lane] = pre[j];
+        const uint32_t t0 = i * kRowTile;
+        const uint32_t len = min((uint32_t)kRowTile, a.n - t0);
+        bustile_turn(s_x, pre, lane);
         __syncthreads();
-        if (i + 1 < n_tiles) fetch(t0 + kBusMeterTile);
+        if (i + 1 < n_tiles) fetch(t0 + kRowTile);
 
         uint32_t k = 0;
         while (k < len) {  // (wave-uniform: segments that end with the open window or with the tile)
             const uint32_t m = min(len - k, left);
-            if (m == (uint32_t)kBusMeterTile)
-                run(std::true_type{}, 0u, (uint32_t)kBusMeterTile);
+            if (m == (uint32_t)kRowTile)
+                run(std::true_type{}, 0u, (uint32_t)kRowTile);
             else
                 run(std::false_type{}, k, k + m);
             k += m;

@@ -30,13 +30,14 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "bustile.hip.h"
 #include "launch_types.hpp"
 #include "modules.hip.h"
 
 namespace srack {
 
-constexpr int kBusVcaTile = 64;      // samples per tile, and buses per workgroup
-constexpr int kBusVcaStride = 65;    // LDS words per bus of the tile: odd
+constexpr int kBusVcaTile = kRowTile;          // samples per tile, and buses per workgroup: the tile's geometry is bustile.hip.h's,
+constexpr int kBusVcaStride = kRowTileStride;  // LDS words per bus of the tile; the pipeline around it is this kernel's own
 #ifndef SRACK_BUSVCA_WAVES           // (variants of the three choices below were built to measure them: notes/r20.md)
 #define SRACK_BUSVCA_WAVES 8
 #endif

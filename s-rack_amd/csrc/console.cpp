@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -65,6 +66,97 @@ void DeviceBuf::release()
     if (p) (void)hipFree(p);
     p = nullptr;
     bytes = 0;
+}
+
+// A stage's device memory and its event, once no call uses them any more; the stage is as it was before it was set.
+template <class Stage>
+static void stage_drop(Stage& F, std::initializer_list<DeviceBuf*> bufs)
+{
+    F.sync.wait();
+    for (DeviceBuf* b : bufs) b->release();
+    F.sync.destroy();
+    F = Stage();
+}
+
+// ---- state by bus, for the stages that keep it that way (the VCAs, the oscillators) ---------------------------------------------------
+template <class T, int kFields>
+std::vector<T> BusState<T, kFields>::filled(const Fresh& one, size_t n)
+{
+    std::vector<T> s((size_t)kFields * n);
+    for (int f = 0; f < kFields; f++) std::fill(s.begin() + (size_t)f * n, s.begin() + (size_t)(f + 1) * n, one[f]);
+    return s;
+}
+
+template <class T, int kFields>
+void BusState<T, kFields>::reset()
+{
+    pending.clear();
+    fresh = true;  // uploaded before the next call's kernel
+}
+
+template <class T, int kFields>
+int BusState<T, kFields>::fetch(StageSync& sync, const Fresh& one, size_t n, std::vector<T>& out)
+{
+    if (!pending.empty()) {
+        out = pending;
+        return SRACK_OK;
+    }
+    out = filled(one, n);
+    if (all_fresh()) return SRACK_OK;
+    sync.wait();
+    HIP_TRY(hipMemcpy(out.data(), d_state.p, sizeof(T) * out.size(), hipMemcpyDeviceToHost));
+    return SRACK_OK;
+}
+
+template <class T, int kFields>
+template <class Owns, class WillOwn>
+int BusState<T, kFields>::refresh(StageSync& sync, const Fresh& one, size_t n, Owns owns, WillOwn will_own)
+{
+    if (all_fresh()) return SRACK_OK;  // fresh stays fresh
+    bool moved = false;
+    for (size_t b = 0; b < n; b++) moved = moved || (owns(b) != will_own(b));
+    if (!moved) return SRACK_OK;
+    std::vector<T> cur;
+    const int rc = fetch(sync, one, n, cur);
+    if (rc != SRACK_OK) return rc;
+    for (size_t b = 0; b < n; b++)
+        if (!owns(b) || !will_own(b))
+            for (int f = 0; f < kFields; f++) cur[(size_t)f * n + b] = one[f];
+    pending = std::move(cur);
+    return SRACK_OK;
+}
+
+template <class T, int kFields>
+int BusState<T, kFields>::alloc(StageSync& sync, size_t n, const char* who, const char* what)
+{
+    const int rc = d_state.grow(sync, sizeof(T) * kFields * n, who, what);
+    if (rc == SRACK_OK && pending.empty()) fresh = true;
+    return rc;
+}
+
+template <class T, int kFields>
+int BusState<T, kFields>::upload(StageSync& sync, const Fresh& one, size_t n)
+{
+    if (pending.empty() && !fresh) return SRACK_OK;
+    const std::vector<T> up = pending.empty() ? filled(one, n) : pending;
+    sync.wait();
+    HIP_TRY(hipMemcpy(d_state.p, up.data(), sizeof(T) * kFields * n, hipMemcpyHostToDevice));
+    pending.clear();
+    fresh = false;
+    return SRACK_OK;
+}
+
+template <class T, int kFields>
+template <class Owns>
+int BusState<T, kFields>::hand_out(StageSync& sync, const Fresh& one, size_t n_buses, Owns owns, T* state, uint32_t cap)
+{
+    std::vector<T> cur;
+    const int rc = fetch(sync, one, n_buses, cur);
+    if (rc != SRACK_OK) return rc;
+    const size_t n = std::min<size_t>(cap, n_buses);
+    for (size_t b = 0; b < n; b++)
+        for (int f = 0; f < kFields; f++) state[b * kFields + f] = owns(b) ? cur[(size_t)f * n_buses + b] : one[f];
+    return SRACK_OK;
 }
 
 // ---- the bus reverbs (busfx.hip.h, launched through launch_bus_reverb) ----------------------------------------------------------------
@@ -162,15 +254,6 @@ static std::string busfx_note(const BusFx& F)
 // event per call.
 void device_master_gains_changed(PatchHandle& h) { h.console.master.gain_dirty = true; }
 
-static void master_drop(Master& M)
-{
-    M.sync.wait();
-    M.d_gain.release();
-    M.d_runs.release();
-    M.sync.destroy();
-    M = Master();
-}
-
 int device_buses_master(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_master, double* d_master_stats, void* stream)
 {
     Master& M = h.console.master;
@@ -219,11 +302,7 @@ void device_sends_changed(PatchHandle& h) { h.console.sends.tab_dirty = true; }
 void device_sends_drop(PatchHandle& h)
 {
     Sends& S = h.console.sends;
-    S.sync.wait();
-    S.d_tab.release();
-    S.d_scratch.release();
-    S.sync.destroy();
-    S = Sends();
+    stage_drop(S, {&S.d_tab, &S.d_scratch});
 }
 
 int device_buses_send(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, float* d_out, void* stream)
@@ -357,15 +436,6 @@ int device_busvcf_state(PatchHandle& h, float* state, uint32_t cap)
     return SRACK_OK;
 }
 
-static void busvcf_drop(BusVcf& F)
-{
-    F.sync.wait();
-    F.d_state.release();
-    F.d_tab.release();
-    F.sync.destroy();
-    F = BusVcf();
-}
-
 int device_buses_filter(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream)
 {
     BusVcf& F = h.console.busvcf;
@@ -456,78 +526,27 @@ static std::string busvcf_note(const BusVcf& F)
 // up again after a change of the setting, the state after a change of the set of GATE buses or a reset — both behind a host-side wait
 // for the last call's kernel, which may still be using them.  A tick session of unchanged VCAs is the launch and one event per call.
 
-// ADSRModule::new's state, f32 [6][n]: phase 0, mode None, r_val 0, from_a_val 0, the rate, TransitionDetector.last true
-static std::vector<float> busvca_fresh(const BusVca& F, size_t n)
+// ADSRModule::new's state: phase 0, mode None, r_val 0, from_a_val 0, the rate, TransitionDetector.last true
+static BusState<float, kBusVcaFields>::Fresh busvca_fresh(const BusVca& F)
 {
-    const float one[kBusVcaFields] = {0.0f, (float)SRACK_ADSR_MODE_NONE, 0.0f, 0.0f, F.rate, 1.0f};
-    std::vector<float> s((size_t)kBusVcaFields * n);
-    for (int f = 0; f < kBusVcaFields; f++) std::fill(s.begin() + (size_t)f * n, s.begin() + (size_t)(f + 1) * n, one[f]);
-    return s;
-}
-
-static bool busvca_all_fresh(const BusVca& F) { return F.pending.empty() && (!F.d_state.p || F.fresh); }
-
-// The state as it stands, f32 [6][n]
-static int busvca_fetch(BusVca& F, size_t n, std::vector<float>& out)
-{
-    if (!F.pending.empty()) {
-        out = F.pending;
-        return SRACK_OK;
-    }
-    out = busvca_fresh(F, n);
-    if (busvca_all_fresh(F)) return SRACK_OK;
-    F.sync.wait();
-    HIP_TRY(hipMemcpy(out.data(), F.d_state.p, sizeof(float) * out.size(), hipMemcpyDeviceToHost));
-    return SRACK_OK;
+    return {0.0f, (float)SRACK_ADSR_MODE_NONE, 0.0f, 0.0f, F.rate, 1.0f};
 }
 
 void device_busvca_changed(PatchHandle& h) { h.console.busvca.tab_dirty = true; }
 
-void device_busvca_reset(PatchHandle& h)
-{
-    h.console.busvca.pending.clear();
-    h.console.busvca.fresh = true;  // uploaded before the next call's kernel
-}
+void device_busvca_reset(PatchHandle& h) { h.console.busvca.state.reset(); }
 
 int device_busvca_modes(PatchHandle& h, const std::vector<int32_t>& mode)
 {
     BusVca& F = h.console.busvca;
-    if (!F.set || busvca_all_fresh(F)) return SRACK_OK;  // fresh stays fresh
-    const size_t n = h.n_buses;
-    bool moved = false;
-    for (size_t b = 0; b < n; b++) moved = moved || ((F.mode[b] == SRACK_BUS_VCA_GATE) != (mode[b] == SRACK_BUS_VCA_GATE));
-    if (!moved) return SRACK_OK;
-    std::vector<float> cur;
-    const int rc = busvca_fetch(F, n, cur);
-    if (rc != SRACK_OK) return rc;
-    const std::vector<float> fresh = busvca_fresh(F, 1);
-    for (size_t b = 0; b < n; b++)  // a bus that stays GATE keeps its state; one that becomes GATE starts fresh; one that leaves drops it
-        if (F.mode[b] != SRACK_BUS_VCA_GATE || mode[b] != SRACK_BUS_VCA_GATE)
-            for (int f = 0; f < kBusVcaFields; f++) cur[(size_t)f * n + b] = fresh[f];
-    F.pending = std::move(cur);
-    return SRACK_OK;
+    if (!F.set) return SRACK_OK;
+    return F.state.refresh(F.sync, busvca_fresh(F), h.n_buses, [&](size_t b) { return F.mode[b] == SRACK_BUS_VCA_GATE; }, [&](size_t b) { return mode[b] == SRACK_BUS_VCA_GATE; });
 }
 
 int device_busvca_state(PatchHandle& h, float* state, uint32_t cap)
 {
     BusVca& F = h.console.busvca;
-    const size_t n_buses = h.n_buses, n = std::min<size_t>(cap, n_buses);
-    std::vector<float> cur;
-    const int rc = busvca_fetch(F, n_buses, cur);
-    if (rc != SRACK_OK) return rc;
-    const std::vector<float> fresh = busvca_fresh(F, 1);
-    for (size_t b = 0; b < n; b++)
-        for (int f = 0; f < kBusVcaFields; f++) state[b * kBusVcaFields + f] = F.mode[b] == SRACK_BUS_VCA_GATE ? cur[(size_t)f * n_buses + b] : fresh[f];
-    return SRACK_OK;
-}
-
-static void busvca_drop(BusVca& F)
-{
-    F.sync.wait();
-    F.d_state.release();
-    F.d_tab.release();
-    F.sync.destroy();
-    F = BusVca();
+    return F.state.hand_out(F.sync, busvca_fresh(F), h.n_buses, [&](size_t b) { return F.mode[b] == SRACK_BUS_VCA_GATE; }, state, cap);
 }
 
 int device_buses_vca(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_ctl, float* d_out, float* d_env, void* stream)
@@ -536,20 +555,13 @@ int device_buses_vca(PatchHandle& h, uint32_t n_samples, const float* d_rows, ui
     const uint32_t n_buses = h.n_buses;
     int rc;
     if ((rc = F.sync.begin(stream)) != SRACK_OK) return rc;
-    const size_t state_bytes = sizeof(float) * kBusVcaFields * n_buses, tab_bytes = sizeof(BusVcaBus) * n_buses;
-    if (!F.d_state.p || !F.d_tab.p) {  // (n_buses is fixed while the VCAs live: another n_buses drops them)
-        if ((rc = F.d_state.grow(F.sync, state_bytes, "buses_vca", "the VCAs' state")) != SRACK_OK) return rc;
+    const size_t tab_bytes = sizeof(BusVcaBus) * n_buses;
+    if (!F.state.d_state.p || !F.d_tab.p) {  // (n_buses is fixed while the VCAs live: another n_buses drops them)
+        if ((rc = F.state.alloc(F.sync, n_buses, "buses_vca", "the VCAs' state")) != SRACK_OK) return rc;
         if ((rc = F.d_tab.grow(F.sync, tab_bytes, "buses_vca", "the VCAs' table")) != SRACK_OK) return rc;
         F.tab_dirty = true;
-        if (F.pending.empty()) F.fresh = true;
     }
-    if (!F.pending.empty() || F.fresh) {
-        const std::vector<float> up = F.pending.empty() ? busvca_fresh(F, n_buses) : F.pending;
-        F.sync.wait();
-        HIP_TRY(hipMemcpy(F.d_state.p, up.data(), state_bytes, hipMemcpyHostToDevice));
-        F.pending.clear();
-        F.fresh = false;
-    }
+    if ((rc = F.state.upload(F.sync, busvca_fresh(F), n_buses)) != SRACK_OK) return rc;
     uint32_t n_on = 0, n_gated = 0;
     for (uint32_t b = 0; b < n_buses; b++) {
         n_on += F.mode[b] != SRACK_BUS_VCA_OFF;
@@ -576,7 +588,7 @@ int device_buses_vca(PatchHandle& h, uint32_t n_samples, const float* d_rows, ui
     a.ctl = d_ctl;
     a.out = d_out;
     a.env = d_env;
-    a.state = (float*)F.d_state.p;
+    a.state = (float*)F.state.d_state.p;
     a.tab = (const BusVcaBus*)F.d_tab.p;
     a.rate = F.rate;
     a.n = n_samples;
@@ -602,14 +614,6 @@ static std::string busvca_note(const BusVca& F)
 // setting, behind a host-side wait for the last call's kernel, which may still be reading it.  A tick session of unchanged shapers is
 // the launch and one event per call.
 void device_busshaper_changed(PatchHandle& h) { h.console.busshaper.tab_dirty = true; }
-
-static void busshaper_drop(BusShaper& F)
-{
-    F.sync.wait();
-    F.d_tab.release();
-    F.sync.destroy();
-    F = BusShaper();
-}
 
 int device_buses_shaper(PatchHandle& h, uint32_t n_samples, const float* d_rows, uint32_t row_channels, const float* d_cv, float* d_out, void* stream)
 {
@@ -703,83 +707,34 @@ static std::string busmeter_note(const BusMeter& F)
 // both behind a host-side wait for the last call's kernel, which may still be using them.  A tick session of unchanged oscillators is
 // the launch and one event per call.
 
-// OscillatorModule::new's state, f64 [2][n]: pos 0.0, TransitionDetector.last true
-static std::vector<double> busosc_fresh(size_t n)
-{
-    std::vector<double> s((size_t)kBusOscFields * n, 0.0);
-    std::fill(s.begin() + n, s.end(), 1.0);
-    return s;
-}
-
-static bool busosc_all_fresh(const BusOsc& F) { return F.pending.empty() && (!F.d_state.p || F.fresh); }
-
-// The state as it stands, f64 [2][n]
-static int busosc_fetch(BusOsc& F, size_t n, std::vector<double>& out)
-{
-    if (!F.pending.empty()) {
-        out = F.pending;
-        return SRACK_OK;
-    }
-    out = busosc_fresh(n);
-    if (busosc_all_fresh(F)) return SRACK_OK;
-    F.sync.wait();
-    HIP_TRY(hipMemcpy(out.data(), F.d_state.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost));
-    return SRACK_OK;
-}
+// OscillatorModule::new's state: pos 0.0, TransitionDetector.last true
+static const BusState<double, kBusOscFields>::Fresh kBusOscFresh = {0.0, 1.0};
 
 void device_busosc_changed(PatchHandle& h) { h.console.busosc.tab_dirty = true; }
 
 void device_busosc_reset(PatchHandle& h, const double* pos)
 {
     BusOsc& F = h.console.busosc;
-    F.pending.clear();
-    F.fresh = true;  // uploaded before the next call's kernel
+    F.state.reset();
     if (!pos) return;
     const size_t n = h.n_buses;
-    F.pending = busosc_fresh(n);
+    F.state.pending = F.state.filled(kBusOscFresh, n);
     for (size_t b = 0; b < n; b++)
-        if (F.enabled[b]) F.pending[b] = pos[b];  // (a disabled bus holds the fresh state)
-    F.fresh = false;
+        if (F.enabled[b]) F.state.pending[b] = pos[b];  // (a disabled bus holds the fresh state)
+    F.state.fresh = false;
 }
 
 int device_busosc_enable(PatchHandle& h, const std::vector<uint8_t>& enabled)
 {
     BusOsc& F = h.console.busosc;
-    if (!F.set || busosc_all_fresh(F)) return SRACK_OK;  // fresh stays fresh
-    const size_t n = h.n_buses;
-    bool moved = false;
-    for (size_t b = 0; b < n; b++) moved = moved || ((F.enabled[b] != 0) != (enabled[b] != 0));
-    if (!moved) return SRACK_OK;
-    std::vector<double> cur;
-    const int rc = busosc_fetch(F, n, cur);
-    if (rc != SRACK_OK) return rc;
-    for (size_t b = 0; b < n; b++)  // a bus that stays enabled keeps its state; one that becomes enabled starts fresh; one that leaves drops it
-        if (!F.enabled[b] || !enabled[b]) cur[b] = 0.0, cur[n + b] = 1.0;
-    F.pending = std::move(cur);
-    return SRACK_OK;
+    if (!F.set) return SRACK_OK;
+    return F.state.refresh(F.sync, kBusOscFresh, h.n_buses, [&](size_t b) { return F.enabled[b] != 0; }, [&](size_t b) { return enabled[b] != 0; });
 }
 
 int device_busosc_state(PatchHandle& h, double* state, uint32_t cap)
 {
     BusOsc& F = h.console.busosc;
-    const size_t n_buses = h.n_buses, n = std::min<size_t>(cap, n_buses);
-    std::vector<double> cur;
-    const int rc = busosc_fetch(F, n_buses, cur);
-    if (rc != SRACK_OK) return rc;
-    for (size_t b = 0; b < n; b++) {
-        state[b * kBusOscFields + 0] = F.enabled[b] ? cur[b] : 0.0;
-        state[b * kBusOscFields + 1] = F.enabled[b] ? cur[n_buses + b] : 1.0;
-    }
-    return SRACK_OK;
-}
-
-static void busosc_drop(BusOsc& F)
-{
-    F.sync.wait();
-    F.d_state.release();
-    F.d_tab.release();
-    F.sync.destroy();
-    F = BusOsc();
+    return F.state.hand_out(F.sync, kBusOscFresh, h.n_buses, [&](size_t b) { return F.enabled[b] != 0; }, state, cap);
 }
 
 int device_buses_osc(PatchHandle& h, uint32_t n_samples, const float* d_cv, const float* d_sync, float* d_out, void* stream)
@@ -788,21 +743,13 @@ int device_buses_osc(PatchHandle& h, uint32_t n_samples, const float* d_cv, cons
     const uint32_t n_buses = h.n_buses;
     int rc;
     if ((rc = F.sync.begin(stream)) != SRACK_OK) return rc;
-    const size_t state_bytes = sizeof(double) * kBusOscFields * n_buses;
     const size_t tab_bytes = sizeof(BusOscBus) * n_buses + sizeof(uint32_t) * n_buses;  // (n_on + n_off = n_buses, and an entry is the larger)
-    if (!F.d_state.p || !F.d_tab.p) {  // (n_buses is fixed while the oscillators live: another n_buses drops them)
-        if ((rc = F.d_state.grow(F.sync, state_bytes, "buses_osc", "the oscillators' state")) != SRACK_OK) return rc;
+    if (!F.state.d_state.p || !F.d_tab.p) {  // (n_buses is fixed while the oscillators live: another n_buses drops them)
+        if ((rc = F.state.alloc(F.sync, n_buses, "buses_osc", "the oscillators' state")) != SRACK_OK) return rc;
         if ((rc = F.d_tab.grow(F.sync, tab_bytes, "buses_osc", "the oscillators' table")) != SRACK_OK) return rc;
         F.tab_dirty = true;
-        if (F.pending.empty()) F.fresh = true;
     }
-    if (!F.pending.empty() || F.fresh) {
-        const std::vector<double> up = F.pending.empty() ? busosc_fresh(n_buses) : F.pending;
-        F.sync.wait();
-        HIP_TRY(hipMemcpy(F.d_state.p, up.data(), state_bytes, hipMemcpyHostToDevice));
-        F.pending.clear();
-        F.fresh = false;
-    }
+    if ((rc = F.state.upload(F.sync, kBusOscFresh, n_buses)) != SRACK_OK) return rc;
     if (F.tab_dirty) {
         std::vector<BusOscBus> tab;
         std::vector<uint32_t> off;
@@ -833,7 +780,7 @@ int device_buses_osc(PatchHandle& h, uint32_t n_samples, const float* d_cv, cons
     a.cv = d_cv;
     a.sync = d_sync;
     a.out = d_out;
-    a.state = (double*)F.d_state.p;
+    a.state = (double*)F.state.d_state.p;
     a.tab = (const BusOscBus*)F.d_tab.p;
     a.off = (const uint32_t*)((const char*)F.d_tab.p + sizeof(BusOscBus) * F.n_on);
     a.sr = F.rate;
@@ -858,14 +805,15 @@ static std::string busosc_note(const BusOsc& F)
 // ---- the eight together -------------------------------------------------------------------------------------------------------------
 void device_console_drop(PatchHandle& h)
 {
-    busosc_drop(h.console.busosc);
-    busfx_drop(h.console.busfx);
-    master_drop(h.console.master);
+    Console& C = h.console;
+    stage_drop(C.busosc, {&C.busosc.state.d_state, &C.busosc.d_tab});
+    busfx_drop(C.busfx);
+    stage_drop(C.master, {&C.master.d_gain, &C.master.d_runs});
     device_sends_drop(h);
-    busvcf_drop(h.console.busvcf);
-    busvca_drop(h.console.busvca);
-    busshaper_drop(h.console.busshaper);
-    h.console.busmeter = BusMeter();
+    stage_drop(C.busvcf, {&C.busvcf.d_state, &C.busvcf.d_tab});
+    stage_drop(C.busvca, {&C.busvca.state.d_state, &C.busvca.d_tab});
+    stage_drop(C.busshaper, {&C.busshaper.d_tab});
+    C.busmeter = BusMeter();
 }
 
 std::string device_console_note(const PatchHandle& h)

@@ -2,11 +2,13 @@
 // master section, meters, and the oscillators that write their control rows — as they hang off the handle.  None of them is part of the program or of DeviceState (that is replaced on every re-flatten,
 // and a reverb's tail or a filter's state carries on across an edit of the patch); all are dropped with the mix table.
 #pragma once
+#include <array>
 #include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
 
+#include "../../include/srack_hip.h"
 #include "program.hpp"
 
 namespace srack {
@@ -32,6 +34,31 @@ struct DeviceBuf {
     // one in place, says "<who>: out of device memory for <what> (<want> bytes)" and returns SRACK_ERR_NOMEM.  The contents do not move.
     int grow(StageSync& sync, size_t want, const char* who, const char* what);
     void release();
+};
+
+// The state of a stage that keeps kFields values of T per bus, indexed by bus: T [kFields][n_buses] on the device between calls, every
+// value as the C ABI hands it out, so nothing moves when the set of buses that own state changes.  A bus that owns none holds the fresh
+// state there — what that is, field by field, the stage says with every call (`one`).  When the set changes, the state comes to the
+// host, the buses that joined or left are made fresh (`pending`) and it goes up again before the next call's kernel.  Whatever reads or
+// rewrites the device's copy waits on the host for the last call's kernels first (console.cpp).
+template <class T, int kFields>
+struct BusState {
+    using Fresh = std::array<T, kFields>;
+    // device side; nothing of it exists before the stage's first call
+    DeviceBuf d_state;       // T [kFields][n_buses]
+    bool fresh = true;       // every state is to be made fresh before the next call uses it (nothing ran yet, or a reset)
+    std::vector<T> pending;  // [kFields][n_buses] the state to be uploaded before the next call; empty: none
+    static std::vector<T> filled(const Fresh& one, size_t n);  // [kFields][n], every bus fresh
+    bool all_fresh() const { return pending.empty() && (!d_state.p || fresh); }
+    void reset();            // every state fresh, before the next call uses it
+    int fetch(StageSync& sync, const Fresh& one, size_t n, std::vector<T>& out);  // the state as it stands: pending, or fresh, or the device's
+    // owns(b) is about to become will_own(b): a bus for which it changes is made fresh; one that keeps its state keeps it
+    template <class Owns, class WillOwn>
+    int refresh(StageSync& sync, const Fresh& one, size_t n, Owns owns, WillOwn will_own);
+    int alloc(StageSync& sync, size_t n, const char* who, const char* what);  // before a call: the device's copy exists (DeviceBuf::grow) ...
+    int upload(StageSync& sync, const Fresh& one, size_t n);                  // ... and holds what is pending, or fresh states after a reset
+    template <class Owns>
+    int hand_out(StageSync& sync, const Fresh& one, size_t n_buses, Owns owns, T* state, uint32_t cap);  // host, [cap][kFields]; a bus that owns none reads fresh
 };
 
 // The bus reverbs (srack_buses_set_reverb / srack_buses_reverb): one Freeverb per mix bus.
@@ -112,20 +139,15 @@ struct BusVcf {
 };
 
 // The bus VCAs (srack_buses_set_vca / srack_buses_vca): an ADSRModule and its VCAModules per mix bus.
-// The state is indexed by bus, f32 [SRACK_BUS_VCA_NSTATE][n_buses] on the device between calls, every value as the C ABI hands it out
-// (busvca.hip.h): nothing moves when modes change.  A bus that is not GATE holds the fresh state there; when the set of GATE buses
-// changes, the state comes to the host, the buses that joined or left are made fresh (`pending`) and it goes up again before the
-// next call's kernel.
+// The state is a BusState of f32 [SRACK_BUS_VCA_NSTATE] per bus (busvca.hip.h) that the GATE buses own.
 struct BusVca {
     bool set = false;
     std::vector<float> params;      // [n_buses][SRACK_BUS_VCA_NPARAMS], as the host gave them
     std::vector<int32_t> mode;      // [n_buses] SRACK_BUS_VCA_OFF / _CV / _GATE
     std::vector<uint8_t> negative;  // [n_buses]
     float rate = 0.0f;              // the f32 sample rate a fresh ADSRModule of this patch carries (Graph::adsr_sample_rate)
+    BusState<float, SRACK_BUS_VCA_NSTATE> state;
     // device side; nothing of it exists before the first srack_buses_vca
-    DeviceBuf d_state;              // f32 [6][n_buses]
-    bool fresh = true;              // every state is to be made fresh before the next call uses it (nothing ran yet, or reset_vca)
-    std::vector<float> pending;     // [6][n_buses] the state to be uploaded before the next call; empty: none
     DeviceBuf d_tab;                // BusVcaBus [n_buses]
     bool tab_dirty = true;          // sliders, modes or flags changed
     StageSync sync;
@@ -134,10 +156,8 @@ struct BusVca {
 };
 
 // The bus oscillators (srack_buses_set_osc / srack_buses_osc): an OscillatorModule and two MathModules per enabled mix bus.
-// The state is indexed by bus, f64 [SRACK_BUS_OSC_NSTATE][n_buses] on the device between calls, every value as the C ABI hands it out
-// (busosc.hip.h): nothing moves when the enabled set changes.  A disabled bus holds the fresh state there; when the enabled set changes,
-// the state comes to the host, the buses that joined or left are made fresh (`pending`) and it goes up again before the next call's
-// kernel.  reset_osc with phases goes the same way.
+// The state is a BusState of f64 [SRACK_BUS_OSC_NSTATE] per bus (busosc.hip.h) that the enabled buses own; reset_osc with phases goes
+// up as `pending`, too.
 struct BusOsc {
     bool set = false;
     std::vector<float> params;      // [n_buses][SRACK_BUS_OSC_NPARAMS], as the host gave them
@@ -145,10 +165,8 @@ struct BusOsc {
     std::vector<uint8_t> aa;        // [n_buses]
     std::vector<uint8_t> enabled;   // [n_buses]
     double rate = 0.0;              // f64(the patch's sample rate)
+    BusState<double, SRACK_BUS_OSC_NSTATE> state;
     // device side; nothing of it exists before the first srack_buses_osc
-    DeviceBuf d_state;              // f64 [2][n_buses]
-    bool fresh = true;              // every state is to be made fresh before the next call uses it (nothing ran yet, or reset_osc(NULL))
-    std::vector<double> pending;    // [2][n_buses] the state to be uploaded before the next call; empty: none
     DeviceBuf d_tab;                // BusOscBus [n_on], then u32 [n_off]: the disabled buses
     bool tab_dirty = true;          // parameters, ports, flags or the enabled set changed
     uint32_t n_on = 0, n_off = 0;
